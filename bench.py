@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched CraftingWorld step/reset hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     N>1 works both ways: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env), or started plainly -- then this process, before it touches
     torch or HIP, starts N fresh child ranks (gym_craftingworld_amd/launch.py), relays rank 0's JSON line and exits with
@@ -16,7 +16,9 @@ ranks with no data-path collective (weak scaling: 65 536 envs per GPU); the only
 are the timing barrier and the max-over-ranks of the elapsed time.  `value` is computed from the slowest rank's DEVICE time for the K steps (two events
 on the launch stream inside the barrier + synchronize bracket); `value_wall` from the wall clock around the bracket (it also holds the closing barrier).
 
-Prints ONE JSON line on rank 0 (contract in the task prompt), with
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given (dump_outputs) and
+prints ONE JSON line on rank 0: metric, value, unit, ms_per_step, higher_is_better, dtype, the timing and the configuration.
+Everything below is measured only with --full, after the K timed steps (and after the dump), and added to the same line:
   roofline     -- dominant kernel (cw_render_pieces_kernel<raster, frames per job>: the sweep of the observation array) vs the HBM roof, from
                   HIP events recorded by the library on the launch stream (cw_profile_begin/end) over a second, identical
                   K-step region (the first region, without events, gives `value`); step_frac = the WHOLE step against the same roof;
@@ -32,7 +34,8 @@ Prints ONE JSON line on rank 0 (contract in the task prompt), with
   metric_window_desync -- the same window with the episode phases spread out (about N/max_steps envs finish on EVERY step: the steady
                   state of a run whose policy finishes episodes), same process, with its own roofline fraction;
   single_env   -- BASELINE configs[0]: make('craftingworld-v3'), 200 random steps through the N=1 facade;
-  per_rank_ms_per_step -- every rank's own time for the timed region (gathered once, after it): stragglers show in a scaling run.
+  per_rank     -- every rank's clock, guard, sweep time and NUMA binding.
+per_rank_ms_per_step (every rank's own time for the timed region, gathered once after it: stragglers show in a scaling run) is on every line.
 The JSON line is the LAST line of rank 0's stdout; everything else any library prints to fd 1 is sent to stderr.
 """
 import argparse
@@ -258,6 +261,53 @@ def place_short_region(prewarm, warmup, steps, max_steps):
     return prewarm
 
 
+def dump_outputs(env, out_dir, budget=64 << 20, frame_envs=128, scalar_envs=1 << 18):
+    """--dump-outputs: what the last timed step hands its caller (VecEnv.step_wait(): the observation dict, reward, done and info's arrays), read
+    from the engine's buffers right after the timed region, as out_dir/<name>.npy: float64 where the engine holds 32-bit integers, float32 otherwise.
+    Per-env arrays are written whole (up to `scalar_envs` envs; beyond that a fixed sample, its indices in env_index.npy); frames for a fixed sample
+    of envs (numpy RandomState(0)), as many as fit `budget` bytes in all, at most `frame_envs`, their indices in frame_env_index.npy.
+    -> (names written, bytes written)."""
+    import torch
+    n = env.num_envs
+    perm = np.random.RandomState(0).permutation(n)
+    per_env = {'reward': env.reward, 'done': env.done, 'info_achieved_mask': env.achieved_mask, 'info_desired_mask': env.desired_mask,
+               'info_episode_length': env.episode_length, 'info_episode_return': env.episode_return}
+    frames = {}
+    if env.obs_mode == 'state':
+        per_env.update(obs_hdr=env.hdr, obs_slot_pos=env.slot_pos)
+    else:                                                # (achieved_goal IS observation: written once)
+        frames = {'obs_observation': env._obs, 'obs_desired_goal': env._desired_img, 'obs_init_observation': env._init_img}
+
+    def host(t, idx):
+        if len(idx) < t.shape[0]:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        x = t.cpu().numpy()
+        return x.astype(np.float64 if x.dtype.itemsize >= 4 else np.float32)
+
+    out = {}
+    idx = np.sort(perm[:scalar_envs]) if n > scalar_envs else np.arange(n)
+    for name, t in per_env.items():
+        out[name] = host(t, idx)
+    if n > scalar_envs:
+        out['env_index'] = idx.astype(np.float64)
+    if frames:
+        used = sum(a.nbytes for a in out.values())
+        per_frame = 4 * int(np.prod(env.frame_shape))
+        k = min(frame_envs, n, (budget - used - 8 * frame_envs) // (len(frames) * per_frame))
+        if k < 1:
+            raise SystemExit('--dump-outputs: not even one frame per array fits %d bytes' % budget)
+        fidx = np.sort(perm[:k])
+        for name, t in frames.items():
+            out[name] = host(t, fidx)
+        out['frame_env_index'] = fidx.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= budget, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(out), total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -292,7 +342,7 @@ def main():
     ap.add_argument('--launch-timeout', type=float, default=1500.0, help='self-launched ranks are stopped after this many seconds')
     ap.add_argument('--no-single-env', action='store_true', help='skip the N=1 facade latency (BASELINE configs[0])')
     ap.add_argument('--consumer', default='default', choices=['default', 'none', 'reduce', 'reduce32', 'conv', 'both', 'all'],
-                    help='policy-in-the-loop measurement (pixel modes): between two steps a torch kernel that reads EVERY observation byte and '
+                    help='with --full, policy-in-the-loop measurement (pixel modes): between two steps a torch kernel that reads EVERY observation byte and '
                          'produces the next actions from it, on the env\'s stream.  reduce: obs.view(N,-1).sum(1) %% 6; reduce32: the same over int32 words '
                          '(a reader at the memory\'s pace); conv: two strided bf16 convolutions + a sampled action.  default: all three, except with '
                          '--quick (none); a named one also runs with --quick')
@@ -307,10 +357,18 @@ def main():
                          'closing barrier (a late rank at the barrier must show in value_wall only, not in value: the region is timed on the device)')
     ap.add_argument('--inject-sleep-rank', type=int, default=1)
     ap.add_argument('--quick', action='store_true',
-                    help='profiling runs (rocprofv3 / PMC passes serialise kernels): only the contract regions -- no repeats, no metric '
-                         'window, no other modes, no single env, no CPU baseline')
+                    help='with --full, for profiling runs (rocprofv3 / PMC passes serialise kernels): only the timed region and the roofline region '
+                         '-- no repeats, no metric window, no other modes, no single env, no CPU baseline')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, everything beside the headline: the roofline region with the library\'s events, repeats, metric '
+                         'windows, policy in the loop, CPU baseline and soak, side modes, short episodes, single env, per-rank blocks')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to DIR/<name>.npy (float32 / float64; frames: a fixed sample of envs; '
+                         'rank 0\'s shard)')
     args = ap.parse_args()
-    if args.quick:
+    if not args.full and (args.quick or args.consumer != 'default'):
+        ap.error('--quick and --consumer select measurements of --full: give --full with them')
+    if args.quick or not args.full:
         args.no_cpu_baseline = args.no_other_modes = args.no_single_env = True
 
     # Plain `python bench.py --gpus N`: become the parent of N fresh ranks BEFORE anything touches torch or HIP (a
@@ -504,50 +562,54 @@ def main():
     timed_region_first = (timed_region.mine, timed_region.mine_wall)
     per_rank_s = gather_over_ranks(timed_region.mine, device=red_dev, group=timing_group)      # (once, after the region: who was the slowest?)
     per_rank_wall_s = gather_over_ranks(timed_region.mine_wall, device=red_dev, group=timing_group)
-    barrier()                                        # what an empty barrier pair costs this rank (control plane; explains value_wall - value at N > 1)
-    tb = time.perf_counter()
-    barrier()
-    barrier_ms = (time.perf_counter() - tb) * 1e3
-    # ... and twice more (the driver's K may be tiny: 20 steps are 5 ms); `value` stays the first region
-    repeats_s, repeats_wall_s = [elapsed], [elapsed_wall]
-    for r in range(0 if args.quick else 2):
-        repeats_s.append(timed_region(K, W + (r + 1) * K))
-        repeats_wall_s.append(timed_region.wall)
-    t_next = W + 3 * K
-
-    # second, identical K-step region with the library's HIP events around each kernel (eager launches:
-    # events cannot be re-recorded from inside a replayed graph)
     launch_desc = ('persistent launches of max_steps steps for the K steps (cw_rollout)' if args.rollout else
                    ('eager' if G == 0 else 'hip graph of %d steps' % G))
-    graph = None
-    args.rollout = False
-    episodes_before_prof = int(env.counters[1].item())
-    env.profile_begin(K)
-    barrier()
-    t1 = time.perf_counter()
-    run(K, t_next)
-    barrier()
-    elapsed_prof = time.perf_counter() - t1
-    prof = env.profile_end()
-    tuner = env.tuner_state()                        # (what pace the profiled launches ran at)
-    t_next += K
-    # every rank's own clock, guard moves, sweep time and NUMA binding (control plane, after the timed regions): a straggler in a scaling run explains itself
-    S_r = args.size
-    own_bytes = float(N) * (S_r * S_r + (48 * S_r * S_r if args.raster == 'ray' else 27 * S_r * (S_r + 1)))
-    per_rank = gather_objects_over_ranks({
-        'rank': rank, 'device': local_rank, 'envs': [lo, hi], 'tuner': tuner, 'numa': numa,
-        'sweep_ms': prof['ms_render_kernel'] or None, 'sweep_ms_median': prof['ms_render_kernel_median'] or None,
-        'roofline_frac': (own_bytes / (prof['ms_render_kernel'] * 1e-3) / 1e9 / HBM_PEAK_GBS) if args.obs_mode == 'pixels' and prof['ms_render_kernel'] > 0 else None,
-        'ms_per_step_with_events': elapsed_prof / K * 1e3, 'barrier_ms': barrier_ms,
-        'region_ms_device': timed_region_first[0] * 1e3, 'region_ms_wall': timed_region_first[1] * 1e3})
-    episodes = int(env.counters[1].item())
-    resets_in_prof = episodes - episodes_before_prof      # envs reset (and repainted: 3 frames each) inside the profiled launches
+    # what the last timed step computed, before anything else steps the env (rank 0's shard)
+    dumped = dump_outputs(env, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+
+    if args.full:
+        barrier()                                    # what an empty barrier pair costs this rank (control plane; explains value_wall - value at N > 1)
+        tb = time.perf_counter()
+        barrier()
+        barrier_ms = (time.perf_counter() - tb) * 1e3
+        # ... and twice more (K may be tiny: 20 steps are 5 ms); `value` stays the first region
+        repeats_s, repeats_wall_s = [elapsed], [elapsed_wall]
+        for r in range(0 if args.quick else 2):
+            repeats_s.append(timed_region(K, W + (r + 1) * K))
+            repeats_wall_s.append(timed_region.wall)
+        t_next = W + 3 * K
+
+        # second, identical K-step region with the library's HIP events around each kernel (eager launches:
+        # events cannot be re-recorded from inside a replayed graph)
+        graph = None
+        args.rollout = False
+        episodes_before_prof = int(env.counters[1].item())
+        env.profile_begin(K)
+        barrier()
+        t1 = time.perf_counter()
+        run(K, t_next)
+        barrier()
+        elapsed_prof = time.perf_counter() - t1
+        prof = env.profile_end()
+        tuner = env.tuner_state()                    # (what pace the profiled launches ran at)
+        t_next += K
+        # every rank's own clock, guard moves, sweep time and NUMA binding (control plane, after the timed regions): a straggler in a scaling run explains itself
+        S_r = args.size
+        own_bytes = float(N) * (S_r * S_r + (48 * S_r * S_r if args.raster == 'ray' else 27 * S_r * (S_r + 1)))
+        per_rank = gather_objects_over_ranks({
+            'rank': rank, 'device': local_rank, 'envs': [lo, hi], 'tuner': tuner, 'numa': numa,
+            'sweep_ms': prof['ms_render_kernel'] or None, 'sweep_ms_median': prof['ms_render_kernel_median'] or None,
+            'roofline_frac': (own_bytes / (prof['ms_render_kernel'] * 1e-3) / 1e9 / HBM_PEAK_GBS) if args.obs_mode == 'pixels' and prof['ms_render_kernel'] > 0 else None,
+            'ms_per_step_with_events': elapsed_prof / K * 1e3, 'barrier_ms': barrier_ms,
+            'region_ms_device': timed_region_first[0] * 1e3, 'region_ms_wall': timed_region_first[1] * 1e3})
+        episodes = int(env.counters[1].item())
+        resets_in_prof = episodes - episodes_before_prof      # envs reset (and repainted: 3 frames each) inside the profiled launches
 
     # SURVEY 8d's metric window, whatever --steps was: 2*max_steps consecutive steps, so both steps on which (nearly)
     # every env times out at once are inside.  One clean pass for the rate; a second one with an event after every step
     # (on the stream the step joins back into) for the per-step durations.
     window = None
-    if not args.quick:
+    if args.full and not args.quick:
         KW_ = 2 * args.max_steps
         ep0 = int(env.counters[1].item())
         win_elapsed = timed_region(KW_, t_next)
@@ -576,7 +638,7 @@ def main():
     # ... and the same window with the episode phases spread out (ray.py:367: episodes end at different steps once a policy succeeds;
     # about N/max_steps envs finish on every step): the steady state of a long run, in the same process.
     window_desync = None
-    if not args.quick and args.obs_mode == 'pixels' and not args.desync:
+    if args.full and not args.quick and args.obs_mode == 'pixels' and not args.desync:
         KW_ = 2 * args.max_steps
         env.set_state(step_num=((np.arange(lo, hi) * 7) % args.max_steps).astype(np.int32))
         run(KW_, t_next)                                 # 2*max_steps untimed steps: every env has finished at its own phase, the look-ahead refills are in their rhythm
@@ -616,7 +678,7 @@ def main():
     policy_blocks = None
     kinds = {'default': () if args.quick else ('reduce32', 'reduce', 'conv'), 'none': (), 'both': ('reduce', 'conv'),
              'all': ('reduce32', 'reduce', 'conv')}.get(args.consumer, (args.consumer,))
-    if kinds and args.obs_mode == 'pixels':
+    if kinds and args.full and args.obs_mode == 'pixels':
         S_ = args.size
         frame_ = 48 * S_ * S_ if args.raster == 'ray' else 27 * S_ * (S_ + 1)
         sweep_bytes = float(N) * (S_ * S_ + frame_)
@@ -878,6 +940,38 @@ def main():
         value = total_steps / elapsed
         S = args.size
         frame = 48 * S * S if args.raster == 'ray' else 27 * S * (S + 1)
+        out = {
+            'metric': 'env-steps/sec at 65536 envs, 1/2/4/8 MI355X; bit-exact vs CPU ref',
+            'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'steps': K, 'warmup': W,
+            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'u8', 'data': 'synthetic',
+            # the same K steps by the wall clock around the whole bracket (opening barrier ... closing barrier + synchronize), max over ranks
+            'value_wall': total_steps / elapsed_wall, 'ms_per_step_wall': elapsed_wall / K * 1e3,
+            'timing': 'value / ms_per_step: the slowest rank\'s DEVICE time for the K steps -- two events on the launch stream inside the barrier + synchronize '
+                      'bracket, the first right behind the opening barrier, the second behind the last step; value_wall: the wall clock around the bracket, '
+                      'which also holds the closing barrier (--full: per_rank[].barrier_ms) and the host\'s wake-up',
+            'config': {'workload': 'BASELINE configs[2]: %d envs/GPU, %dx%d grid, %s obs, auto-reset, uniform random '
+                                   'actions, max_steps=%d' % (N, S, S, {'pixels': 'full-frame 4x4-cell uint8 pixel',
+                                                                        'pixels_dirty': 'dirty-cell-repaint pixel',
+                                                                        'state': 'state-only'}[args.obs_mode], args.max_steps),
+                       'envs_per_gpu': N, 'size': S, 'max_steps': args.max_steps, 'obs_mode': args.obs_mode, 'raster': args.raster,
+                       'sharding': 'contiguous env ranges per rank, no data-path collective',
+                       'task_lists': 'eight ordered menus, env i uses menu i mod 8' if args.mixed_menus else 'one (all nine tasks)',
+                       'launch': launch_desc, 'episode_phases': 'spread out (--desync)' if args.desync else 'synchronized start',
+                       'timed_region': ('placed between two of the steps on which every env times out at once (K < max_steps: %d untimed steps '
+                                        'before the W warm-up steps instead of %d); metric_window holds them in their true proportion'
+                                        % (prewarm_steps, max(args.prewarm_steps, 0))) if prewarm_steps != max(args.prewarm_steps, 0) else
+                                       'the first K steps after the warm-up, wherever the all-env time-out steps fall'},
+            'prewarm_steps': prewarm_steps,
+            'warmup_total': prewarm_steps + W,           # untimed steps before the timed region: `warmup` is the contract's W
+            'per_rank_ms_per_step': [x / K * 1e3 for x in per_rank_s],
+            'per_rank_ms_per_step_wall': [x / K * 1e3 for x in per_rank_wall_s],
+            'dist_backend': backend_used,
+        }
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped[0], 'bytes': dumped[1],
+                                   'note': 'the last timed step\'s outputs, rank 0\'s shard (bench.dump_outputs)'}
+    if rank == 0 and args.full:
         if args.obs_mode == 'pixels':
             # A_pix = 48 + S*S (grid read) + frame write; the sweep's share is S*S + frame bytes per env, and one sweep
             # paints N envs.  (The INIT_OBS / desired_goal frames of envs that finished -- 2 x resets_in_prof frames in the profiled region --
@@ -920,28 +1014,7 @@ def main():
             ts = sorted(ts[2:])
             fill_gbs = alg_bytes / (ts[len(ts) // 2] * 1e-3) / 1e9
             del probe
-        out = {
-            'metric': 'env-steps/sec at 65536 envs, 1/2/4/8 MI355X; bit-exact vs CPU ref',
-            'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'steps': K, 'warmup': W,
-            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'u8', 'data': 'synthetic',
-            # the same K steps by the wall clock around the whole bracket (opening barrier ... closing barrier + synchronize), max over ranks
-            'value_wall': total_steps / elapsed_wall, 'ms_per_step_wall': elapsed_wall / K * 1e3,
-            'timing': 'value / ms_per_step: the slowest rank\'s DEVICE time for the K steps -- two events on the launch stream inside the barrier + synchronize '
-                      'bracket, the first right behind the opening barrier, the second behind the last step; value_wall: the wall clock around the bracket, '
-                      'which also holds the closing barrier (per_rank[].barrier_ms) and the host\'s wake-up',
-            'config': {'workload': 'BASELINE configs[2]: %d envs/GPU, %dx%d grid, %s obs, auto-reset, uniform random '
-                                   'actions, max_steps=%d' % (N, S, S, {'pixels': 'full-frame 4x4-cell uint8 pixel',
-                                                                        'pixels_dirty': 'dirty-cell-repaint pixel',
-                                                                        'state': 'state-only'}[args.obs_mode], args.max_steps),
-                       'envs_per_gpu': N, 'size': S, 'max_steps': args.max_steps, 'obs_mode': args.obs_mode, 'raster': args.raster,
-                       'sharding': 'contiguous env ranges per rank, no data-path collective',
-                       'task_lists': 'eight ordered menus, env i uses menu i mod 8' if args.mixed_menus else 'one (all nine tasks)',
-                       'launch': launch_desc, 'episode_phases': 'spread out (--desync)' if args.desync else 'synchronized start',
-                       'timed_region': ('placed between two of the steps on which every env times out at once (K < max_steps: %d untimed steps '
-                                        'before the W warm-up steps instead of %d); metric_window holds them in their true proportion'
-                                        % (prewarm_steps, max(args.prewarm_steps, 0))) if prewarm_steps != max(args.prewarm_steps, 0) else
-                                       'the first K steps after the warm-up, wherever the all-env time-out steps fall'},
+        out.update({
             # the figures to quote: the 2*max_steps window with both all-env time-out steps inside, and the same with the episode phases spread out
             'quote': {'metric_window': window['value'] if window else None, 'metric_window_desync': window_desync['value'] if window_desync else None},
             'roofline': {'bound': 'hbm', 'kernel': dominant,
@@ -970,10 +1043,7 @@ def main():
             'kernels_ms': {'step': prof['ms_step_kernel'] or None, 'reset': prof['ms_reset_kernel'] or None,
                            'render': prof['ms_render_kernel'] or None, 'ms_per_step_with_events': elapsed_prof / K * 1e3},
             'tuner': tuner,
-            'episodes_finished': episodes, 'prewarm_steps': prewarm_steps,
-            'warmup_total': prewarm_steps + W,           # untimed steps before the timed region: `warmup` is the contract's W
-            'per_rank_ms_per_step': [x / K * 1e3 for x in per_rank_s],
-            'per_rank_ms_per_step_wall': [x / K * 1e3 for x in per_rank_wall_s],
+            'episodes_finished': episodes,
             'per_rank_tuner': [r_['tuner'] for r_ in per_rank],
             'per_rank_roofline_frac': [r_['roofline_frac'] for r_ in per_rank],
             'per_rank': per_rank,
@@ -983,12 +1053,11 @@ def main():
                         'note': 'the K-step region three times back to back; `value` is the first'},
             'metric_window': window,
             'metric_window_desync': window_desync,
-            'dist_backend': backend_used,
             'other_obs_modes_1gpu': other,
             'config1_state_4096': config1,
             'short_episodes_1gpu': short_eps,
             'policy_in_loop': policy_blocks,
-        }
+        })
         if cpu_result is not None:                       # rank 0 at N=1 only (task contract); measured above, beside the GPU soak
             out['cpu_baseline'] = cpu_result
             out['soak_beside_cpu_baseline'] = soak

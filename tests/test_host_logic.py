@@ -234,6 +234,40 @@ def test_bench_cpu_baseline_leg_reports_port_and_calibration():
     assert abs(c['reference_equivalent_env_steps_per_s'] * c['port_over_reference_1core'] - out['dirty_cell_value']) < 1e-6 * out['dirty_cell_value']
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.py --dump-outputs (dump_outputs) on a stand-in env of CPU tensors with the VecEnv's buffer attributes: per-env arrays whole, frames of a
+    fixed env sample sized to the byte budget, float32 for 8- / 16-bit data and float64 for 32-bit data, exact values, the same files every time."""
+    import importlib.util
+    import types
+    import torch
+    spec = importlib.util.spec_from_file_location('cw_bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, fs = 1000, (20, 20, 3)
+    g = torch.Generator().manual_seed(0)
+    i32 = lambda: torch.randint(-2 ** 31, 2 ** 31 - 1, (n,), dtype=torch.int32, generator=g)  # noqa: E731
+    u8 = lambda *s: torch.randint(0, 256, (n,) + s, dtype=torch.uint8, generator=g)           # noqa: E731
+    e = types.SimpleNamespace(num_envs=n, obs_mode='pixels', frame_shape=fs, reward=i32(), done=(u8() & 1).bool(),
+                              achieved_mask=i32().to(torch.int16), desired_mask=i32().to(torch.int16), episode_length=i32(), episode_return=i32(),
+                              _obs=u8(*fs), _desired_img=u8(*fs), _init_img=u8(*fs))
+    per_env_bytes = n * (8 + 4 + 4 + 4 + 8 + 8)                 # reward, done, the two masks, episode length and return
+    budget = per_env_bytes + 3 * 50 * 4 * 1200 + 8 * 128       # ... and room for 50 frames of each kind and their indices
+    names, total = bench.dump_outputs(e, str(tmp_path / 'a'), budget=budget)
+    got = {k: np.load(tmp_path / 'a' / (k + '.npy')) for k in names}
+    assert total == sum(x.nbytes for x in got.values()) <= budget and len(os.listdir(tmp_path / 'a')) == len(names)
+    assert np.array_equal(got['reward'], e.reward.numpy()) and got['reward'].dtype == np.float64
+    assert np.array_equal(got['done'], e.done.numpy()) and got['done'].dtype == np.float32
+    assert np.array_equal(got['info_achieved_mask'], e.achieved_mask.numpy()) and got['info_achieved_mask'].dtype == np.float32
+    idx = got['frame_env_index'].astype(np.int64)
+    assert len(idx) == 50 and np.all(np.diff(idx) > 0) and idx.max() < n
+    for k, t in (('obs_observation', e._obs), ('obs_desired_goal', e._desired_img), ('obs_init_observation', e._init_img)):
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], t.numpy()[idx]), k
+    names2, _ = bench.dump_outputs(e, str(tmp_path / 'b'), budget=budget)
+    assert names2 == names and all(np.array_equal(got[k], np.load(tmp_path / 'b' / (k + '.npy'))) for k in names)
+    with pytest.raises(SystemExit):                           # (not one frame of each kind fits)
+        bench.dump_outputs(e, str(tmp_path / 'c'), budget=per_env_bytes + 100)
+
+
 def test_vector_env_surface_matches_gym_vector():
     """SURVEY 8b "interface": the gym.vector.VectorEnv surface of the batch class -- attribute and method names with the
     argument lists gym.vector (<= 0.21) gives them -- checked without constructing an engine (no GPU here)."""

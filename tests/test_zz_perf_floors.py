@@ -96,7 +96,7 @@ def test_bench_self_launched_two_ranks_share_the_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     # (rank 1 sleeps 30 ms on the host between its last launch and the closing barrier: a late rank at the barrier must not show in `value`)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--rehearse-on-one-gpu', '--dist-backend', 'gloo',
-                        '--quick', '--steps', '12', '--warmup', '3', '--envs-per-gpu', '4096', '--max-steps', '20', '--inject-sleep-ms', '30',
+                        '--full', '--quick', '--steps', '12', '--warmup', '3', '--envs-per-gpu', '4096', '--max-steps', '20', '--inject-sleep-ms', '30',
                         '--inject-sleep-rank', '1'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -124,7 +124,7 @@ def test_bench_self_launched_two_ranks_share_the_gpu():
 
 @pytest.mark.gpu
 def test_bench_json_line_carries_the_contract():
-    """One small `python bench.py` run on this GPU: exactly one JSON line with the contract's keys, the roofline object (dominant kernel
+    """One small `python bench.py --full` run on this GPU: exactly one JSON line with the contract's keys, the roofline object (dominant kernel
     by the name a rocprofv3 trace lists it under, HIP-event launch times, average and median), the CPU baseline (kind "port", a described
     sample, like for like with the headline), the repeats and the metric window."""
     import json
@@ -132,7 +132,7 @@ def test_bench_json_line_carries_the_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '40', '--warmup', '5', '--envs-per-gpu', '8192',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '40', '--warmup', '5', '--envs-per-gpu', '8192',
                         '--max-steps', '20', '--cpu-seconds', '0.5', '--no-other-modes', '--no-single-env'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -180,6 +180,51 @@ def test_bench_json_line_carries_the_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline alone: the contract's keys and none of --full's blocks.  --dump-outputs writes
+    what the last timed step returned as float32 / float64 .npy files within 64 MB, and two runs with the same arguments write identical arrays.
+    --steps is the number of timed steps: in the state-only mode with no pre-warm-up and no episode able to time out, the longest-running env
+    has taken exactly W + K steps when the arrays are written."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+
+    def bench(out, *extra):
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '30', '--warmup', '4', '--dump-outputs', str(tmp_path / out)]
+                           + list(extra), env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.strip().splitlines() if l.startswith('{')]
+        assert len(lines) == 1 and p.stdout.strip().splitlines()[-1] == lines[0], p.stdout
+        files = sorted(os.listdir(tmp_path / out))
+        return json.loads(lines[0]), {f[:-4]: np.load(tmp_path / out / f) for f in files if f.endswith('.npy')}
+
+    pix = ('--envs-per-gpu', '8192', '--max-steps', '20')
+    d, a = bench('a', *pix)
+    _, b = bench('b', *pix)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'steps', 'warmup', 'config', 'warmup_total'):
+        assert k in d, k
+    assert d['steps'] == 30 and d['warmup'] == 4 and d['unit'] == 'env-steps/s' and d['dtype'] == 'u8' and d['higher_is_better'] is True
+    assert abs(d['value'] - 8192 * 30 / (d['ms_per_step'] * 30e-3)) < 1e-6 * d['value']
+    for k in ('roofline', 'kernels_ms', 'repeats', 'metric_window', 'metric_window_desync', 'policy_in_loop', 'cpu_baseline', 'per_rank',
+              'other_obs_modes_1gpu', 'short_episodes_1gpu', 'single_env'):
+        assert k not in d, k
+    assert sorted(a) == sorted(b) == sorted(d['dump_outputs']['arrays'])
+    assert {'reward', 'done', 'obs_observation', 'obs_desired_goal', 'obs_init_observation', 'frame_env_index'} <= set(a)
+    assert sum(x.nbytes for x in a.values()) == d['dump_outputs']['bytes'] <= 64 << 20
+    assert a['reward'].shape == (8192,) and a['obs_observation'].shape == (128, 84, 84, 3) and a['frame_env_index'].shape == (128,)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert a['obs_observation'].max() > 0 and a['obs_desired_goal'].max() > 0
+
+    d, s = bench('c', '--obs-mode', 'state', '--envs-per-gpu', '4096', '--max-steps', '1000', '--prewarm-steps', '0')
+    assert d['steps'] == 30 and d['warmup_total'] == 4 and s['obs_hdr'].shape == (4096, 16)
+    step_num = s['obs_hdr'][:, 8].astype(np.int64) + 256 * s['obs_hdr'][:, 9].astype(np.int64)      # (bytes 8-9: step_num, LE u16)
+    assert step_num.max() == 4 + 30, np.bincount(step_num.astype(np.int64))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('name,args,floor_frac,floor_value', [
     ('headline', [], 0.81, 2.80e8),                                     # measured 0.876-0.884 / 3.04-3.07e8 (profiles/r04_clock.txt K)
     ('phases spread out', ['--desync'], 0.80, 2.72e8),                  # 0.859-0.864 / 2.97e8 (round 3: 0.74 / 2.65e8)
@@ -187,7 +232,7 @@ def test_bench_json_line_carries_the_contract():
     ('AltObs 21x21', ['--raster', 'alt'], 0.79, 4.4e8),                 # 0.849-0.873 / 4.8e8
 ])
 def test_perf_floors_of_the_sweep(name, args, floor_frac, floor_value):
-    """The performance of the dominant kernel is a tested property: a fresh `bench.py --quick --steps 300` of BASELINE configs[2] (65 536 envs,
+    """The performance of the dominant kernel is a tested property: a fresh `bench.py --full --quick --steps 300` of BASELINE configs[2] (65 536 envs,
     21x21, full frames) -- with the episode phases in step and spread out (~220 envs finish on every step: the steady state of any policy that
     finishes episodes) --, of configs[4]'s 32x32 grids and of the AltObs raster must paint at the given fraction of the 8 TB/s HBM peak at its
     median launch, and step at the given rate: each floor 7-8 % under the committed measurement (profiles/r04_*)."""
@@ -196,7 +241,7 @@ def test_perf_floors_of_the_sweep(name, args, floor_frac, floor_value):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT') and not k.startswith('CW_TUNE_')}
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--quick', '--steps', '300'] + args, env=env, capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--quick', '--steps', '300'] + args, env=env, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])                # the JSON line is the LAST line of rank 0's stdout

@@ -3,7 +3,7 @@
 # CW_TUNE_* the caller exports (e.g. CW_TUNE_PERIOD_NS=0: every sweep unclocked) -- r04_ab.sh "<lib names, 'product' = the built library>"
 cd ${GRAFT_REPO_ROOT:-.}
 run() { label=$1; shift
-  python bench.py --quick --steps 600 "$@" 2>/dev/null | python -c "
+  python bench.py --full --quick --steps 600 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; t=d['tuner']
 print('%-8s %-26s %.4e env-steps/s  ms/step %.4f  kernel avg %.4f med %.4f min %.4f  frac %.3f / %.3f  period %.0f ns  beside the sweep %.1f us' % ('$V', '$label', d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['launch_ms_min_max'][0], r['frac'], r['frac_at_median_launch'], t['period16'] / 1.6, (d['ms_per_step'] - r['avg_launch_ms'] * max(1, round(d['ms_per_step'] / r['avg_launch_ms'] - 0.3))) * 1e3))"

@@ -2,7 +2,7 @@
 # GPU box: throw-away builds on the shapes whose steady state (episode phases spread out) is the fragile one -- r04_desync.sh "<lib names>"
 cd ${GRAFT_REPO_ROOT:-.}
 run() { label=$1; shift
-  python bench.py --quick --steps 600 --desync "$@" 2>/dev/null | python -c "
+  python bench.py --full --quick --steps 600 --desync "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; t=d['tuner']
 print('%-8s %-26s %.4e env-steps/s  ms/step %.4f  kernel avg %.4f med %.4f min %.4f max %.4f  frac %.3f / %.3f  period %.0f / %.0f ns' % ('$V', '$label', d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['launch_ms_min_max'][0], r['launch_ms_min_max'][1], r['frac'], r['frac_at_median_launch'], t['period16'] / 1.6, t['period16_busy'] / 1.6))"

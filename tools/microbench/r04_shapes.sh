@@ -1,8 +1,8 @@
 #!/bin/bash
-# GPU box: bench.py --quick on the shapes that are not the headline (default tuning) -> one line each
+# GPU box: bench.py --full --quick on the shapes that are not the headline (default tuning) -> one line each
 cd ${GRAFT_REPO_ROOT:-.}
 run() { label=$1; shift
-  python bench.py --quick --steps 600 "$@" 2>/dev/null | python -c "
+  python bench.py --full --quick --steps 600 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; t=d['tuner']
 print('%-34s %.4e env-steps/s  ms/step %.4f  kernel avg %.4f med %.4f min %.4f  frac %.3f / %.3f  period %.0f ns' % ('$label', d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['launch_ms_min_max'][0], r['frac'], r['frac_at_median_launch'], t['period16'] / 1.6))"

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 run() { label=$1; shift
   for s in 10 12 14 16; do
-    env "$@" python bench.py --quick --steps 600 --size $s 2>/dev/null | python -c "
+    env "$@" python bench.py --full --quick --steps 600 --size $s 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-8s %2dx%-2d value %.4e  ms/step %.4f  sweep %.4f ms (median %.4f)  frac %.3f (median %.3f)  period16 %d' % ('$label', $s, $s, d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['frac'], r['frac_at_median_launch'], d['tuner']['period16']))"

@@ -8,7 +8,7 @@ SIZES=${1:-"4 5 6 7 8 9 12"}; RASTERS=${2:-"ray"}; N=${3:-65536}
 run() { # label, env assignments...
   label=$1; shift
   for raster in $RASTERS; do for s in $SIZES; do
-    env "$@" python bench.py --quick --steps 600 --size $s --raster $raster --envs-per-gpu $N 2>/dev/null | python -c "
+    env "$@" python bench.py --full --quick --steps 600 --size $s --raster $raster --envs-per-gpu $N 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-12s %-3s %2dx%-2d %7d envs  value %.4e  ms/step %.4f  sweep %.4f ms (median %.4f)  frac %.3f (median %.3f)  period16 %d  %s' % ('$label', '$raster', $s, $s, $N, d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['frac'], r['frac_at_median_launch'], d['tuner']['period16'], r['kernel_in_trace']))"

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 run() { label=$1; raster=$2; sizes=$3; shift 3
   for s in $sizes; do
-    env "$@" python bench.py --quick --steps 600 --size $s --raster $raster 2>/dev/null | python -c "
+    env "$@" python bench.py --full --quick --steps 600 --size $s --raster $raster 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('%-12s %-3s %2dx%-2d value %.4e  ms/step %.4f  sweep %.4f ms (median %.4f)  frac %.3f (median %.3f)  period16 %d' % ('$label', '$raster', $s, $s, d['value'], d['ms_per_step'], r['avg_launch_ms'], r['median_launch_ms'], r['frac'], r['frac_at_median_launch'], d['tuner']['period16']))"

@@ -9,9 +9,9 @@ for lib in product "$@"; do
   if [ $lib = product ]; then unset CW_LIB_PATH; else export CW_LIB_PATH=$PWD/gym_craftingworld_amd/libcw_exp_$lib.so; fi
   for mode in sync desync; do
     extra=""; [ $mode = desync ] && extra="--desync"
-    python bench.py --quick --steps 600 $extra > $O/${lib}_$mode.json 2>/dev/null
+    python bench.py --full --quick --steps 600 $extra > $O/${lib}_$mode.json 2>/dev/null
     rm -rf $O/rp_${lib}_$mode
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_$mode -o p -- python bench.py --quick --steps 600 $extra > $O/${lib}_${mode}_rp.json 2> $O/${lib}_${mode}_rp.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_$mode -o p -- python bench.py --full --quick --steps 600 $extra > $O/${lib}_${mode}_rp.json 2> $O/${lib}_${mode}_rp.err
     python - <<PY
 import json, csv, glob
 d = json.loads(open('$O/${lib}_$mode.json').read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ run() { label=$1; shift
   for mode in sync desync; do
     extra=""; [ $mode = desync ] && extra="--desync"
     rm -rf $O/rp_${label}_$mode
-    env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${label}_$mode -o p -- python bench.py --quick --steps 600 $extra > $O/${label}_${mode}_rp.json 2> $O/${label}_${mode}_rp.err
+    env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${label}_$mode -o p -- python bench.py --full --quick --steps 600 $extra > $O/${label}_${mode}_rp.json 2> $O/${label}_${mode}_rp.err
     python - <<PY
 import csv, glob
 f = sorted(glob.glob('$O/rp_${label}_$mode/**/p_kernel_stats.csv', recursive=True))[0]

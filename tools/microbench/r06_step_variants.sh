@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: cw_step_fused_kernel specialised on <PAINT, TERM> (round 6) against the round-5 kernel (one body, `paint` a runtime argument):
 #   tools builds the old one as gym_craftingworld_amd/libcw_exp_r05step.so (git show f5ad428:.../cw_kernels.hip with today's cw_engine.cpp).
-#   the kernels' own times from rocprofv3 --kernel-trace --stats: bench.py --quick --steps 3000 --obs-mode state / pixels_dirty (the step kernel IS the
+#   the kernels' own times from rocprofv3 --kernel-trace --stats: bench.py --full --quick --steps 3000 --obs-mode state / pixels_dirty (the step kernel IS the
 #   step there), and --steps 600 in the full-frame mode (the step kernel that FOLLOWS the sweep); episode phases in step and spread out.
 #   bash tools/microbench/r06_step_variants.sh   -> stdout
 export TMPDIR=/tmp
@@ -13,7 +13,7 @@ for lib in product r05step; do
     for mode in sync desync; do
       extra=""; [ $mode = desync ] && extra="--desync"
       rm -rf $O/rp_${lib}_${obs}_$mode
-      rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_${obs}_$mode -o p -- python bench.py --quick --steps 3000 --obs-mode $obs $extra > $O/${lib}_${obs}_${mode}_rp.json 2> $O/${lib}_${obs}_${mode}_rp.err
+      rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_${obs}_$mode -o p -- python bench.py --full --quick --steps 3000 --obs-mode $obs $extra > $O/${lib}_${obs}_${mode}_rp.json 2> $O/${lib}_${obs}_${mode}_rp.err
       python - <<PY
 import json, csv, glob
 d = json.loads(open('$O/${lib}_${obs}_${mode}_rp.json').read().strip().splitlines()[-1])
@@ -29,9 +29,9 @@ PY
   done
   for mode in sync desync; do
     extra=""; [ $mode = desync ] && extra="--desync"
-    python bench.py --quick --steps 600 $extra > $O/${lib}_$mode.json 2>/dev/null
+    python bench.py --full --quick --steps 600 $extra > $O/${lib}_$mode.json 2>/dev/null
     rm -rf $O/rp_${lib}_$mode
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_$mode -o p -- python bench.py --quick --steps 600 $extra > $O/${lib}_${mode}_rp.json 2> $O/${lib}_${mode}_rp.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp_${lib}_$mode -o p -- python bench.py --full --quick --steps 600 $extra > $O/${lib}_${mode}_rp.json 2> $O/${lib}_${mode}_rp.err
     python - <<PY
 import json, csv, glob
 d = json.loads(open('$O/${lib}_$mode.json').read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ MODES=${1:-"pixels_dirty state"}; shift || true
 OUT=$GRAFT_REPO_ROOT/gpurun_out/dirty
 rm -rf $OUT; mkdir -p $OUT
 for mode in $MODES; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$mode -o p -- python bench.py --quick --steps 600 --obs-mode $mode "$@" > $OUT/bench_stats_$mode.json 2> $OUT/stats_$mode.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$mode -o p -- python bench.py --full --quick --steps 600 --obs-mode $mode "$@" > $OUT/bench_stats_$mode.json 2> $OUT/stats_$mode.err
   cp $(ls $OUT/stats_$mode/p_kernel_stats.csv $OUT/stats_$mode/*/p_kernel_stats.csv 2>/dev/null | head -1) $OUT/kernel_stats_$mode.csv
   i=0
   for G in "WRITE_SIZE" "FETCH_SIZE" \
@@ -21,14 +21,14 @@ for mode in $MODES; do
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_VALU" \
            "GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    rocprofv3 --pmc $G --kernel-trace --output-format csv -d $OUT/${mode}_g$i -- python bench.py --quick --steps 120 --warmup 5 --obs-mode $mode "$@" > $OUT/${mode}_g$i.json 2> $OUT/${mode}_g$i.err || echo "$mode group $i failed"
+    rocprofv3 --pmc $G --kernel-trace --output-format csv -d $OUT/${mode}_g$i -- python bench.py --full --quick --steps 120 --warmup 5 --obs-mode $mode "$@" > $OUT/${mode}_g$i.json 2> $OUT/${mode}_g$i.err || echo "$mode group $i failed"
     echo "$mode group $i done"
   done
 done
 OUT=$OUT MODES="$MODES" python - <<'PY'
 import csv, glob, os, collections, json
 out, modes = os.environ['OUT'], os.environ['MODES'].split()
-res = {'note': 'median per launch of cw_step_fused_kernel over a bench.py --quick run (65 536 envs, 21x21); FETCH_SIZE / WRITE_SIZE in KiB as rocprofv3 reports '
+res = {'note': 'median per launch of cw_step_fused_kernel over a bench.py --full --quick run (65 536 envs, 21x21); FETCH_SIZE / WRITE_SIZE in KiB as rocprofv3 reports '
                'them (x 1024 -> bytes; gfx950: FETCH_SIZE counts half of wide coalesced reads); *_sum counters summed over the 8 XCDs'}
 for mode in modes:
     acc = collections.defaultdict(list)

@@ -2,7 +2,7 @@
 """Per-kernel launch times of a `rocprofv3 --kernel-trace` run of bench.py over the TIMED launches only.
 
 rocprofv3's own --stats table averages every launch of the process: cw_create's calibration of the sweep's clock (~260 sweeps at seven rates) and the
-warm-up steps are in it.  bench.py --quick takes prewarm + W untimed steps, K timed steps (`value`) and K more with the library's HIP events around the
+warm-up steps are in it.  bench.py --full --quick takes prewarm + W untimed steps, K timed steps (`value`) and K more with the library's HIP events around the
 dominant kernel (`roofline.avg_launch_ms`): this reads the per-launch trace and reports the dominant kernel's and the step kernel's averages over exactly
 those two K-launch regions -- the figure to hold against roofline.avg_launch_ms.
 
