@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,8 +97,8 @@ struct cw_engine {
     unsigned la_steps = 0;
     unsigned la_period = 16;           // the CURRENT refill period: la_period_max, or shorter while envs finish twice between two refills (la_adapt)
     unsigned la_period_max = 16;       // la_period_for(max_steps), or CW_TUNE_LA_PERIOD
-    bool la_adaptive = true;
-    int rollout_segment = -1;          // CW_TUNE_ROLLOUT_SEGMENT (read at cw_create like every tuning variable): steps per persistent launch of cw_rollout, 0: one launch, -1: max_steps
+    bool la_adaptive = true;           // (false: a period forced by CW_TUNE_LA_PERIOD)
+    int rollout_segment = -1;          // CW_TUNE_ROLLOUT_SEGMENT: steps per persistent launch of cw_rollout, 0: one launch, -1: max_steps
     unsigned long long *la_feedback = nullptr;     // pinned: counters[5] as the last refill kernel saw it
     unsigned long long la_slow_seen = 0;
     int32_t la_quiet = 0;              // refills in a row with (nearly) no slow-path reset
@@ -107,6 +108,8 @@ struct cw_engine {
     int sweep_waves = 1024;            // waves of a sweep's launch, jobs (4-KiB pieces) per wave over all of its launches
     double sweep_jobs = 0, sweep_rate = 0, sweep_beside_ms = 0;      // (sweep_rate: cw_create's choice; the live one is guard.rate)
     bool guard_on = false;
+    double head_notch = 0.4, busy_notch = 0.75, tune_period_ns = -1, tune_rate_tbs = -1;      // the host's own CW_TUNE_* values (read_tuning; the launch side's are in
+    bool tune_guard = true, tune_lookahead = true, verbose = false;                             // tune): the clock's notches (TB/s), a forced period (ns) or starting rate (TB/s; -1: none)
     // the guard's samples in flight: the host runs up to ~1 000 steps ahead of the card, so a sample recorded now is read a dozen samples later
     enum { GUARD_RING = 32 };
     struct GuardSample { hipEvent_t ev[6]; int period16; } guard_ring[GUARD_RING] = {};
@@ -267,12 +270,11 @@ static int timed_render_stats(cw_engine *e, double *median, double *p90, double 
 // (sweep_guard_tick): a sweep that does not keep its schedule any more is slowed down a notch.
 // CW_TUNE_PERIOD_NS forces a period (0: unclocked, every wave as fast as it can).
 static double sweep_period_ns(const cw_engine *e, double tb_per_s) { return (double)e->sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }
-// the clock's three periods from one rate (cwh_sweep_periods): a launch's first CWH_HEAD_JOBS jobs run CW_HEAD_NOTCH slower, after a step on which envs
-// finished CW_BUSY_NOTCH slower (cw_render_pieces_kernel)
-static double CW_HEAD_NOTCH = 0.4, CW_BUSY_NOTCH = 0.75;      // (TB/s; CW_TUNE_HEAD_NOTCH / CW_TUNE_BUSY_NOTCH for experiments: profiles/r05_experiments.txt J)
+// the clock's three periods from one rate (cwh_sweep_periods): a launch's first CWH_HEAD_JOBS jobs run the engine's head_notch slower, after a step on
+// which envs finished its busy_notch slower (cw_render_pieces_kernel; CW_TUNE_HEAD_NOTCH / CW_TUNE_BUSY_NOTCH for experiments: profiles/r05_experiments.txt J)
 static void set_sweep_rate(cw_engine *e, double tb_per_s)
 {
-    cwh_sweep_periods(tb_per_s, e->sweep_waves, CW_HEAD_NOTCH, CW_BUSY_NOTCH, &e->tune.period16, &e->tune.period16_head, &e->tune.period16_busy);
+    cwh_sweep_periods(tb_per_s, e->sweep_waves, e->head_notch, e->busy_notch, &e->tune.period16, &e->tune.period16_head, &e->tune.period16_busy);
 }
 
 static int calibrate_sweep(cw_engine *e)
@@ -281,10 +283,8 @@ static int calibrate_sweep(cw_engine *e)
     int n_chunks = 1, jobs_per_wave = 1;
     cwk_sweep_shape(&e->P, &tn, &n_chunks, &e->sweep_waves, &jobs_per_wave);
     e->sweep_jobs = (double)n_chunks * jobs_per_wave;
-    if (const char *v = getenv("CW_TUNE_HEAD_NOTCH")) CW_HEAD_NOTCH = atof(v);
-    if (const char *v = getenv("CW_TUNE_BUSY_NOTCH")) CW_BUSY_NOTCH = atof(v);
-    if (const char *per = getenv("CW_TUNE_PERIOD_NS")) {                         // (the heads keep their distance: a forced 545 ns is 7.7 TB/s with 7.3 / 6.95 heads)
-        const double ns = atof(per);
+    if (e->tune_period_ns >= 0) {                                                // (the heads keep their distance: a forced 545 ns is 7.7 TB/s with 7.3 / 6.95 heads)
+        const double ns = e->tune_period_ns;
         set_sweep_rate(e, ns > 0 ? (double)e->sweep_waves * 4096.0 / (ns * 1e-9) * 1e-12 : 0.0);
         if (ns > 0) tn.period16 = (int)(ns * 1.6 + 0.5);
         return CW_OK;
@@ -306,9 +306,8 @@ static int calibrate_sweep(cw_engine *e)
     set_sweep_rate(e, 6.4);
     if (rc == CW_OK) rc = timed_render_stats(e, &med, &p90);
     e->sweep_beside_ms = med - e->sweep_jobs * sweep_period_ns(e, 6.4) * 1e-6;
-    const char *forced_rate = getenv("CW_TUNE_RATE_TBS");                      // (the starting rate, the guard stays on: the test that it slows a saturated sweep down)
-    if (forced_rate && atof(forced_rate) > 0) { e->sweep_rate = atof(forced_rate); best_p90 = 1e-9; }
-    for (size_t i = 0; i < sizeof(rates) / sizeof(rates[0]) && rc == CW_OK && !forced_rate; i++) {
+    if (e->tune_rate_tbs >= 0) e->sweep_rate = e->tune_rate_tbs;               // (the starting rate, the guard stays on: the test that it slows a saturated sweep down)
+    for (size_t i = 0; i < sizeof(rates) / sizeof(rates[0]) && rc == CW_OK && e->tune_rate_tbs < 0; i++) {
         set_sweep_rate(e, rates[i]);
         rc = timed_render_stats(e, &med, &p90, &mean);
         if (len < sizeof(log) - 56) len += (size_t)snprintf(log + len, sizeof(log) - len, " %.1f TB/s (%.0f ns): %.4f/%.4f/%.4f |", rates[i], tn.period16 / 1.6, med, p90, mean);
@@ -316,12 +315,12 @@ static int calibrate_sweep(cw_engine *e)
     }
     set_sweep_rate(e, e->sweep_rate);
     cwh_guard_init(&e->guard, e->sweep_rate);
-    e->guard_on = rc == CW_OK && e->sweep_rate > 0 && e->auto_reset && !(getenv("CW_TUNE_GUARD") && atoi(getenv("CW_TUNE_GUARD")) == 0);
+    e->guard_on = rc == CW_OK && e->sweep_rate > 0 && e->auto_reset && e->tune_guard;
     if (e->guard_on)
         for (auto &smp : e->guard_ring)
             for (hipEvent_t &ev : smp.ev)
                 if (hipEventCreate(&ev) != hipSuccess) e->guard_on = false;
-    if (getenv("CW_TUNE_VERBOSE"))
+    if (e->verbose)
         fprintf(stderr, "[craftingworld] sweep clock, ms per sweep (median/90th percentile/mean of 20; 0.0 TB/s = unclocked):%s -> %s%.0f ns\n", log,
                 tn.period16 ? "" : "unclocked, ", tn.period16 / 1.6);
     return rc;
@@ -335,7 +334,6 @@ enum { CW_GUARD_EVERY = 64 };
 static hipEvent_t *sweep_guard_tick(cw_engine *e, hipStream_t st)
 {
     if (++e->guard_step % CW_GUARD_EVERY) return nullptr;
-    const bool verbose = getenv("CW_TUNE_VERBOSE") != nullptr;
     // the samples whose sweeps have run by now, oldest first (the host may be a thousand steps ahead of the card: a sample is read long after it was recorded)
     while (e->guard_tail != e->guard_head && hipEventQuery(e->guard_ring[e->guard_tail % cw_engine::GUARD_RING].ev[5]) == hipSuccess) {
         cw_engine::GuardSample &smp = e->guard_ring[e->guard_tail++ % cw_engine::GUARD_RING];
@@ -346,7 +344,7 @@ static hipEvent_t *sweep_guard_tick(cw_engine *e, hipStream_t st)
         const int recovering = e->guard.recovering;
         const int action = cwh_guard_step(&e->guard, ms, scheduled);
         if (e->guard.rate != rate_before) set_sweep_rate(e, e->guard.rate);
-        if (verbose && action != CWH_GUARD_NONE) {
+        if (e->verbose && action != CWH_GUARD_NONE) {
             static const char *what[] = {"", "three samples in a row late: a notch down", "trying a notch up", "the trial pays: kept", "the trial does not pay: undone"};
             fprintf(stderr, "[craftingworld] sweep clock: %s%s -- %.4f ms against %.4f scheduled (mean at the rate left %.4f): %.1f -> %.1f TB/s (%.0f ns)\n", what[action],
                     recovering ? " (on the way back to the best rate known)" : "", ms, scheduled, prev_mean, rate_before, e->guard.rate, e->tune.period16 / 1.6);
@@ -356,6 +354,35 @@ static hipEvent_t *sweep_guard_tick(cw_engine *e, hipStream_t st)
     cw_engine::GuardSample &slot = e->guard_ring[e->guard_head++ % cw_engine::GUARD_RING];
     slot.period16 = e->tune.period16;
     return slot.ev;
+}
+
+// Every CW_TUNE_* environment variable, read once, by cw_create: the launch side's into e->tune, the host's own into the engine.
+// It runs on a fresh engine, whose values are the defaults: a value out of its range keeps the default.  (The default refill period follows P.max_steps.)
+static void read_tuning(cw_engine *e)
+{
+    auto geti = [](const char *k, int d, int lo = INT_MIN, int hi = INT_MAX) { const char *v = getenv(k); const int x = v ? atoi(v) : d; return x >= lo && x <= hi ? x : d; };
+    auto getd = [](const char *k, double d, double lo) { const char *v = getenv(k); const double x = v ? atof(v) : d; return x >= lo ? x : d; };
+    CwTuning &tn = e->tune;
+    tn.render_chunk_rounds = geti("CW_TUNE_RENDER_CHUNK_ROUNDS", tn.render_chunk_rounds, 0);
+    const int epw = geti("CW_TUNE_STEP_ENVS_PER_WAVE", tn.step_envs_per_wave);
+    tn.step_envs_per_wave = epw == 8 || epw == 16 || epw == 32 || epw == 64 ? epw : tn.step_envs_per_wave;
+    tn.gather = geti("CW_TUNE_GATHER", tn.gather);
+    tn.gather_max_size = geti("CW_TUNE_GATHER_MAX_SIZE", tn.gather_max_size, 0, 9);          // (cw_render_gather_kernel's tables: frames under 4 KiB)
+    tn.small_frame_bytes = geti("CW_TUNE_SMALL_FRAME_BYTES", tn.small_frame_bytes, 0);
+    tn.small_blocks_per_cu = geti("CW_TUNE_SMALL_BLOCKS", tn.small_blocks_per_cu, 1, 8);
+    tn.small_launch_bytes = (long long)geti("CW_TUNE_SMALL_LAUNCH_MB", (int)(tn.small_launch_bytes >> 20), 0) << 20;
+    tn.reset_blocks_per_cu = geti("CW_TUNE_RESET_BLOCKS", tn.reset_blocks_per_cu, 1, 16);
+    e->head_notch = getd("CW_TUNE_HEAD_NOTCH", e->head_notch, 0);
+    e->busy_notch = getd("CW_TUNE_BUSY_NOTCH", e->busy_notch, 0);
+    e->tune_period_ns = getd("CW_TUNE_PERIOD_NS", -1, 0);
+    e->tune_rate_tbs = getd("CW_TUNE_RATE_TBS", -1, 0);
+    e->tune_guard = geti("CW_TUNE_GUARD", 1) != 0;
+    e->verbose = getenv("CW_TUNE_VERBOSE") != nullptr;
+    e->tune_lookahead = geti("CW_TUNE_LOOKAHEAD", 1) != 0;
+    const int la_period = geti("CW_TUNE_LA_PERIOD", 0, 1);                  // (a forced refill period, no adaptation: profiles/r06_experiments.txt D)
+    e->la_adaptive = la_period == 0;
+    e->la_period = e->la_period_max = (unsigned)(la_period ? la_period : la_period_for(e->P.max_steps));
+    e->rollout_segment = geti("CW_TUNE_ROLLOUT_SEGMENT", e->rollout_segment, -1);
 }
 
 extern "C" {
@@ -428,33 +455,14 @@ int cw_create(const cw_config *cfg, int device, cw_engine **out)
     P.size = e->S;
     P.ncell = e->ncell;
     P.max_steps = cfg->max_steps;
-    e->la_period = (unsigned)la_period_for(cfg->max_steps);
-    if (const char *v = getenv("CW_TUNE_LA_PERIOD")) if (atoi(v) >= 1) { e->la_period = (unsigned)atoi(v); e->la_adaptive = false; }      // (a forced period: profiles/r06_experiments.txt D)
-    e->la_period_max = e->la_period;
-    if (const char *v = getenv("CW_TUNE_ROLLOUT_SEGMENT")) e->rollout_segment = atoi(v);
+    read_tuning(e);                    // (the defaults are the measured best)
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) e->tune.n_cu = prop.multiProcessorCount;
     P.task_mask = (1u << cfg->n_task_list) - 1u;
     P.pool_k = e->K;
     P.div_magic = (uint32_t)((1ull << 32) / (uint64_t)e->S) + 1u;
     P.raster = cfg->raster;
     P.frame_bytes = cfg->raster == CW_RASTER_ALT ? 27u * (uint32_t)e->S * (uint32_t)(e->S + 1) : 48u * (uint32_t)e->ncell;
-    {   // Tuning: the defaults are the measured best
-        auto geti = [](const char *k, int d) { const char *v = getenv(k); return v ? atoi(v) : d; };
-        CwTuning &tn = e->tune;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) tn.n_cu = prop.multiProcessorCount;
-        tn.render_chunk_rounds = geti("CW_TUNE_RENDER_CHUNK_ROUNDS", tn.render_chunk_rounds);
-        tn.step_envs_per_wave = geti("CW_TUNE_STEP_ENVS_PER_WAVE", tn.step_envs_per_wave);
-        if (tn.step_envs_per_wave != 8 && tn.step_envs_per_wave != 16 && tn.step_envs_per_wave != 32) tn.step_envs_per_wave = 64;
-        tn.gather = geti("CW_TUNE_GATHER", tn.gather);
-        tn.gather_max_size = geti("CW_TUNE_GATHER_MAX_SIZE", tn.gather_max_size);
-        if (tn.gather_max_size > 9) tn.gather_max_size = 9;                       // (cw_render_gather_kernel's tables: frames under 4 KiB)
-        tn.small_frame_bytes = geti("CW_TUNE_SMALL_FRAME_BYTES", tn.small_frame_bytes);
-        tn.small_blocks_per_cu = geti("CW_TUNE_SMALL_BLOCKS", tn.small_blocks_per_cu);
-        if (tn.small_blocks_per_cu < 1 || tn.small_blocks_per_cu > 8) tn.small_blocks_per_cu = 1;
-        tn.small_launch_bytes = (long long)geti("CW_TUNE_SMALL_LAUNCH_MB", (int)(tn.small_launch_bytes >> 20)) << 20;
-        tn.reset_blocks_per_cu = geti("CW_TUNE_RESET_BLOCKS", tn.reset_blocks_per_cu);
-        if (tn.reset_blocks_per_cu < 1 || tn.reset_blocks_per_cu > 16) tn.reset_blocks_per_cu = 2;
-    }
 
     int rc = CW_OK;
 #define ALLOC(field, count)                                     \
@@ -499,7 +507,7 @@ int cw_create(const cw_config *cfg, int device, cw_engine **out)
     if (cfg->host_outputs && rc == CW_OK) rc = host_alloc(e, &e->host_actions, N);
     // look-ahead records: every engine that resets by itself and lives in device memory (CW_TUNE_LOOKAHEAD=0: the slow path only, for A/B runs
     // and the test that both give the same results)
-    P.lookahead = (cfg->auto_reset && !cfg->host_outputs && !(getenv("CW_TUNE_LOOKAHEAD") && atoi(getenv("CW_TUNE_LOOKAHEAD")) == 0)) ? 1 : 0;
+    P.lookahead = (cfg->auto_reset && !cfg->host_outputs && e->tune_lookahead) ? 1 : 0;
     ALLOC(nx_init_pos, P.lookahead ? N * CW_LA_DEPTH : 1);      // (a queue of CW_LA_DEPTH records per env, one array per slot: cw_layout.h)
     ALLOC(nx_goal_pos, P.lookahead ? N * CW_LA_DEPTH : 1);
     ALLOC(nx_misc, P.lookahead ? N * CW_LA_DEPTH : 1);

@@ -100,6 +100,15 @@ __device__ __forceinline__ u32x3 overlay_dwords(u32x3 d, uint32_t o)
     d.z = (d.z & 0xFFFFFF00u) | (o >> 16);
     return d;
 }
+// one cell of the one-hot view (ray.py:94-98): channel bits 0..11 as 12 bytes of 0/1
+__device__ __forceinline__ u32x3 onehot_dwords(uint32_t bits)
+{
+    u32x3 d;
+    d.x = (bits & 1u) | ((bits >> 1 & 1u) << 8) | ((bits >> 2 & 1u) << 16) | ((bits >> 3 & 1u) << 24);
+    d.y = (bits >> 4 & 1u) | ((bits >> 5 & 1u) << 8) | ((bits >> 6 & 1u) << 16) | ((bits >> 7 & 1u) << 24);
+    d.z = (bits >> 8 & 1u) | ((bits >> 9 & 1u) << 8) | ((bits >> 10 & 1u) << 16) | ((bits >> 11 & 1u) << 24);
+    return d;
+}
 
 // render_edit (ray.py:522-557): repaint one cell of the persistent frame, one lane does 4 x 12 B
 __device__ __forceinline__ void paint_cell(uint8_t *frame, int S, uint32_t cell, uint32_t code,
@@ -280,6 +289,9 @@ __device__ __forceinline__ void paint_state_frame(const CwParams &P, uint8_t *ds
         render_frame(dst, dst1, P.size, P.ncell, P.div_magic, sp, rgb, agent_cell, hold ? rgb_of_code(hold) : 0x00FFFFFFu, lane);
     }
 }
+// the header's word x (cw_layout.h): the agent's cell and what it holds
+__device__ __forceinline__ uint32_t agent_cell_of(const CwParams &P, uint32_t hx) { return (hx & 0xFFu) * P.size + ((hx >> 8) & 0xFFu); }
+__device__ __forceinline__ uint32_t hold_of(uint32_t hx) { return (hx >> 16) & 0xFFu; }
 // which of an env's three states a frame shows: its current one (observation), the one at reset (INIT_OBS), imagine_obs' final one (desired_goal)
 enum { CW_SRC_CURRENT = 0, CW_SRC_INIT = 1, CW_SRC_GOAL = 2 };
 // ... as wave-uniform values (every lane loads the same record)
@@ -291,8 +303,8 @@ __device__ __forceinline__ void load_state_uniform(const CwParams &P, int env, i
         const uint4 h = P.hdr[env];
         v_p = P.pos[env];
         v_c = h.w;
-        v_a = (h.x & 0xFFu) * P.size + ((h.x >> 8) & 0xFFu);
-        v_h = (h.x >> 16) & 0xFFu;
+        v_a = agent_cell_of(P, h.x);
+        v_h = hold_of(h.x);
     } else if (src == CW_SRC_INIT) {
         v_p = P.init_pos[env];
         v_c = CW_CODES_INITIAL;
@@ -310,8 +322,8 @@ __device__ __forceinline__ void load_state_uniform(const CwParams &P, int env, i
 }
 
 // ------------------------------------------------------------------------------------ step
-// One env's step() on registers (ray.py:301-378).  Shared by cw_step_kernel (one launch per step)
-// and cw_rollout_kernel (T steps in one persistent launch).
+// One env's step() on registers (ray.py:301-378).  Shared by cw_step_kernel (one launch per step), cw_step_fused_kernel (the same
+// with auto-reset), cw_rollout_kernel (T steps in one persistent launch) and cw_resident_kernel (the single-env loop).
 struct CwStepOut {
     int reward;
     bool done, success, invalid, changed;
@@ -457,8 +469,8 @@ __device__ __forceinline__ CwStepOut step_env(const CwParams &P, uint4 &h, uint3
 __device__ __forceinline__ void paint_changed_cells(const CwParams &P, int env, const uint4 &h, const uint32_t sp[8], const CwStepOut &o)
 {
     uint8_t *frame = P.obs + (size_t)env * P.frame_bytes;
-    const uint32_t hold = (h.x >> 16) & 0xFFu;
-    const uint32_t acell = (h.x & 0xFFu) * P.size + ((h.x >> 8) & 0xFFu);
+    const uint32_t hold = hold_of(h.x);
+    const uint32_t acell = agent_cell_of(P, h.x);
     if (P.raster == 1) {
         const uint32_t r0 = __umulhi(o.dirty0, P.div_magic);
         alt_paint_tile(frame, P.size, r0, o.dirty0 - r0 * P.size, code_of(h.w, slot_at(sp, o.dirty0)), o.dirty0 == acell, hold);
@@ -472,6 +484,25 @@ __device__ __forceinline__ void paint_changed_cells(const CwParams &P, int env, 
         if (o.dirty1 != 0xFFFFFFFFu)
             paint_cell(frame, P.size, o.dirty1, code_of(h.w, slot_at(sp, o.dirty1)), o.dirty1 == acell, hold, P.div_magic, o.mark1);
     }
+}
+
+// a step's outputs for env `env` (cw_step_kernel, cw_step_fused_kernel, cw_resident_kernel): reward, done, both masks and, where the
+// episode ended, its length and return
+__device__ __forceinline__ void store_step_outputs(const CwParams &P, int env, const CwStepOut &o)
+{
+    P.reward[env] = o.reward;
+    P.done[env] = o.done ? 1 : 0;
+    P.achieved_out[env] = (uint16_t)o.achieved;
+    P.desired_out[env] = (uint16_t)o.desired;
+    if (o.done) { P.episode_length[env] = (int32_t)o.step_num; P.episode_return[env] = episode_return_of(P, o); }
+}
+
+// the action of env `i` from the caller's array: int32 (act_dtype 0), int64 (1) or uint8 (2)
+__device__ __forceinline__ int load_action(const void *actions, int act_dtype, int i)
+{
+    if (act_dtype == 0) return ((const int32_t *)actions)[i];
+    if (act_dtype == 1) return (int)((const long long *)actions)[i];
+    return ((const uint8_t *)actions)[i];
 }
 
 // LOOK-AHEAD (cw_layout.h): the finished env `env` takes over the record of its next episode, if the refill kernel has left one -- the whole
@@ -532,11 +563,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwParams P, const void *ac
     const bool live = i < P.n_envs;
     bool done = false, success = false, invalid = false;
     if (live) {
-        int a;
-        if (act_dtype == 0) a = ((const int32_t *)actions)[i];
-        else if (act_dtype == 1) a = (int)((const long long *)actions)[i];
-        else a = ((const uint8_t *)actions)[i];
-
+        const int a = load_action(actions, act_dtype, i);
         uint4 h = P.hdr[i];
         uint32_t sp[8];
         unpack_pos(P.pos[i], sp);
@@ -545,11 +572,7 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwParams P, const void *ac
 
         P.hdr[i] = h;
         P.pos[i] = pack_pos(sp);
-        P.reward[i] = o.reward;
-        P.done[i] = done ? 1 : 0;
-        P.achieved_out[i] = (uint16_t)o.achieved;
-        P.desired_out[i] = (uint16_t)o.desired;
-        if (done) { P.episode_length[i] = (int32_t)o.step_num; P.episode_return[i] = episode_return_of(P, o); }
+        store_step_outputs(P, i, o);
         if (paint_dirty && o.changed) paint_changed_cells(P, i, h, sp, o);   // render_edit, :358
     }
     const unsigned long long m_done = CW_BALLOT(done), m_succ = CW_BALLOT(success), m_inv = CW_BALLOT(invalid);
@@ -973,7 +996,7 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_rollout_kernel(CwP
         }
         const unsigned long long m_pop = CW_BALLOT(popped);
         unsigned long long m = m_all & ~m_pop;
-        while (m) {                                  // ... else the slow way, one finished env at a time, whole wave
+        while (m) {                                  // ... else the slow way, one finished env at a time, whole wave (as in fused_step; kept apart: a shared form changed both kernels' code)
             const int l = __builtin_ctzll(m);
             m &= m - 1;
             const int env_l = env0 + l;
@@ -1039,29 +1062,8 @@ __global__ __launch_bounds__(CW_WAVE) void cw_resident_kernel(CwParams P, CwResi
                 const CwStepOut o = step_env(P, h, sp, a, [&]() { return ip; });
                 P.hdr[0] = h;
                 P.pos[0] = pack_pos(sp);
-                P.reward[0] = o.reward;
-                P.done[0] = o.done ? 1 : 0;
-                P.achieved_out[0] = (uint16_t)o.achieved;
-                P.desired_out[0] = (uint16_t)o.desired;
-                if (o.done) { P.episode_length[0] = (int32_t)o.step_num; P.episode_return[0] = episode_return_of(P, o); }
-                if (paint_dirty && o.changed) {                                  // render_edit, ray.py:522-557 (as in cw_step_kernel)
-                    uint8_t *frame = P.obs;
-                    const uint32_t hold = (h.x >> 16) & 0xFFu;
-                    const uint32_t acell = (h.x & 0xFFu) * P.size + ((h.x >> 8) & 0xFFu);
-                    if (P.raster == 1) {
-                        const uint32_t r0 = __umulhi(o.dirty0, P.div_magic);
-                        alt_paint_tile(frame, P.size, r0, o.dirty0 - r0 * P.size, code_of(h.w, slot_at(sp, o.dirty0)), o.dirty0 == acell, hold);
-                        if (o.dirty1 != 0xFFFFFFFFu) {
-                            const uint32_t r1 = __umulhi(o.dirty1, P.div_magic);
-                            alt_paint_tile(frame, P.size, r1, o.dirty1 - r1 * P.size, code_of(h.w, slot_at(sp, o.dirty1)), o.dirty1 == acell, hold);
-                        }
-                        alt_paint_strip(frame, P.size, hold, 0, 1, false);
-                    } else {
-                        paint_cell(frame, P.size, o.dirty0, code_of(h.w, slot_at(sp, o.dirty0)), o.dirty0 == acell, hold, P.div_magic, o.mark0);
-                        if (o.dirty1 != 0xFFFFFFFFu)
-                            paint_cell(frame, P.size, o.dirty1, code_of(h.w, slot_at(sp, o.dirty1)), o.dirty1 == acell, hold, P.div_magic, o.mark1);
-                    }
-                }
+                store_step_outputs(P, 0, o);
+                if (paint_dirty && o.changed) paint_changed_cells(P, 0, h, sp, o);   // render_edit, ray.py:522-557
                 atomicAdd(&P.counters[0], 1ull);
                 if (o.done) atomicAdd(&P.counters[1], 1ull);
                 if (o.success) atomicAdd(&P.counters[2], 1ull);
@@ -1072,16 +1074,12 @@ __global__ __launch_bounds__(CW_WAVE) void cw_resident_kernel(CwParams P, CwResi
                 uint32_t bp[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++) bp[k] = __builtin_amdgcn_readlane(sp[k], 0);
-                const uint32_t agent_cell = (hx & 0xFFu) * P.size + ((hx >> 8) & 0xFFu), hold = (hx >> 16) & 0xFFu;
+                const uint32_t agent_cell = agent_cell_of(P, hx), hold = hold_of(hx);
                 for (int cell = lane; cell < P.ncell; cell += CW_WAVE) {
                     const uint32_t code = code_of(codes, slot_at(bp, (uint32_t)cell));
                     uint32_t bits = code ? (1u << (code - 1)) : 0u;
                     if ((uint32_t)cell == agent_cell) bits |= (1u << 8) | (hold ? (1u << (8 + hold)) : 0u);
-                    u32x3 dd;
-                    dd.x = (bits & 1u) | ((bits >> 1 & 1u) << 8) | ((bits >> 2 & 1u) << 16) | ((bits >> 3 & 1u) << 24);
-                    dd.y = (bits >> 4 & 1u) | ((bits >> 5 & 1u) << 8) | ((bits >> 6 & 1u) << 16) | ((bits >> 7 & 1u) << 24);
-                    dd.z = (bits >> 8 & 1u) | ((bits >> 9 & 1u) << 8) | ((bits >> 10 & 1u) << 16) | ((bits >> 11 & 1u) << 24);
-                    *(u32x3_a4 *)(P.res_onehot + 12 * cell) = dd;
+                    *(u32x3_a4 *)(P.res_onehot + 12 * cell) = onehot_dwords(bits);
                 }
             }
             __threadfence_system();                                              // every lane's stores, then (lane 0) the answer
@@ -1128,10 +1126,7 @@ __device__ __forceinline__ void fused_step(const CwParams &P, const void *action
     const int env = env0 + lane;
     const bool live = wave_live && lane < epw && env < P.n_envs;
     const int e = live ? env : (wave_live ? env0 : 0);      // idle lanes shadow a valid env (their results are dropped)
-    int a;
-    if (act_dtype == 0) a = ((const int32_t *)actions)[e];
-    else if (act_dtype == 1) a = (int)((const long long *)actions)[e];
-    else a = ((const uint8_t *)actions)[e];
+    const int a = load_action(actions, act_dtype, e);
     uint4 h = P.hdr[e];
     uint32_t sp[8];
     unpack_pos(P.pos[e], sp);
@@ -1142,11 +1137,7 @@ __device__ __forceinline__ void fused_step(const CwParams &P, const void *action
     const CwStepOut o = step_env(P, h, sp, a, [&]() { return ip; });
     const bool done = live && o.done;
     if (live) {
-        P.reward[env] = o.reward;
-        P.done[env] = o.done ? 1 : 0;
-        P.achieved_out[env] = (uint16_t)o.achieved;
-        P.desired_out[env] = (uint16_t)o.desired;
-        if (o.done) { P.episode_length[env] = (int32_t)o.step_num; P.episode_return[env] = episode_return_of(P, o); }
+        store_step_outputs(P, env, o);
         if constexpr (PAINT == 1) { if (o.changed && !o.done) paint_changed_cells(P, env, h, sp, o); }      // render_edit, :358 (a finished env is repainted whole below)
     }
     // auto-reset, look-ahead first: a finished env takes its next episode's record over in its own lane ...
@@ -1194,14 +1185,14 @@ __device__ __forceinline__ void fused_step(const CwParams &P, const void *action
             CwPaintJob &j = s_jobs[jmine + 2];
             j.pos = pack_pos(sp_last);
             j.codes = h_last.w;
-            j.agent_hold_kind = ((h_last.x & 0xFFu) * P.size + ((h_last.x >> 8) & 0xFFu)) | (((h_last.x >> 16) & 0xFFu) << 16) | (CW_JOB_TERMINAL << 24);
+            j.agent_hold_kind = agent_cell_of(P, h_last.x) | (hold_of(h_last.x) << 16) | (CW_JOB_TERMINAL << 24);
             j.env = (uint32_t)env;
         }
         if (popped) {
             CwPaintJob &j0 = s_jobs[jmine], &j1 = s_jobs[jmine + 1];
             j0.pos = pack_pos(sp);                    // (the new episode's slots are its reset-time placement)
             j0.codes = CW_CODES_INITIAL;
-            j0.agent_hold_kind = ((h.x & 0xFFu) * P.size + ((h.x >> 8) & 0xFFu)) | (CW_JOB_INIT << 24);
+            j0.agent_hold_kind = agent_cell_of(P, h.x) | (CW_JOB_INIT << 24);
             j0.env = (uint32_t)env;
             j1.pos = goal.pos;
             j1.codes = goal.codes;
@@ -1210,7 +1201,7 @@ __device__ __forceinline__ void fused_step(const CwParams &P, const void *action
         }
     }
     unsigned long long m = m_all & ~m_pop;           // envs that found no record: reset here, one at a time, by the whole wave (rare)
-    while (m) {
+    while (m) {                                      // (as in cw_rollout_kernel, plus the paint jobs)
         const int l = __builtin_ctzll(m);
         m &= m - 1;
         const int env_l = env0 + l;
@@ -1699,17 +1690,11 @@ __global__ __launch_bounds__(256) void cw_export_onehot_kernel(CwParams P, uint8
         unpack_pos(which == 1 ? P.goal_pos[env] : which == 2 ? P.init_pos[env] : P.pos[env], sp);
         const uint32_t codes = which == 1 ? P.goal_codes[env] : which == 2 ? CW_CODES_INITIAL : h.w;
         const uint32_t code = code_of(codes, slot_at(sp, cell));
-        const uint32_t agent_cell = which == 1 ? (uint32_t)P.goal_agent[env] : which == 2 ? (uint32_t)P.init_agent[env]
-                                                                                            : (h.x & 0xFFu) * P.size + ((h.x >> 8) & 0xFFu);
-        const uint32_t hold = which ? 0u : (h.x >> 16) & 0xFFu;
+        const uint32_t agent_cell = which == 1 ? (uint32_t)P.goal_agent[env] : which == 2 ? (uint32_t)P.init_agent[env] : agent_cell_of(P, h.x);
+        const uint32_t hold = which ? 0u : hold_of(h.x);
         uint32_t bits = code ? (1u << (code - 1)) : 0u;
         if (cell == agent_cell) bits |= (1u << 8) | (hold ? (1u << (8 + hold)) : 0u);
-        // 12 bytes of 0/1
-        u32x3 d;
-        d.x = (bits & 1u) | ((bits >> 1 & 1u) << 8) | ((bits >> 2 & 1u) << 16) | ((bits >> 3 & 1u) << 24);
-        d.y = (bits >> 4 & 1u) | ((bits >> 5 & 1u) << 8) | ((bits >> 6 & 1u) << 16) | ((bits >> 7 & 1u) << 24);
-        d.z = (bits >> 8 & 1u) | ((bits >> 9 & 1u) << 8) | ((bits >> 10 & 1u) << 16) | ((bits >> 11 & 1u) << 24);
-        *(u32x3_a4 *)(out + g * 12) = d;
+        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(bits);
     }
 }
 
@@ -1917,10 +1902,12 @@ static void cw_launch_sweep(const CwParams &P, const CwTuning &tn, uint8_t *fram
     }
 }
 
+// workgroups of CW_RESET_WAVES waves that hold `waves` waves
+static inline int cw_wave_blocks(int waves) { return (waves + CW_RESET_WAVES - 1) / CW_RESET_WAVES; }
 static inline int cw_reset_grid(const CwTuning &tn, int jobs)
 {
     // persistent: one wave per env in flight, reset_blocks_per_cu workgroups (x 4 waves) per CU at most
-    int blocks = (jobs + CW_RESET_WAVES - 1) / CW_RESET_WAVES;
+    int blocks = cw_wave_blocks(jobs);
     if (blocks > tn.n_cu * tn.reset_blocks_per_cu) blocks = tn.n_cu * tn.reset_blocks_per_cu;
     if (blocks < 1) blocks = 1;
     return blocks;
@@ -1950,8 +1937,8 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
         const int epw = cw_envs_per_wave(n, tn.step_envs_per_wave);
         const int waves = (n + epw - 1) / epw;
         const int paint = obs_mode == 2 ? 1 : obs_mode == 1 ? 2 : 0;
-        hipLaunchKernelGGL(cw_step_fused_variant(paint, paint != 0 && P->terminal_img != nullptr), dim3((waves + CW_RESET_WAVES - 1) / CW_RESET_WAVES),
-                           dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, actions, act_dtype, epw);
+        hipLaunchKernelGGL(cw_step_fused_variant(paint, paint != 0 && P->terminal_img != nullptr), dim3(cw_wave_blocks(waves)), dim3(CW_RESET_WAVES * CW_WAVE),
+                           0, st, *P, actions, act_dtype, epw);
     } else {
         hipLaunchKernelGGL(cw_step_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *P, actions, act_dtype, obs_mode == 2 ? 1 : 0);
     }
@@ -1973,8 +1960,7 @@ hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, 
 {
     const int epw = cw_envs_per_wave(P->n_envs);
     const int waves = (P->n_envs + epw - 1) / epw;
-    hipLaunchKernelGGL(cw_rollout_kernel, dim3((waves + CW_RESET_WAVES - 1) / CW_RESET_WAVES), dim3(CW_RESET_WAVES * CW_WAVE), 0, st,
-                       *P, actions, T, rewards, dones, epw);
+    hipLaunchKernelGGL(cw_rollout_kernel, dim3(cw_wave_blocks(waves)), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, actions, T, rewards, dones, epw);
     return hipGetLastError();
 }
 

@@ -43,8 +43,8 @@ struct CwMenuDev {
     int32_t reward_subset;
 };
 
-// Host-side launch tuning of one engine (defaults = the measured best; the CW_TUNE_* environment variables read in
-// cw_create override them for experiments).
+// Host-side launch tuning of one engine (defaults = the measured best; the CW_TUNE_* environment variables, read once by
+// cw_create (cw_engine.cpp: read_tuning), override them for experiments; a value out of range keeps the default).
 struct CwTuning {
     int n_cu = 256;                 // compute units of the engine's device (hipDeviceProp_t::multiProcessorCount, set by cw_create)
     int period16 = 0;               // the sweep's CLOCK: a wave's jobs (4-KiB pieces) start one period apart; in 1/16 of a 10-ns tick of the 100-MHz clock (0: unclocked)
