@@ -108,6 +108,16 @@ class cwh_guard(C.Structure):
                 ('probes', C.c_int32), ('probe_need', C.c_int32), ('recover_need', C.c_int32), ('probing', C.c_int32), ('recovering', C.c_int32)]
 
 
+class cwh_tuning(C.Structure):
+    """the CW_TUNE_* variables' values (csrc/cw_host.h: cwh_read_tuning)"""
+    _fields_ = [(f, C.c_int32) for f in ('render_chunk_rounds', 'step_envs_per_wave', 'gather', 'gather_max_size', 'small_frame_bytes',
+                                         'small_blocks_per_cu', 'small_launch_mb', 'reset_blocks_per_cu', 'guard', 'verbose', 'lookahead',
+                                         'la_period', 'rollout_segment', 'pad')] + \
+              [(f, C.c_double) for f in ('head_notch', 'busy_notch', 'period_ns', 'rate_tbs')]
+
+
+cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variable's text or None (a pointer: ctypes cannot return a char* a callback made)
+
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
 CWH_CKPT_SECTIONS = 22
 
@@ -127,6 +137,7 @@ HOST_HELPERS = {
     'cwh_sweep_periods': (None, [C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'cwh_guard_scheduled_ms': (C.c_double, [C.c_double, C.c_int32, C.c_int32, C.c_double]),
     'cwh_la_adapt': (C.c_int32, [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32)]),
+    'cwh_read_tuning': (None, [cwh_lookup, _VP, C.POINTER(cwh_tuning)]),
 }
 
 

@@ -360,29 +360,44 @@ static hipEvent_t *sweep_guard_tick(cw_engine *e, hipStream_t st)
 // It runs on a fresh engine, whose values are the defaults: a value out of its range keeps the default.  (The default refill period follows P.max_steps.)
 static void read_tuning(cw_engine *e)
 {
-    auto geti = [](const char *k, int d, int lo = INT_MIN, int hi = INT_MAX) { const char *v = getenv(k); const int x = v ? atoi(v) : d; return x >= lo && x <= hi ? x : d; };
-    auto getd = [](const char *k, double d, double lo) { const char *v = getenv(k); const double x = v ? atof(v) : d; return x >= lo ? x : d; };
     CwTuning &tn = e->tune;
-    tn.render_chunk_rounds = geti("CW_TUNE_RENDER_CHUNK_ROUNDS", tn.render_chunk_rounds, 0);
-    const int epw = geti("CW_TUNE_STEP_ENVS_PER_WAVE", tn.step_envs_per_wave);
-    tn.step_envs_per_wave = epw == 8 || epw == 16 || epw == 32 || epw == 64 ? epw : tn.step_envs_per_wave;
-    tn.gather = geti("CW_TUNE_GATHER", tn.gather);
-    tn.gather_max_size = geti("CW_TUNE_GATHER_MAX_SIZE", tn.gather_max_size, 0, 9);          // (cw_render_gather_kernel's tables: frames under 4 KiB)
-    tn.small_frame_bytes = geti("CW_TUNE_SMALL_FRAME_BYTES", tn.small_frame_bytes, 0);
-    tn.small_blocks_per_cu = geti("CW_TUNE_SMALL_BLOCKS", tn.small_blocks_per_cu, 1, 8);
-    tn.small_launch_bytes = (long long)geti("CW_TUNE_SMALL_LAUNCH_MB", (int)(tn.small_launch_bytes >> 20), 0) << 20;
-    tn.reset_blocks_per_cu = geti("CW_TUNE_RESET_BLOCKS", tn.reset_blocks_per_cu, 1, 16);
-    e->head_notch = getd("CW_TUNE_HEAD_NOTCH", e->head_notch, 0);
-    e->busy_notch = getd("CW_TUNE_BUSY_NOTCH", e->busy_notch, 0);
-    e->tune_period_ns = getd("CW_TUNE_PERIOD_NS", -1, 0);
-    e->tune_rate_tbs = getd("CW_TUNE_RATE_TBS", -1, 0);
-    e->tune_guard = geti("CW_TUNE_GUARD", 1) != 0;
-    e->verbose = getenv("CW_TUNE_VERBOSE") != nullptr;
-    e->tune_lookahead = geti("CW_TUNE_LOOKAHEAD", 1) != 0;
-    const int la_period = geti("CW_TUNE_LA_PERIOD", 0, 1);                  // (a forced refill period, no adaptation: profiles/r06_experiments.txt D)
-    e->la_adaptive = la_period == 0;
-    e->la_period = e->la_period_max = (unsigned)(la_period ? la_period : la_period_for(e->P.max_steps));
-    e->rollout_segment = geti("CW_TUNE_ROLLOUT_SEGMENT", e->rollout_segment, -1);
+    cwh_tuning t{};                    // the defaults in, the variables' values out (cw_host.cpp: the parsing and the ranges, tested on the CPU)
+    t.render_chunk_rounds = tn.render_chunk_rounds;
+    t.step_envs_per_wave = tn.step_envs_per_wave;
+    t.gather = tn.gather;
+    t.gather_max_size = tn.gather_max_size;
+    t.small_frame_bytes = tn.small_frame_bytes;
+    t.small_blocks_per_cu = tn.small_blocks_per_cu;
+    t.small_launch_mb = (int32_t)(tn.small_launch_bytes >> 20);
+    t.reset_blocks_per_cu = tn.reset_blocks_per_cu;
+    t.guard = 1;
+    t.verbose = 0;
+    t.lookahead = 1;
+    t.la_period = 0;
+    t.rollout_segment = e->rollout_segment;
+    t.head_notch = e->head_notch;
+    t.busy_notch = e->busy_notch;
+    t.period_ns = -1;
+    t.rate_tbs = -1;
+    cwh_read_tuning([](void *, const char *k) -> const char * { return getenv(k); }, nullptr, &t);
+    tn.render_chunk_rounds = t.render_chunk_rounds;
+    tn.step_envs_per_wave = t.step_envs_per_wave;
+    tn.gather = t.gather;
+    tn.gather_max_size = t.gather_max_size;
+    tn.small_frame_bytes = t.small_frame_bytes;
+    tn.small_blocks_per_cu = t.small_blocks_per_cu;
+    tn.small_launch_bytes = (long long)t.small_launch_mb << 20;
+    tn.reset_blocks_per_cu = t.reset_blocks_per_cu;
+    e->head_notch = t.head_notch;
+    e->busy_notch = t.busy_notch;
+    e->tune_period_ns = t.period_ns;
+    e->tune_rate_tbs = t.rate_tbs;
+    e->tune_guard = t.guard != 0;
+    e->verbose = t.verbose != 0;
+    e->tune_lookahead = t.lookahead != 0;
+    e->la_adaptive = t.la_period == 0;
+    e->la_period = e->la_period_max = (unsigned)(t.la_period ? t.la_period : la_period_for(e->P.max_steps));
+    e->rollout_segment = t.rollout_segment;
 }
 
 extern "C" {

@@ -3,6 +3,9 @@
 #include "cw_host.h"
 
 #include <algorithm>
+#include <cerrno>
+#include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -261,3 +264,57 @@ int32_t cwh_la_adapt(int32_t period, int32_t period_max, uint64_t slow_delta, in
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------ the CW_TUNE_* variables
+// Whole-text parses: strtol / strtod must consume everything but surrounding whitespace, and the value must be in range (an int that overflows a long,
+// or a double that overflows, sets ERANGE; nan and inf are no tuning values).  On any failure the field keeps what it held.
+static bool tail_is_blank(const char *end)
+{
+    while (*end == ' ' || (*end >= '\t' && *end <= '\r')) end++;
+    return *end == '\0';
+}
+static void tune_int(cwh_lookup lookup, void *ctx, const char *name, int32_t *field, long lo, long hi)
+{
+    const char *s = lookup(ctx, name);
+    if (!s) return;
+    char *end = nullptr;
+    errno = 0;
+    const long v = strtol(s, &end, 10);
+    if (end == s || errno == ERANGE || !tail_is_blank(end) || v < lo || v > hi) return;
+    *field = (int32_t)v;
+}
+static void tune_real(cwh_lookup lookup, void *ctx, const char *name, double *field, double lo)
+{
+    const char *s = lookup(ctx, name);
+    if (!s) return;
+    char *end = nullptr;
+    errno = 0;
+    const double v = strtod(s, &end);
+    if (end == s || errno == ERANGE || !tail_is_blank(end) || !std::isfinite(v) || v < lo) return;
+    *field = v;
+}
+
+extern "C" void cwh_read_tuning(cwh_lookup lookup, void *ctx, cwh_tuning *t)
+{
+    tune_int(lookup, ctx, "CW_TUNE_RENDER_CHUNK_ROUNDS", &t->render_chunk_rounds, 0, INT32_MAX);
+    int32_t epw = t->step_envs_per_wave;
+    tune_int(lookup, ctx, "CW_TUNE_STEP_ENVS_PER_WAVE", &epw, 8, 64);
+    if (epw == 8 || epw == 16 || epw == 32 || epw == 64) t->step_envs_per_wave = epw;
+    tune_int(lookup, ctx, "CW_TUNE_GATHER", &t->gather, INT32_MIN, INT32_MAX);
+    tune_int(lookup, ctx, "CW_TUNE_GATHER_MAX_SIZE", &t->gather_max_size, 0, 9);          // (cw_render_gather_kernel's tables: frames under 4 KiB)
+    tune_int(lookup, ctx, "CW_TUNE_SMALL_FRAME_BYTES", &t->small_frame_bytes, 0, INT32_MAX);
+    tune_int(lookup, ctx, "CW_TUNE_SMALL_BLOCKS", &t->small_blocks_per_cu, 1, 8);
+    tune_int(lookup, ctx, "CW_TUNE_SMALL_LAUNCH_MB", &t->small_launch_mb, 0, INT32_MAX);
+    tune_int(lookup, ctx, "CW_TUNE_RESET_BLOCKS", &t->reset_blocks_per_cu, 1, 16);
+    tune_real(lookup, ctx, "CW_TUNE_HEAD_NOTCH", &t->head_notch, 0);
+    tune_real(lookup, ctx, "CW_TUNE_BUSY_NOTCH", &t->busy_notch, 0);
+    tune_real(lookup, ctx, "CW_TUNE_PERIOD_NS", &t->period_ns, 0);
+    tune_real(lookup, ctx, "CW_TUNE_RATE_TBS", &t->rate_tbs, 0);
+    tune_int(lookup, ctx, "CW_TUNE_GUARD", &t->guard, INT32_MIN, INT32_MAX);
+    t->guard = t->guard != 0;
+    if (lookup(ctx, "CW_TUNE_VERBOSE")) t->verbose = 1;
+    tune_int(lookup, ctx, "CW_TUNE_LOOKAHEAD", &t->lookahead, INT32_MIN, INT32_MAX);
+    t->lookahead = t->lookahead != 0;
+    tune_int(lookup, ctx, "CW_TUNE_LA_PERIOD", &t->la_period, 1, INT32_MAX);            // (a forced refill period, no adaptation: profiles/r06_experiments.txt D)
+    tune_int(lookup, ctx, "CW_TUNE_ROLLOUT_SEGMENT", &t->rollout_segment, -1, INT32_MAX);
+}

@@ -76,6 +76,32 @@ double cwh_guard_scheduled_ms(double sweep_jobs, int32_t period16, int32_t perio
 #define CWH_LA_QUIET 8
 int32_t cwh_la_adapt(int32_t period, int32_t period_max, uint64_t slow_delta, int32_t *quiet);
 
+// ---- the CW_TUNE_* variables (cw_engine.cpp: read_tuning, once at cw_create).  `t` holds the defaults on entry; a variable whose text is
+// a number in its range replaces its field.  Text that is empty, not a number, has trailing characters, does not fit, or is nan / inf keeps the default,
+// like a value out of range; whitespace around the number is accepted.  `lookup` maps a variable's name to its text (null: unset) -- getenv, or a test's dict.
+typedef struct cwh_tuning {
+    int32_t render_chunk_rounds;    // CW_TUNE_RENDER_CHUNK_ROUNDS >= 0
+    int32_t step_envs_per_wave;     // CW_TUNE_STEP_ENVS_PER_WAVE 8 / 16 / 32 / 64
+    int32_t gather;                 // CW_TUNE_GATHER any int (0: off)
+    int32_t gather_max_size;        // CW_TUNE_GATHER_MAX_SIZE 0 .. 9
+    int32_t small_frame_bytes;      // CW_TUNE_SMALL_FRAME_BYTES >= 0
+    int32_t small_blocks_per_cu;    // CW_TUNE_SMALL_BLOCKS 1 .. 8
+    int32_t small_launch_mb;        // CW_TUNE_SMALL_LAUNCH_MB >= 0
+    int32_t reset_blocks_per_cu;    // CW_TUNE_RESET_BLOCKS 1 .. 16
+    int32_t guard;                  // CW_TUNE_GUARD any int -> 0 / 1
+    int32_t verbose;                // CW_TUNE_VERBOSE: 1 when set at all, whatever its text ("0" included)
+    int32_t lookahead;              // CW_TUNE_LOOKAHEAD any int -> 0 / 1
+    int32_t la_period;              // CW_TUNE_LA_PERIOD >= 1 (the default 0: adaptive)
+    int32_t rollout_segment;        // CW_TUNE_ROLLOUT_SEGMENT >= -1
+    int32_t pad;
+    double head_notch;              // CW_TUNE_HEAD_NOTCH >= 0
+    double busy_notch;              // CW_TUNE_BUSY_NOTCH >= 0
+    double period_ns;               // CW_TUNE_PERIOD_NS >= 0 (the default -1: none)
+    double rate_tbs;                // CW_TUNE_RATE_TBS >= 0 (the default -1: none)
+} cwh_tuning;
+typedef const char *(*cwh_lookup)(void *ctx, const char *name);
+void cwh_read_tuning(cwh_lookup lookup, void *ctx, cwh_tuning *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -497,11 +497,12 @@ __device__ __forceinline__ void store_step_outputs(const CwParams &P, int env, c
     if (o.done) { P.episode_length[env] = (int32_t)o.step_num; P.episode_return[env] = episode_return_of(P, o); }
 }
 
-// the action of env `i` from the caller's array: int32 (act_dtype 0), int64 (1) or uint8 (2)
+// the action of env `i` from the caller's array: int32 (act_dtype 0), int64 (1) or uint8 (2).  An int64 outside the int range is -1, the counted no-op
+// like every value outside 0..5 (a plain cast would run 2^32 + 2 as Down)
 __device__ __forceinline__ int load_action(const void *actions, int act_dtype, int i)
 {
     if (act_dtype == 0) return ((const int32_t *)actions)[i];
-    if (act_dtype == 1) return (int)((const long long *)actions)[i];
+    if (act_dtype == 1) { const long long a = ((const long long *)actions)[i]; return a == (long long)(int)a ? (int)a : -1; }
     return ((const uint8_t *)actions)[i];
 }
 

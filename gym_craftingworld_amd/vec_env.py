@@ -349,6 +349,8 @@ class CraftingWorldVecEnv:
             if a.size != self.num_envs:
                 raise ValueError('expected %d actions, got %d' % (self.num_envs, a.size))
             self._host_actions[:] = a
+            if a.dtype != np.int32:                          # (a wider value must not wrap into 0..5: every one outside it is the counted no-op)
+                self._host_actions[(a < 0) | (a > 5)] = -1
             L.check(self._lib.cw_step(self._h, C.c_void_p(self._host_actions.ctypes.data), L.CW_ACT_I32, self._stream()),
                     'cw_step', self._lib)
             self._pending = True
@@ -415,11 +417,18 @@ class CraftingWorldVecEnv:
 
     def rollout(self, actions, record=True):
         """T consecutive steps (auto-reset included) in ONE persistent kernel launch, for action streams
-        known up front: actions uint8 [T, N] on the device.  Bit-identical to T calls of step().
+        known up front: actions uint8 [T, N] on the device (any other dtype is converted: values outside 0..5 become 255, the counted no-op
+        they are in step()).  Bit-identical to T calls of step().
         State-only observation mode.  -> (rewards int32 [T,N], dones bool [T,N]) if record."""
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions), device=self.device)
-        actions = actions.to(device=self.device, dtype=torch.uint8).contiguous()
+        actions = actions.to(device=self.device)
+        if actions.dtype != torch.uint8:
+            if actions.dtype not in _ACT_DTYPES:
+                actions = actions.to(torch.int32)            # (as step_async converts it)
+            invalid = (actions < 0) | (actions > 5)          # (a plain cast wraps modulo 256: 258 would run as Down)
+            actions = actions.to(torch.uint8).masked_fill_(invalid, 255)
+        actions = actions.contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
             raise ValueError('actions must have shape [T, num_envs]')
         T = actions.shape[0]

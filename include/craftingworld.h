@@ -179,8 +179,8 @@ int cw_reset(cw_engine *e, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
- * PickUp,Drop (ACTIONS, ray.py:130-131).  Out-of-range values are counted in counters[3] and
- * executed as a state-preserving step (step_num += 1, reward -1).  Enqueues the step kernel -- engines with auto_reset: finished envs take
+ * PickUp,Drop (ACTIONS, ray.py:130-131).  Out-of-range values of any dtype (an int64 beyond the int range included) are counted in
+ * counters[3] and executed as a state-preserving step (step_num += 1, reward -1).  Enqueues the step kernel -- engines with auto_reset: finished envs take
  * over the record of their next episode, computed ahead of time by a refill kernel that rides on every max_steps/4-th call (8 ... 64; fewer steps apart while
  * envs finish faster than that: the period follows the count of slow resets the card reports, never waited for); every env keeps a queue of four such records,
  * and one that finishes a fifth time between two refills is reset on the spot -- and, in CW_OBS_PIXELS_FULL, the sweep that paints the observation array.

@@ -2,8 +2,8 @@
 without a GPU does, each in a subprocess with libasan preloaded --
   * the C oracle (make -C oracle asan: -fsanitize=address,undefined) replays reference fixtures of every kind (CW_ORACLE_SO picks the build);
   * the engine's HIP-free host logic (csrc/cw_host.cpp by g++ -fsanitize=address,undefined -fno-sanitize-recover: libcw_host_asan.so; CW_HOST_LIB
-    picks it) runs the hypothesis properties of the MT19937 state conversion and rewind, the guard's synthetic traces, the dense views and the
-    checkpoint-size arithmetic.
+    picks it) runs the hypothesis properties of the MT19937 state conversion and rewind, the guard's synthetic traces, the dense views, the
+    checkpoint-size arithmetic and the parsing of the CW_TUNE_* variables.
 GPU AddressSanitizer is not available on the pool: the kernels' memory safety is argued by the parity tests reading every byte they write."""
 import os
 import subprocess
@@ -44,9 +44,10 @@ def test_oracle_replays_fixtures_under_asan_and_ubsan():
 def test_host_logic_under_asan_and_ubsan():
     subprocess.check_call(['make', '-C', os.path.join(ROOT, 'gym_craftingworld_amd', 'csrc'), 'host_asan'], stdout=subprocess.DEVNULL)
     so = os.path.join(ROOT, 'gym_craftingworld_amd', 'libcw_host_asan.so')
-    out = _pytest_under_asan({'CW_HOST_LIB': so}, ['tests/test_guard_logic.py', 'tests/test_host_logic.py', '-k',
+    out = _pytest_under_asan({'CW_HOST_LIB': so}, ['tests/test_guard_logic.py', 'tests/test_host_logic.py', 'tests/test_tuning_logic.py', '-k',
                                                    'guard or steady or late or alternating or saturated or probes or delay or disturbance or periods or dense or refill_period or '
-                                                   'checkpoint_section or mt_conversion_property or mt_rewind_property'])
+                                                   'checkpoint_section or mt_conversion_property or mt_rewind_property or variable or verbose or special_sets or '
+                                                   'malformed_values or flags_and_gather'])
     assert ' passed' in out and 'failed' not in out, out
     n = int(out.strip().splitlines()[-1].split(' passed')[0].split()[-1])
     assert n >= 15, out
