@@ -242,17 +242,25 @@ class OracleBatch:
 
     def reset(self):
         for e in self.envs:
-            e.reset()
+            e._lib.cwo_reset(e._h)                        # (OracleEnv.reset() without the observation dict, which nobody reads here)
 
-    def step(self, actions):
-        """-> (reward[N] int32, done[N] bool); done envs are reset (their obs is the new episode's)."""
+    def step(self, actions, details=False, auto_reset=True):
+        """-> (reward[N] int32, done[N] bool); done envs are reset (their obs is the new episode's) unless auto_reset=False.
+        details=True: -> (reward, done, achieved[N] int64, terminal): every env's achieved mask BEFORE the reset, and
+        {i: the frame env i finished on} for the done envs."""
         rew = np.empty(self.num_envs, dtype=np.int32)
         done = np.zeros(self.num_envs, dtype=bool)
+        ach = np.empty(self.num_envs, dtype=np.int64)
+        term = {}
         for i, e in enumerate(self.envs):
-            _, rew[i], done[i], _ = e.step(int(actions[i]))
-            if done[i]:
+            o, rew[i], done[i], _ = e.step(int(actions[i]))
+            if details:
+                ach[i] = e.view().achieved
+                if done[i]:
+                    term[i] = o['observation'].copy()
+            if done[i] and auto_reset:
                 e.reset()
-        return rew, done
+        return (rew, done, ach, term) if details else (rew, done)
 
     def rollout(self, actions, nthreads=1, record=False):
         """actions int8 [T,N]; returns env-steps executed (and reward/done arrays if record)."""

@@ -31,8 +31,8 @@ def test_c_demo_matches_oracle():
     m = re.search(r'env_steps (\d+) episodes (\d+) successes (\d+) reward_sum_sampled (-?\d+) frame17_fnv ([0-9a-f]{8})', out)
     assert m, out
     N, T = 1024, 600
-    states = [np.random.RandomState(5000 + i).get_state() for i in range(N)]
-    ora = OracleBatch(N, rng_states=[(s[1], s[2]) for s in states], size=(21, 21), max_steps=300)
+    from oracle_replay import np_states
+    ora = OracleBatch(N, rng_states=list(zip(*np_states(N, 5000))), size=(21, 21), max_steps=300)
     ora.reset()
     s = np.uint32(12345)
     acts = np.empty(T * N, dtype=np.int8)

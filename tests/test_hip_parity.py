@@ -13,6 +13,8 @@ import torch
 
 
 from golden_util import crc, fixture_names, load
+from oracle_replay import (FRAMES, VIEWS, make_env, np_states, one_hot_of, oracle_arrays, oracle_kw, record_steps, replay_against_oracle, same,
+                           same_states, same_terminal, set_phase)
 
 
 pytestmark = pytest.mark.gpu
@@ -20,13 +22,6 @@ pytestmark = pytest.mark.gpu
 
 TASKS = ['MakeBread', 'EatBread', 'BuildHouse', 'ChopTree', 'ChopRock', 'GoToHouse', 'MoveAxe', 'MoveHammer',
          'MoveSticks']
-
-
-def _np_states(n, base):
-    sts = [np.random.RandomState(base + i).get_state() for i in range(n)]
-    keys = np.stack([s[1] for s in sts]).astype(np.uint32)
-    pos = np.array([s[2] for s in sts], dtype=np.int32)
-    return keys, pos
 
 
 def _hdr_fields(hdr):
@@ -51,67 +46,22 @@ _MENUS8 = [dict(), dict(selected_tasks=TASKS[::-1]), dict(selected_tasks=TASKS[:
 def test_every_env_of_the_full_size_batches_against_the_oracle(N, size, T, menus, raster):
     """BASELINE configs[2], [4] and [3]'s per-GPU share at FULL size with EVERY env checked against the CPU oracle, not a sample (the round-4 verdict's
     caveat): full frames, auto-reset, pre-generated random actions, episodes of 37 steps with the phases spread out (envs finish on every step, at least
-    once each on the way).  The engine records reward and done of every step on the device; the oracle then replays the same actions in slices of
-    8 192 envs on all host threads (cwo_batch_rollout) and every reward, every done, and at the end every env's three frames, state and RNG stream must
-    be the engine's.  Also at that size: the AltObs raster, the Flat id's 8x8 default (four workgroups per CU) and 5x5 (the gather painter)."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
-    from oracle import OracleBatch
-    SL = 8192
+    once each on the way).  The engine records reward and done of every step on the device; the oracle then replays the same actions
+    (replay_against_oracle) and every reward, every done, and at the end every env's three frames, state, episode count and RNG state (key and
+    position, exactly) must be the engine's.  Also at that size: the AltObs raster, the Flat id's 8x8 default (four workgroups per CU) and 5x5 (the
+    gather painter)."""
     kw = dict(size=(size, size), max_steps=37)
     env_menu = (np.arange(N) % 8).astype(np.uint8) if menus else None
-    env = CraftingWorldVecEnv(N, obs_mode='pixels', seed=77, raster=raster, **kw, **(dict(task_menus=_MENUS8, env_menu=env_menu) if menus else {}))
-    if raster == 'alt':
-        kw['alt_obs'] = True                                 # (the oracle's name for CraftingWorldEnvAltObs's rasteriser)
-    keys, pos = env.get_rng_states()
+    env, keys, pos = make_env(N, obs_mode='pixels', seed=77, raster=raster, **kw, **(dict(task_menus=_MENUS8, env_menu=env_menu) if menus else {}))
     phase = (np.arange(N) % 31).astype(np.int32)
-    obs = env.reset()
+    env.reset()
     env.set_state(step_num=phase)
     gen = torch.Generator(device='cuda').manual_seed(21)
     acts = torch.randint(0, 6, (T, N), device='cuda', dtype=torch.uint8, generator=gen)
-    rec_r = torch.empty((T, N), dtype=torch.int32, device='cuda')
-    rec_d = torch.empty((T, N), dtype=torch.bool, device='cuda')
-    for t in range(T):
-        obs, r, d, _ = env.step(acts[t])
-        rec_r[t] = r
-        rec_d[t] = d
-    torch.cuda.synchronize()
-    a_host, r_host, d_host = acts.cpu().numpy().astype(np.int8), rec_r.cpu().numpy(), rec_d.cpu().numpy()
-    st = env.get_state()
-    k2, p2 = env.get_rng_states()
-    threads = max(1, len(os.sched_getaffinity(0)))
-    finished = 0
-    ra, rb = np.random.RandomState(), np.random.RandomState()
-    for lo in range(0, N, SL):
-        hi = lo + SL
-        ora = OracleBatch(SL, rng_states=[(keys[i], int(pos[i])) for i in range(lo, hi)],
-                          per_env_kwargs=[_MENUS8[int(m)] for m in env_menu[lo:hi]] if menus else None, **kw)
-        ora.reset()
-        for j, e in enumerate(ora.envs):                     # the same phase spread (step_num only)
-            v = e.view()
-            e._lib.cwo_set_state(e._h, v.grid, v.init_grid, v.agent_r, v.agent_c, v.hold, v.achieved, v.desired, int(phase[lo + j]))
-        total, o_rew, o_done = ora.rollout(a_host[:, lo:hi], nthreads=threads, record=True)
-        assert total == SL * T
-        assert np.array_equal(r_host[:, lo:hi], o_rew), ('reward', lo)
-        assert np.array_equal(d_host[:, lo:hi], o_done.astype(bool)), ('done', lo)
-        finished += int(o_done.sum())
-        f_obs, f_goal, f_init = (obs[k][lo:hi].cpu().numpy() for k in ('observation', 'desired_goal', 'init_observation'))
-        ish = ora.envs[0].img_shape
-        for j, e in enumerate(ora.envs):
-            v, i = e.view(), lo + j
-            assert np.array_equal(f_obs[j], np.ctypeslib.as_array(v.obs, shape=ish)), ('observation', i)
-            assert np.array_equal(f_goal[j], np.ctypeslib.as_array(v.desired_img, shape=ish)), ('desired_goal', i)
-            assert np.array_equal(f_init[j], np.ctypeslib.as_array(v.init_img, shape=ish)), ('init_observation', i)
-            assert (st['agent_rc'][i][0], st['agent_rc'][i][1], st['hold'][i], st['achieved'][i], st['desired'][i], st['step_num'][i]) == \
-                (v.agent_r, v.agent_c, v.hold, v.achieved, v.desired, v.step_num), ('state', i)
-            assert np.array_equal(st['grid'][i].reshape(-1), np.ctypeslib.as_array(v.grid, shape=(size * size,))), ('grid', i)
-            ok, op = e.get_rng()                             # (the same point of the same stream: numpy holds 624 where the engine holds 0 -- compare what comes next)
-            assert op % 624 == int(p2[i]) % 624, ('rng position', i)
-            if j % 8 == 0:
-                ra.set_state(('MT19937', ok, op, 0, 0.0))
-                rb.set_state(('MT19937', k2[i], int(p2[i]), 0, 0.0))
-                assert np.array_equal(ra.randint(0, 2**32, 4, dtype=np.uint32), rb.randint(0, 2**32, 4, dtype=np.uint32)), ('rng stream', i)
-        del ora
-    assert finished == int(env.counters[1].item()) and finished >= N
+    r_host, d_host = record_steps(env, acts)
+    res = replay_against_oracle(env, keys, pos, oracle_kw(kw, raster), acts.cpu().numpy(), r_host, d_host, phase=phase, frames=True,
+                                per_env_kwargs=[_MENUS8[int(m)] for m in env_menu] if menus else None)
+    assert res['finished'] == int(env.counters[1].item()) and res['finished'] >= N
     env.close()
 
 
@@ -122,53 +72,15 @@ def test_every_env_of_a_batch_whose_episodes_end_early_against_the_oracle(obs_mo
     random walker -- episodes of ~140 steps under max_steps = 300, ~480 envs finishing on every step, many of them two, three, four times between two
     look-ahead refills (the ring of records runs down, the refill period adapts, a few are reset the slow way).  Every reward and done of 450 steps, and at
     the end every env's state, frames, episode counters and RNG state (key and position, exactly), against the oracle."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
-    from oracle import OracleBatch
-    N, T, SL, size = 65536, 450, 8192, 8
-    kw = dict(size=(size, size), max_steps=300, reward_style='subset', selected_tasks=['EatBread'], number_of_tasks=1)
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, seed=123, **kw)
-    keys, pos = env.get_rng_states()
-    obs = env.reset()
+    N, T = 65536, 450
+    kw = dict(size=(8, 8), max_steps=300, reward_style='subset', selected_tasks=['EatBread'], number_of_tasks=1)
+    env, keys, pos = make_env(N, obs_mode=obs_mode, seed=123, **kw)
+    env.reset()
     acts = torch.randint(0, 4, (T, N), device='cuda', dtype=torch.uint8, generator=torch.Generator(device='cuda').manual_seed(9))
-    rec_r = torch.empty((T, N), dtype=torch.int32, device='cuda')
-    rec_d = torch.empty((T, N), dtype=torch.bool, device='cuda')
-    for t in range(T):
-        obs, r, d, _ = env.step(acts[t])
-        rec_r[t] = r
-        rec_d[t] = d
-    torch.cuda.synchronize()
-    a_host, r_host, d_host = acts.cpu().numpy().astype(np.int8), rec_r.cpu().numpy(), rec_d.cpu().numpy()
-    st = env.get_state()
-    k2, p2 = env.get_rng_states()
-    threads = max(1, len(os.sched_getaffinity(0)))
-    finished, most = 0, 0
-    for lo in range(0, N, SL):
-        hi = lo + SL
-        ora = OracleBatch(SL, rng_states=[(keys[i], int(pos[i])) for i in range(lo, hi)], **kw)
-        ora.reset()
-        total, o_rew, o_done = ora.rollout(a_host[:, lo:hi], nthreads=threads, record=True)
-        assert total == SL * T
-        assert np.array_equal(r_host[:, lo:hi], o_rew), ('reward', lo)
-        assert np.array_equal(d_host[:, lo:hi], o_done.astype(bool)), ('done', lo)
-        finished += int(o_done.sum())
-        per_env = o_done.sum(axis=0)
-        most = max(most, int(np.add.reduceat(o_done[:448], np.arange(0, 448, 64), axis=0).max()))      # most finishes of one env inside 64 consecutive steps
-        if obs_mode != 'state':
-            f_obs, f_goal, f_init = (obs[k][lo:hi].cpu().numpy() for k in ('observation', 'desired_goal', 'init_observation'))
-        ish = ora.envs[0].img_shape
-        for j, e in enumerate(ora.envs):
-            v, i = e.view(), lo + j
-            if obs_mode != 'state':
-                assert np.array_equal(f_obs[j], np.ctypeslib.as_array(v.obs, shape=ish)), ('observation', i)
-                assert np.array_equal(f_goal[j], np.ctypeslib.as_array(v.desired_img, shape=ish)), ('desired_goal', i)
-                assert np.array_equal(f_init[j], np.ctypeslib.as_array(v.init_img, shape=ish)), ('init_observation', i)
-            assert (st['agent_rc'][i][0], st['agent_rc'][i][1], st['hold'][i], st['achieved'][i], st['desired'][i], st['step_num'][i], st['ep_no'][i]) == \
-                (v.agent_r, v.agent_c, v.hold, v.achieved, v.desired, v.step_num, v.ep_no), ('state', i)
-            assert np.array_equal(st['grid'][i].reshape(-1), np.ctypeslib.as_array(v.grid, shape=(size * size,))), ('grid', i)
-            ok, op = e.get_rng()
-            assert op == int(p2[i]) and np.array_equal(ok, k2[i]), ('rng state', i, int(per_env[j]))
-        del ora
-    c = env._counters_raw.cpu()
+    r_host, d_host = record_steps(env, acts)
+    finished = replay_against_oracle(env, keys, pos, kw, acts.cpu().numpy(), r_host, d_host, frames=obs_mode != 'state')['finished']
+    most = int(np.add.reduceat(d_host[:448].astype(np.int32), np.arange(0, 448, 64), axis=0).max())    # most finishes of one env inside 64 consecutive steps (the
+    c = env._counters_raw.cpu()                                                                        # engine's dones: the oracle's, as just found)
     assert finished == int(c[1]) and 0.8 * finished < int(c[2]) <= finished and finished > 2 * N      # (mostly successes -- the rest walked 300 steps --; each env finished ~3 times)
     assert most >= 5                                                         # (some env ran its ring of four records empty between two refills ...)
     assert 0 < int(c[5]) < finished // 100                                   # (... and was reset the slow way: rare, and it changes nothing)
@@ -179,16 +91,9 @@ def test_every_env_of_a_batch_whose_episodes_end_early_against_the_oracle(obs_mo
 @pytest.mark.parametrize('obs_mode', ['pixels', 'pixels_dirty'])
 @pytest.mark.parametrize('name', fixture_names())
 def test_golden_fixture_replay(name, obs_mode):
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     meta, kw, g = load(name)
-    env = CraftingWorldVecEnv(1, obs_mode=obs_mode, seed=0, raster='alt' if meta['env'] == 'CraftingWorldEnvAltObs' else 'ray', **kw)
-    env.set_rng_states(g['key0'][None], np.array([g['pos0']]))
-    if kw.get('fixed_init_state'):
-        # the pool is drawn from the env RNG at construction (ray.py:116-118): redo it on the injected stream
-        import ctypes as C
-        from gym_craftingworld_amd import _lib as L
-        L.check(env._lib.cw_generate_fixed_states(env._h, env._stream()), 'pool')
-    size = kw['size'][0]
+    env, _, _ = make_env(1, g['key0'][None], np.array([g['pos0']]), obs_mode=obs_mode, seed=0,
+                         raster='alt' if meta['env'] == 'CraftingWorldEnvAltObs' else 'ray', **kw)
     ri = 0
     # fixtures captured from CraftingWorldEnvOneHot hold what THAT class returns: (S,S,12) one-hot states
     # (carftingworld_onehot.py:203,310,369-371) -- the engine's one-hot views of the current / goal / reset states
@@ -267,16 +172,9 @@ CASES = [
 @pytest.mark.parametrize('obs_mode', ['pixels', 'pixels_dirty', 'state'])
 @pytest.mark.parametrize('case', CASES, ids=lambda c: 'N%d_S%d' % (c['N'], c['kw']['size'][0]))
 def test_random_batch_vs_oracle(case, obs_mode):
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T, kw = case['N'], case['T'], case['kw']
-    keys, pos = _np_states(N, 31000)
-    # fixed_init_state pools are drawn from the env stream (ray.py:116-118): inject the stream, then redraw the pool
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, **kw)
-    env.set_rng_states(keys, pos)
-    if kw.get('fixed_init_state'):
-        from gym_craftingworld_amd import _lib as L
-        L.check(env._lib.cw_generate_fixed_states(env._h, env._stream()), 'pool')
+    env, keys, pos = make_env(N, *np_states(N, 31000), obs_mode=obs_mode, **kw)
     ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **kw)
     env.reset()
     ora.reset()
@@ -286,15 +184,7 @@ def test_random_batch_vs_oracle(case, obs_mode):
     ret, length = np.zeros(N, np.int64), np.zeros(N, np.int64)         # the oracle's running episode return / length (ray.py:361-367 summed by the loop)
     for t in range(T):
         obs, rew, done, info = env.step(dacts[t])
-        # terminal masks must be read before the oracle resets
-        o_rew = np.empty(N, np.int32)
-        o_done = np.zeros(N, bool)
-        o_ach = np.empty(N, np.int64)
-        for i, e in enumerate(ora.envs):
-            _, o_rew[i], o_done[i], _ = e.step(int(acts[t, i]))
-            o_ach[i] = e.view().achieved
-            if o_done[i]:
-                e.reset()
+        o_rew, o_done, o_ach, _ = ora.step(acts[t], details=True)      # (the terminal masks: read before the oracle resets)
         assert np.array_equal(rew.cpu().numpy(), o_rew), ('reward', t)
         assert np.array_equal(done.cpu().numpy(), o_done), ('done', t)
         assert np.array_equal(info['achieved_goal'].cpu().numpy().astype(np.int64) & 0xFFFF, o_ach), ('achieved', t)
@@ -307,55 +197,16 @@ def test_random_batch_vs_oracle(case, obs_mode):
             ret[o_done] = 0
             length[o_done] = 0
         n_done += int(o_done.sum())
-        if t % 37 == 0 or t == T - 1:
-            _compare_full(env, ora, obs_mode, t)
+        if t % 37 == 0 or t == T - 1:                    # state, render() / grid() / one_hot(), the frames step() returned, the RNG states
+            same_states(env, ora, frames=VIEWS + (tuple(FRAMES) if obs_mode != 'state' else ()), tag='step %d: ' % t)
     assert n_done > 0
     assert int(env.counters[1].item()) == n_done
     assert int(env.counters[0].item()) == N * T
-    # RNG streams continue identically
-    k2, p2 = env.get_rng_states()
-    for i in (0, N // 2, N - 1):
-        rs = np.random.RandomState()
-        rs.set_state(('MT19937', k2[i], int(p2[i]), 0, 0.0))
-        ok, op = ora.envs[i].get_rng()
-        ro = np.random.RandomState()
-        ro.set_state(('MT19937', ok, op, 0, 0.0))
-        assert np.array_equal(rs.randint(0, 2**32, 700, dtype=np.uint32), ro.randint(0, 2**32, 700, dtype=np.uint32))
     env.close()
-
-
-def _compare_full(env, ora, obs_mode, t):
-    st = env.get_state()
-    grid_dev = env.grid().cpu().numpy()
-    oh = env.one_hot().cpu().numpy()
-    frames = env.render().cpu().numpy()
-    if obs_mode != 'state':
-        o = env._observation()
-        obs, des, ini = (o[k].cpu().numpy() for k in ('observation', 'desired_goal', 'init_observation'))
-    for i, s in enumerate(ora.states()):
-        tag = ('env', i, 'step', t)
-        assert np.array_equal(st['grid'][i], s['grid']), tag
-        assert np.array_equal(grid_dev[i], s['grid']), tag
-        assert np.array_equal(st['init_grid'][i], s['init_grid']), tag
-        assert np.array_equal(st['goal_grid'][i], s['goal_grid']), tag
-        assert tuple(st['agent_rc'][i]) == s['agent'] and tuple(st['goal_agent_rc'][i]) == s['goal_agent'], tag
-        assert st['hold'][i] == s['hold'] and st['achieved'][i] == s['achieved'] and st['desired'][i] == s['desired'], tag
-        assert st['step_num'][i] == s['step_num'] and st['ep_no'][i] == s['ep_no'], tag
-        assert np.array_equal(frames[i], s['obs']), tag
-        # one-hot view: channels 0-7 objects, 8 agent, 9-11 hold (ray.py:94-98)
-        g = s['grid']
-        assert np.array_equal(oh[i, :, :, :8].argmax(-1) * oh[i, :, :, :8].any(-1) + oh[i, :, :, :8].any(-1), np.where(g > 0, g, 0)), tag
-        assert oh[i, s['agent'][0], s['agent'][1], 8] == 1 and oh[i, :, :, 8].sum() == 1, tag
-        assert oh[i, :, :, 9:].sum() == (1 if s['hold'] else 0), tag
-        if obs_mode != 'state':
-            assert np.array_equal(obs[i], s['obs']), tag
-            assert np.array_equal(des[i], s['desired_img']), tag
-            assert np.array_equal(ini[i], s['init_img']), tag
 
 
 def test_mixed_task_menus_vs_oracle():
     """BASELINE config 4 shape: env i uses menu[i % M] (ordered selected_tasks lists)."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     menus = [dict(selected_tasks=TASKS), dict(selected_tasks=['MoveSticks', 'MakeBread'], stacking=False),
              dict(selected_tasks=['ChopRock', 'ChopTree', 'BuildHouse', 'GoToHouse'], number_of_tasks=3, reward_style='subset'),
@@ -363,9 +214,7 @@ def test_mixed_task_menus_vs_oracle():
     N, T = 128, 160
     env_menu = np.arange(N) % len(menus)
     kw = dict(size=(6, 6), max_steps=25)
-    keys, pos = _np_states(N, 777)
-    env = CraftingWorldVecEnv(N, obs_mode='pixels_dirty', task_menus=menus, env_menu=env_menu, **kw)
-    env.set_rng_states(keys, pos)
+    env, keys, pos = make_env(N, *np_states(N, 777), obs_mode='pixels_dirty', task_menus=menus, env_menu=env_menu, **kw)
     ora = OracleBatch(N, rng_states=list(zip(keys, pos)), per_env_kwargs=[menus[m] for m in env_menu], **kw)
     env.reset()
     ora.reset()
@@ -375,7 +224,7 @@ def test_mixed_task_menus_vs_oracle():
         obs, rew, done, _ = env.step(dacts[t])
         o_rew, o_done = ora.step(acts[t])
         assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), t
-    _compare_full(env, ora, 'pixels_dirty', T)
+    same_states(env, ora, frames=VIEWS + tuple(FRAMES))
     env.close()
 
 
@@ -461,7 +310,7 @@ def test_shard_equivalence_and_batch_position_invariance():
     """GPU g of G owns envs [g*N/G,(g+1)*N/G): running the shards separately equals the single batch."""
     from gym_craftingworld_amd import CraftingWorldVecEnv
     N, T, kw = 512, 80, dict(size=(8, 8), max_steps=30)
-    keys, pos = _np_states(N, 4000)
+    keys, pos = np_states(N, 4000)
     acts = torch.as_tensor(np.random.RandomState(3).randint(0, 6, size=(T, N)).astype(np.int32), device='cuda')
 
     def run(lo, hi):
@@ -499,10 +348,9 @@ def test_full_size_properties_65536(size, max_steps, monkeypatch):
     N, T = 65536, 45
     kw = dict(size=(size, size), max_steps=max_steps)
     monkeypatch.setenv('CW_TUNE_RENDER_CHUNK_ROUNDS', '150' if size == 21 else '350')
-    full = CraftingWorldVecEnv(N, obs_mode='pixels', seed=123, **kw)
+    full, keys, pos = make_env(N, obs_mode='pixels', seed=123, **kw)
     monkeypatch.delenv('CW_TUNE_RENDER_CHUNK_ROUNDS')
     dirty = CraftingWorldVecEnv(N, obs_mode='pixels_dirty', seed=123, **kw)
-    keys, pos = full.get_rng_states()
     idx = sorted(set(list(range(64)) + [24574, 24575, 24576, 24577, 49150, 49151, 49152, 49153] + list(range(1000, N, 4099))[:48] + list(range(N - 32, N))))
     idx_t = torch.as_tensor(idx, device='cuda')
     ora = OracleBatch(len(idx), rng_states=[(keys[i], int(pos[i])) for i in idx], **kw)
@@ -524,9 +372,7 @@ def test_full_size_properties_65536(size, max_steps, monkeypatch):
             assert torch.equal(of['desired_goal'], od['desired_goal']), t
             assert torch.equal(of['init_observation'], od['init_observation']), t
             assert torch.equal(full.render(), of['observation']), t
-    obs, des, ini = (of[k][idx_t].cpu().numpy() for k in ('observation', 'desired_goal', 'init_observation'))
-    for j_, s in enumerate(ora.states()):
-        assert np.array_equal(obs[j_], s['obs']) and np.array_equal(des[j_], s['desired_img']) and np.array_equal(ini[j_], s['init_img']), idx[j_]
+    same_states(full, ora, idx, frames=tuple(FRAMES))
     assert torch.equal(full.hdr, dirty.hdr) and torch.equal(full.slot_pos, dirty.slot_pos)
     assert int(full.counters[1].item()) == dones and int(full.counters[0].item()) == N * T
     if max_steps <= T:
@@ -541,7 +387,7 @@ def test_single_env_facade_matches_golden():
     import gym_craftingworld_amd as g
     env = g.make('craftingworld-v3')
     env.np_random = np.random.RandomState(12345)              # exactly what SURVEY 8c's reference session did
-    assert env.np_random.get_state()[2] % 624 == 0            # (reading gives a snapshot of the device-resident stream)
+    assert env.np_random.get_state()[2] in (0, 624)           # (reading gives a snapshot of the device-resident stream: at the start of a block)
     obs = env.reset()
     assert env.np_random.get_state()[2] == 617                # "MT pos after reset 617"
     assert obs['achieved_goal'] is obs['observation']
@@ -578,7 +424,7 @@ def test_step_captured_in_hip_graph(obs_mode):
     with it -- cw_step sees the capture -- so the replayed env refills on every step where the eager one does on every max_steps/4-th (8 ... 64): same results.)"""
     from gym_craftingworld_amd import CraftingWorldVecEnv
     N, T, kw = 2048, 90, dict(size=(7, 7), max_steps=25)
-    keys, pos = _np_states(N, 99)
+    keys, pos = np_states(N, 99)
     envs = []
     for _ in range(2):
         e = CraftingWorldVecEnv(N, obs_mode=obs_mode, **kw)
@@ -658,12 +504,9 @@ def test_step_many_and_captured_graphs_equal_stepping(obs_mode, K):
 def test_terminal_observation_vs_oracle(obs_mode):
     """keep_terminal_obs: where done, info['terminal_observation'] is the oracle's frame BEFORE its
     reset, and obs is the first frame of the next episode (gym.vector auto-reset semantics)."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T, kw = 160, 70, dict(size=(5, 5), max_steps=12)
-    keys, pos = _np_states(N, 555)
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, keep_terminal_obs=True, **kw)
-    env.set_rng_states(keys, pos)
+    env, keys, pos = make_env(N, *np_states(N, 555), obs_mode=obs_mode, keep_terminal_obs=True, **kw)
     ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **kw)
     env.reset()
     ora.reset()
@@ -672,18 +515,13 @@ def test_terminal_observation_vs_oracle(obs_mode):
     seen = 0
     for t in range(T):
         obs, rew, done, info = env.step(dacts[t])
-        term = info['terminal_observation'].cpu().numpy()
-        cur = obs['observation'].cpu().numpy()
-        d = done.cpu().numpy()
-        for i, e in enumerate(ora.envs):
-            o, r, dd, _ = e.step(int(acts[t, i]))
-            assert dd == d[i]
-            if dd:
-                assert np.array_equal(term[i], o['observation']), (t, i)
-                e.reset()
-                seen += 1
-            assert np.array_equal(cur[i], e.state()['obs']), (t, i)
+        o_rew, o_done, _, o_term = ora.step(acts[t], details=True)
+        assert np.array_equal(done.cpu().numpy(), o_done), t
+        same_terminal(info['terminal_observation'], o_term, tag='step %d: ' % t)
+        same_states(env, ora, frames=('observation',), rng=False, tag='step %d: ' % t)      # (obs: the first frame of the next episode where done)
+        seen += len(o_term)
     assert seen > N
+    same_states(env, ora, frames=tuple(FRAMES))
     env.close()
 
 
@@ -694,7 +532,7 @@ def test_multi_device_facade_and_gymnasium_adapter(obs_mode):
     from gym_craftingworld_amd import CraftingWorldVecEnv
     from gym_craftingworld_amd.adapters import GymnasiumVecAdapter, MultiDeviceVecEnv
     N, T, kw = 300, 60, dict(size=(5, 5), max_steps=15, obs_mode=obs_mode)
-    keys, pos = _np_states(N, 2222)
+    keys, pos = np_states(N, 2222)
     acts = torch.as_tensor(np.random.RandomState(1).randint(0, 6, size=(T, N)).astype(np.int32), device='cuda')
     single = CraftingWorldVecEnv(N, **kw)
     single.set_rng_states(keys, pos)
@@ -733,19 +571,11 @@ def test_multi_device_facade_and_gymnasium_adapter(obs_mode):
 def test_persistent_rollout_equals_stepping(case):
     """cw_rollout (T steps in one persistent kernel) == T x cw_step: rewards and dones of every step,
     final state, goal state, RNG streams and counters; and both equal the oracle on the first envs."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
-    from gym_craftingworld_amd import _lib as L
-    from oracle import OracleBatch
     N, T, kw = case['N'], case['T'], case['kw']
-    keys, pos = _np_states(N, 8080)
-    envs = []
-    for _ in range(2):
-        e = CraftingWorldVecEnv(N, obs_mode='state', **kw)
-        e.set_rng_states(keys, pos)
-        if kw.get('fixed_init_state'):
-            L.check(e._lib.cw_generate_fixed_states(e._h, e._stream()), 'pool')
+    keys, pos = np_states(N, 8080)
+    envs = [make_env(N, keys, pos, obs_mode='state', **kw)[0] for _ in range(2)]
+    for e in envs:
         e.reset()
-        envs.append(e)
     stepped, rolled = envs
     acts = torch.randint(0, 6, (T, N), device='cuda', dtype=torch.uint8, generator=torch.Generator(device='cuda').manual_seed(21))
     rew, don = rolled.rollout(acts)
@@ -764,11 +594,8 @@ def test_persistent_rollout_equals_stepping(case):
     ka, pa = stepped.get_rng_states()
     kb, pb = rolled.get_rng_states()
     assert np.array_equal(pa, pb) and np.array_equal(ka[:, 1:], kb[:, 1:])
-    M = min(N, 96)
-    ora = OracleBatch(M, rng_states=[(keys[i], int(pos[i])) for i in range(M)], **kw)
-    ora.reset()
-    _, o_rew, o_don = ora.rollout(acts[:, :M].cpu().numpy().astype(np.int8), nthreads=4, record=True)
-    assert np.array_equal(rew[:, :M].cpu().numpy(), o_rew) and np.array_equal(don[:, :M].cpu().numpy(), o_don.astype(bool))
+    replay_against_oracle(rolled, keys, pos, kw, acts.cpu().numpy(), rew.cpu().numpy(), don.cpu().numpy(), pools=bool(kw.get('fixed_init_state')),
+                          idx=np.arange(min(N, 96)))
     for e in envs:
         e.close()
 
@@ -777,14 +604,12 @@ def test_persistent_rollout_equals_stepping(case):
 def test_reset_soak_vs_oracle(size, n_envs):
     """Reset-heavy soak: max_steps=2 forces a reset of every env every other step, so the
     lane-parallel rejection sampling, the token bookkeeping and imagine_obs are compared with the
-    oracle on >100 000 independent MT19937 streams/resets (placement, desired mask, goal state, agent,
-    final stream position)."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
+    oracle on >100 000 independent MT19937 streams/resets (every field of the state, the goal state and
+    the reset state, and the final RNG state: key and position, exactly)."""
     from oracle import OracleBatch
     T = 16
     kw = dict(size=(size, size), max_steps=2)
-    env = CraftingWorldVecEnv(n_envs, obs_mode='state', seed=77, **kw)
-    keys, pos = env.get_rng_states()
+    env, keys, pos = make_env(n_envs, obs_mode='state', seed=77, **kw)
     ora = OracleBatch(n_envs, rng_states=[(keys[i], int(pos[i])) for i in range(n_envs)], **kw)
     env.reset()
     ora.reset()
@@ -792,19 +617,7 @@ def test_reset_soak_vs_oracle(size, n_envs):
     env.rollout(torch.as_tensor(acts.astype(np.uint8), device=env.device), record=False)   # persistent kernel: same reset code
     total = ora.rollout(acts, nthreads=8)
     assert total == T * n_envs
-    st = env.get_state()
-    k2, p2 = env.get_rng_states()
-    for i, s in enumerate(ora.states()):
-        assert np.array_equal(st['grid'][i], s['grid']), i
-        assert np.array_equal(st['init_grid'][i], s['init_grid']), i
-        assert np.array_equal(st['goal_grid'][i], s['goal_grid']), i
-        assert tuple(st['agent_rc'][i]) == s['agent'] and tuple(st['goal_agent_rc'][i]) == s['goal_agent'], i
-        assert st['desired'][i] == s['desired'] and st['ep_no'][i] == s['ep_no'], i
-    for i in range(0, n_envs, 97):
-        ok, op = ora.envs[i].get_rng()
-        assert p2[i] % 624 == op % 624, i
-        if op % 624:
-            assert np.array_equal(k2[i][1:], ok[1:]), i
+    same_states(env, ora)
     assert int(env.counters[1].item()) == n_envs * (T // 2)
     env.close()
 
@@ -812,7 +625,6 @@ def test_reset_soak_vs_oracle(size, n_envs):
 def test_config4_shard_shape_mixed_menus_131072():
     """BASELINE configs[3] as one rank sees it: 131 072 envs per GPU (1M over 8), env i using ordered
     task menu i mod 8, full-frame pixels.  A strided sample of envs is replayed by the oracle."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T = 131072, 24
     menus = [dict(selected_tasks=TASKS), dict(selected_tasks=TASKS[:3]), dict(selected_tasks=TASKS[3:], number_of_tasks=2),
@@ -821,8 +633,7 @@ def test_config4_shard_shape_mixed_menus_131072():
              dict(selected_tasks=['EatBread', 'MakeBread'], number_of_tasks=1), dict(selected_tasks=TASKS[1::2])]
     env_menu = (np.arange(N) % len(menus)).astype(np.uint8)
     kw = dict(size=(21, 21), max_steps=10)
-    env = CraftingWorldVecEnv(N, obs_mode='pixels', seed=4242, task_menus=menus, env_menu=env_menu, **kw)
-    keys, pos = env.get_rng_states()
+    env, keys, pos = make_env(N, obs_mode='pixels', seed=4242, task_menus=menus, env_menu=env_menu, **kw)
     sample = np.unique(np.concatenate([np.arange(0, N, 1021)[:120], np.arange(N - 8, N)]))      # (a stride through the batch and the last envs: the array's last piece)
     ora = OracleBatch(len(sample), rng_states=[(keys[i], int(pos[i])) for i in sample],
                       per_env_kwargs=[menus[env_menu[i]] for i in sample], **kw)
@@ -835,13 +646,7 @@ def test_config4_shard_shape_mixed_menus_131072():
         obs, rew, done, _ = env.step(a)
         o_rew, o_done = ora.step(a[sidx].cpu().numpy())
         assert np.array_equal(rew[sidx].cpu().numpy(), o_rew) and np.array_equal(done[sidx].cpu().numpy(), o_done), t
-    frames = obs['observation'][sidx].cpu().numpy()
-    goals = obs['desired_goal'][sidx].cpu().numpy()
-    for j, s in enumerate(ora.states()):
-        assert np.array_equal(frames[j], s['obs']) and np.array_equal(goals[j], s['desired_img']), sample[j]
-    inits = obs['init_observation'][sidx].cpu().numpy()
-    for j, s in enumerate(ora.states()):
-        assert np.array_equal(inits[j], s['init_img']), sample[j]
+    same_states(env, ora, sample, frames=tuple(FRAMES))
     assert int(env.counters[0].item()) == N * T and int(env.counters[1].item()) >= 2 * N
     env.close()
 
@@ -852,13 +657,10 @@ def test_altobs_raster_vs_oracle(obs_mode, S, N):
     vs the oracle: all three frames, cw_render, terminal frames; includes sticks held over sticks (2 x colour).
     (All sizes go through the sweep of aligned 4-KiB pieces: a piece of the 6x6 array overlaps up to five 1 134-byte frames, of the 13x13 and
     21x21 arrays two; the arrays end in a partial piece.)"""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     T, kw = 90, dict(size=(S, S), max_steps=30)
-    keys, pos = _np_states(N, 6060)
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, raster='alt', keep_terminal_obs=True, **kw)
-    env.set_rng_states(keys, pos)
-    ora = OracleBatch(N, rng_states=list(zip(keys, pos)), alt_obs=True, **kw)
+    env, keys, pos = make_env(N, *np_states(N, 6060), obs_mode=obs_mode, raster='alt', keep_terminal_obs=True, **kw)
+    ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **oracle_kw(kw, 'alt'))
     obs = env.reset()
     ora.reset()
     assert tuple(obs['observation'].shape) == (N, 3 * S + 3, 3 * S, 3)
@@ -867,21 +669,13 @@ def test_altobs_raster_vs_oracle(obs_mode, S, N):
     dacts = torch.as_tensor(acts, device=env.device)
     for t in range(T):
         obs, rew, done, info = env.step(dacts[t])
-        term = info['terminal_observation'].cpu().numpy() if (t % 9 == 0) else None
-        d = done.cpu().numpy()
-        for i, e in enumerate(ora.envs):
-            o, r, dd, _ = e.step(int(acts[t, i]))
-            assert dd == d[i] and r == int(rew[i].item()) if t % 9 == 0 else dd == d[i]
-            if dd:
-                if term is not None:
-                    assert np.array_equal(term[i], o['observation']), (t, i)
-                e.reset()
+        o_rew, o_done, _, o_term = ora.step(acts[t], details=True)
+        assert np.array_equal(done.cpu().numpy(), o_done), t
+        if t % 9 == 0:
+            assert np.array_equal(rew.cpu().numpy(), o_rew), t
+            same_terminal(info['terminal_observation'], o_term, tag='step %d: ' % t)
         if t % 9 == 0 or t == T - 1:
-            cur, des, ini, ren = (x.cpu().numpy() for x in (obs['observation'], obs['desired_goal'], obs['init_observation'], env.render()))
-            for i, s in enumerate(ora.states()):
-                assert np.array_equal(cur[i], s['obs']), (t, i)
-                assert np.array_equal(ren[i], s['obs']), (t, i)
-                assert np.array_equal(des[i], s['desired_img']) and np.array_equal(ini[i], s['init_img']), (t, i)
+            same_states(env, ora, frames=tuple(FRAMES) + ('render',), rng=t == T - 1, tag='step %d: ' % t)
     # the double-count corner: sticks in hand, standing on sticks -> blue channel 2*160 mod 256 = 64
     grid = np.zeros((N, S, S), np.uint8)
     grid[:, 2, 3] = 1
@@ -932,25 +726,23 @@ def test_compute_reward_batch_matches_reference_rules():
 
 
 def test_overlap_stress_desynchronised_resets():
-    """The full-pixel step forks: main stream paints non-done envs while the side stream resets done
-    envs and paints their three frames.  Short, de-synchronised episodes (max_steps=23, random phases
-    from successes) keep both streams busy on every step; full-frame and dirty-cell engines must stay
-    identical throughout, and the first envs equal to the oracle."""
+    """Short, de-synchronised episodes (max_steps=23, the phases spread out from the start, successes shifting them further): envs finish on
+    every one of 700 steps, so every full-frame step has frames of running envs to sweep and frames of freshly reset envs to paint (the step
+    kernel's look-ahead records, the done list's kernel).  The full-frame and the dirty-cell engine must stay identical throughout (outputs, the
+    three frames and the terminal frames at every 50th step; state and counters at the end), and the first 96 envs equal to the oracle: reward
+    and done of every step, and at the end state, the three frames and the RNG states."""
     from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T, M = 32768, 700, 96
     kw = dict(size=(21, 21), max_steps=23)
-    full = CraftingWorldVecEnv(N, obs_mode='pixels', seed=31, keep_terminal_obs=True, **kw)
+    full, keys, pos = make_env(N, obs_mode='pixels', seed=31, keep_terminal_obs=True, **kw)
     dirty = CraftingWorldVecEnv(N, obs_mode='pixels_dirty', seed=31, keep_terminal_obs=True, **kw)
-    keys, pos = full.get_rng_states()
     # scatter the episode phases so that some envs finish on every step
     phase = (np.arange(N) * 7 % 23).astype(np.int32)
     ora = OracleBatch(M, rng_states=[(keys[i], int(pos[i])) for i in range(M)], **kw)
     full.reset(); dirty.reset(); ora.reset()
     full.set_state(step_num=phase); dirty.set_state(step_num=phase)
-    for i, e in enumerate(ora.envs):
-        s = e.state()
-        e.set_state(s['grid'], s['init_grid'], s['agent'], s['hold'], s['achieved'], s['desired'], int(phase[i]))
+    set_phase(ora, phase[:M])
     gen = torch.Generator(device='cuda').manual_seed(5)
     for t in range(T):
         a = torch.randint(0, 6, (N,), device='cuda', dtype=torch.uint8, generator=gen)
@@ -965,9 +757,7 @@ def test_overlap_stress_desynchronised_resets():
             assert torch.equal(inf_f['terminal_observation'][m], inf_d['terminal_observation'][m]), t
         o_rew, o_done = ora.step(a[:M].cpu().numpy())
         assert np.array_equal(rf[:M].cpu().numpy(), o_rew) and np.array_equal(df[:M].cpu().numpy(), o_done), t
-    for i, s in enumerate(ora.states()):
-        assert np.array_equal(of['observation'][i].cpu().numpy(), s['obs']), i
-        assert np.array_equal(of['desired_goal'][i].cpu().numpy(), s['desired_img']), i
+    same_states(full, ora, np.arange(M), frames=tuple(FRAMES))
     assert torch.equal(full.hdr, dirty.hdr) and torch.equal(full.counters, dirty.counters)
     full.close(); dirty.close()
 
@@ -1413,26 +1203,19 @@ def test_episode_statistics_of_envs_stepped_past_done_without_auto_reset(obs_mod
     """An engine WITHOUT auto-reset keeps stepping a finished env until reset(), as the reference does (ray.py:367): a goal that stays satisfied pays
     MAX_STEPS again on every step that changes the state, time-outs stay done.  info['episode'] = {'r', 'l'} at every done step must be the SUM of
     the rewards the oracle returned since the reset, and the step count -- not the closed form of an episode that stopped at its first done."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
-    from oracle import OracleEnv
+    from oracle import OracleBatch
     N, T, kw = 384, 70, dict(size=(5, 5), max_steps=14, reward_style=reward_style, selected_tasks=['MoveAxe', 'MoveSticks', 'GoToHouse', 'EatBread'], number_of_tasks=1)
-    keys, pos = _np_states(N, 31000)
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, auto_reset=False, **kw)
-    env.set_rng_states(keys, pos)
+    env, keys, pos = make_env(N, *np_states(N, 31000), obs_mode=obs_mode, auto_reset=False, **kw)
     env.reset()
-    oras = [OracleEnv(rng_state=(keys[i], int(pos[i])), **kw) for i in range(N)]
-    for o in oras:
-        o.reset()
+    ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **kw)
+    ora.reset()
     acts = np.random.RandomState(5).randint(0, 6, size=(T, N))
     ret = np.zeros(N, np.int64)
     repeated = checked = 0
     n_succ = np.zeros(N, np.int64)
     for t in range(T):
         _, rew, done, info = env.step(torch.as_tensor(acts[t], device=env.device))
-        o_r = np.empty(N, np.int64)
-        o_d = np.empty(N, bool)
-        for i, o in enumerate(oras):
-            _, o_r[i], o_d[i], _ = o.step(int(acts[t, i]))
+        o_r, o_d = ora.step(acts[t], auto_reset=False)      # (finished envs are stepped on, as the engine's are)
         ret += o_r
         n_succ += o_r == kw['max_steps']
         assert np.array_equal(rew.cpu().numpy(), o_r) and np.array_equal(done.cpu().numpy(), o_d), t
@@ -1479,12 +1262,10 @@ def test_long_reset_chains_on_one_stream_vs_oracle():
     """3 000 consecutive episodes on each of 256 MT19937 streams (max_steps=1: every step ends an episode), so that
     the lazily regenerated state is entered at every alignment and wraps hundreds of times per stream; state, goal
     state and the exact stream (key and position) must still equal the oracle's at the end and on the way."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T, chunk = 256, 3000, 750
     kw = dict(size=(9, 9), max_steps=1)
-    env = CraftingWorldVecEnv(N, obs_mode='state', seed=2024, **kw)
-    keys, pos = env.get_rng_states()
+    env, keys, pos = make_env(N, obs_mode='state', seed=2024, **kw)
     ora = OracleBatch(N, rng_states=[(keys[i], int(pos[i])) for i in range(N)], **kw)
     env.reset()
     ora.reset()
@@ -1497,16 +1278,7 @@ def test_long_reset_chains_on_one_stream_vs_oracle():
             for t in range(chunk):
                 env.step(torch.as_tensor(acts[t].astype(np.uint8), device=env.device))
         assert ora.rollout(acts, nthreads=8) == chunk * N
-        st = env.get_state()
-        k2, p2 = env.get_rng_states()
-        for i, s in enumerate(ora.states()):
-            assert np.array_equal(st['grid'][i], s['grid']) and np.array_equal(st['goal_grid'][i], s['goal_grid']), (c, i)
-            assert st['desired'][i] == s['desired'] and st['ep_no'][i] == s['ep_no'], (c, i)
-        for i in range(0, N, 5):
-            ok, op = ora.envs[i].get_rng()
-            assert p2[i] % 624 == op % 624, (c, i)
-            if op % 624:
-                assert np.array_equal(k2[i][1:], ok[1:]), (c, i)
+        same_states(env, ora, tag='chunk %d: ' % c)
     assert int(env.counters[1].item()) == N * T
     env.close()
 
@@ -1516,7 +1288,6 @@ def test_random_configurations_vs_oracle():
     """A seeded sweep over the configuration space itself -- grid size, episode length, ordered task subsets with
     number_of_tasks / stacking / reward style, fixed-init pools, observation mode, raster -- each drawn at random and run
     against the oracle with auto-reset: reward, done, masks every step; state, frames and RNG stream at the end."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     cfg_rng = np.random.RandomState(20260101)
     for c in range(40):
@@ -1530,38 +1301,16 @@ def test_random_configurations_vs_oracle():
         raster = 'alt' if (obs_mode != 'state' and cfg_rng.rand() < 0.3) else 'ray'
         N, T = int(cfg_rng.choice([1, 3, 17, 64, 130])), int(cfg_rng.randint(20, 90))
         tag = (c, S, kw, obs_mode, raster, N, T)
-        keys, pos = _np_states(N, 5000 + 37 * c)
-        env = CraftingWorldVecEnv(N, obs_mode=obs_mode, raster=raster, **kw)
-        env.set_rng_states(keys, pos)
-        if kw['fixed_init_state']:
-            from gym_craftingworld_amd import _lib as L
-            L.check(env._lib.cw_generate_fixed_states(env._h, env._stream()), 'pool')
-        ora = OracleBatch(N, rng_states=list(zip(keys, pos)), alt_obs=(raster == 'alt'), **kw)
+        env, keys, pos = make_env(N, *np_states(N, 5000 + 37 * c), obs_mode=obs_mode, raster=raster, **kw)
+        ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **oracle_kw(kw, raster))
         env.reset(); ora.reset()
         acts = np.random.RandomState(c).randint(0, 6, size=(T, N)).astype(np.int64)
         for t in range(T):
             obs, rew, done, info = env.step(torch.as_tensor(acts[t], device=env.device))
-            o_rew, o_done, o_ach = np.empty(N, np.int32), np.zeros(N, bool), np.empty(N, np.int64)
-            for i, e in enumerate(ora.envs):
-                _, o_rew[i], o_done[i], _ = e.step(int(acts[t, i]))
-                o_ach[i] = e.view().achieved
-                if o_done[i]:
-                    e.reset()
+            o_rew, o_done, o_ach, _ = ora.step(acts[t], details=True)
             assert np.array_equal(rew.cpu().numpy(), o_rew) and np.array_equal(done.cpu().numpy(), o_done), (tag, t)
             assert np.array_equal(info['achieved_goal'].cpu().numpy().astype(np.int64) & 0xFFFF, o_ach), (tag, t)
-        st = env.get_state()
-        frames = env.render().cpu().numpy()
-        k2, p2 = env.get_rng_states()
-        for i, s in enumerate(ora.states()):
-            assert np.array_equal(st['grid'][i], s['grid']) and np.array_equal(st['goal_grid'][i], s['goal_grid']), (tag, i)
-            assert tuple(st['agent_rc'][i]) == s['agent'] and st['hold'][i] == s['hold'] and st['desired'][i] == s['desired'], (tag, i)
-            assert st['ep_no'][i] == s['ep_no'] and st['step_num'][i] == s['step_num'], (tag, i)
-            assert np.array_equal(frames[i], s['obs']), (tag, i)
-            if obs_mode != 'state':
-                assert np.array_equal(obs['observation'][i].cpu().numpy(), s['obs']), (tag, i)
-                assert np.array_equal(obs['desired_goal'][i].cpu().numpy(), s['desired_img']), (tag, i)
-            ok, op = ora.envs[i].get_rng()
-            assert p2[i] % 624 == op % 624, (tag, i)
+        same_states(env, ora, frames=('render',) + (tuple(FRAMES) if obs_mode != 'state' else ()), tag='%s: ' % (tag,))
         env.close()
 
 
@@ -1772,24 +1521,19 @@ def test_facade_store_gif_files_and_rng_draw(tmp_path, monkeypatch):
 def test_one_hot_of_goal_and_init_states_vs_oracle():
     """The OneHot variant's other two observations at batch scale: one_hot(which='goal') is imagine_obs' final state
     (onehot.py:310), one_hot(which='init') the state at reset (onehot.py:203), both [N,S,S,12] on the device."""
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, kw = 96, dict(size=(8, 8), max_steps=15)
-    keys, pos = _np_states(N, 777)
-    env = CraftingWorldVecEnv(N, obs_mode='state', **kw)
-    env.set_rng_states(keys, pos)
+    env, keys, pos = make_env(N, *np_states(N, 777), obs_mode='state', **kw)
     ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **kw)
     env.reset(); ora.reset()
     acts = np.random.RandomState(1).randint(0, 6, size=(40, N)).astype(np.int8)
     env.rollout(torch.as_tensor(acts.astype(np.uint8), device=env.device), record=False)
     ora.rollout(acts, nthreads=4)
-    goal, init, cur = (env.one_hot(which=w).cpu().numpy() for w in ('goal', 'init', 'current'))
-    codes = lambda oh: (oh[:, :, :8] * np.arange(1, 9)).sum(axis=2)   # noqa: E731
-    for i, s in enumerate(ora.states()):
-        assert np.array_equal(codes(goal[i]), s['goal_grid']) and np.array_equal(codes(init[i]), s['init_grid']), i
-        assert np.array_equal(codes(cur[i]), s['grid']), i
-        assert tuple(np.argwhere(goal[i][:, :, 8] == 1)[0]) == s['goal_agent'], i
-        assert goal[i][:, :, 8].sum() == 1 and init[i][:, :, 8].sum() == 1 and goal[i][:, :, 9:].sum() == 0 and init[i][:, :, 9:].sum() == 0
+    same_states(env, ora, frames=('one_hot',))                       # (which='current', with the state itself and the RNG states)
+    o = oracle_arrays(ora.envs, ())
+    nothing = np.zeros(N, np.int64)                                  # the goal and the reset state hold nothing: channels 9-11 empty
+    same('one_hot(goal)', 0, env.one_hot(which='goal').cpu().numpy(), one_hot_of(o['goal_grid'], o['goal_agent_rc'], nothing))
+    same('one_hot(init)', 0, env.one_hot(which='init').cpu().numpy(), one_hot_of(o['init_grid'], o['init_agent_rc'], nothing))
     env.close()
 
 
@@ -1921,15 +1665,14 @@ def test_headline_shape_reset_storm_65536(keep_terminal):
     """The headline shape (65 536 envs, 21x21, full-frame pixel obs) across steps on which EVERY env times out at once
     (max_steps=20, T=45: storms at t=19 and t=39 -- ray.py:367 then reset ray.py:156-218 for the whole batch: on the first every env takes its
     look-ahead record, on the second -- four steps after a refill -- too): full frames == dirty-cell frames on the storm step itself and after
-    it, a sample of 256 envs (the first 128, a stride through the batch, the last 64) == the CPU oracle (all three frames, terminal frame, RNG
-    stream position), counters."""
+    it, a sample of 256 envs (the first 128, a stride through the batch, the last 64) == the CPU oracle (reward and done of every step; state, all
+    three frames and the terminal frames on the storm steps and every 13th; the RNG states, key and position, at the end), counters."""
     from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T, M = 65536, 45, 256
     kw = dict(size=(21, 21), max_steps=20)
-    full = CraftingWorldVecEnv(N, obs_mode='pixels', seed=321, keep_terminal_obs=keep_terminal, **kw)
+    full, keys, pos = make_env(N, obs_mode='pixels', seed=321, keep_terminal_obs=keep_terminal, **kw)
     dirty = CraftingWorldVecEnv(N, obs_mode='pixels_dirty', seed=321, keep_terminal_obs=keep_terminal, **kw)
-    keys, pos = full.get_rng_states()
     idx = list(range(128)) + list(range(300, N - 64, (N - 364) // 64))[:64] + list(range(N - 64, N))
     assert len(idx) == M and idx[-1] == N - 1
     idx_t = torch.as_tensor(idx, device='cuda')
@@ -1944,15 +1687,7 @@ def test_headline_shape_reset_storm_65536(keep_terminal):
         assert torch.equal(rf, rd) and torch.equal(df, dd), t
         n_done = int(df.sum().item())
         dones += n_done
-        an = a[idx_t].cpu().numpy()
-        term_ref = {}
-        o_done = np.zeros(M, bool)
-        o_rew = np.zeros(M, np.int32)
-        for i, e in enumerate(ora.envs):
-            o, o_rew[i], o_done[i], _ = e.step(int(an[i]))
-            if o_done[i]:
-                term_ref[i] = o['observation'].copy()
-                e.reset()
+        o_rew, o_done, _, o_term = ora.step(a[idx_t].cpu().numpy(), details=True)
         assert np.array_equal(rf[idx_t].cpu().numpy(), o_rew) and np.array_equal(df[idx_t].cpu().numpy(), o_done), t
         storm = n_done > N * 0.9
         if storm or t % 13 == 0 or t == T - 1:
@@ -1963,16 +1698,9 @@ def test_headline_shape_reset_storm_65536(keep_terminal):
             if keep_terminal:
                 d = df.nonzero().flatten()
                 assert torch.equal(inf['terminal_observation'][d], ind['terminal_observation'][d]), t
-                term = inf['terminal_observation'][idx_t].cpu().numpy()
-                for i, fr in term_ref.items():
-                    assert np.array_equal(term[i], fr), (t, i)
-            fo, fg, fi = (of[k][idx_t].cpu().numpy() for k in ('observation', 'desired_goal', 'init_observation'))
-            for i, s in enumerate(ora.states()):
-                assert np.array_equal(fo[i], s['obs']) and np.array_equal(fg[i], s['desired_img']) and np.array_equal(fi[i], s['init_img']), (t, idx[i])
+                same_terminal(inf['terminal_observation'], o_term, idx, tag='step %d: ' % t)
+            same_states(full, ora, idx, frames=tuple(FRAMES), rng=t == T - 1, tag='step %d: ' % t)
     assert storms == 2 and dones >= 2 * N
-    _, p2 = full.get_rng_states()
-    for i, e in enumerate(ora.envs):
-        assert p2[idx[i]] % 624 == e.get_rng()[1] % 624, idx[i]
     assert torch.equal(full.hdr, dirty.hdr) and torch.equal(full.slot_pos, dirty.slot_pos)
     assert int(full.counters[1].item()) == dones == int(dirty.counters[1].item()) and int(full.counters[0].item()) == N * T
     full.close(); dirty.close()
@@ -2172,17 +1900,14 @@ def test_policy_in_the_loop_actions_replay_through_the_oracle(obs_mode, consumer
     """SURVEY 8b's callers: a torch policy consuming the device tensors without host copies (docs/source/envs/gen_info.rst:62-82 with a network where
     the reference samples; ray.py:376-378 hands the observation back).  Between two steps a consumer reads EVERY observation byte and produces the
     next actions from it (bench.py's --consumer), all on the env's stream, no host synchronisation inside the loop: 200 steps of 4 096 envs.  Then
-    the RECORDED actions go through the oracle: rewards, dones and frames must be the oracle's, and -- `reduce` / `reduce32`, whose policy a host can
+    the RECORDED actions go through the oracle: rewards, dones and, at the end, every env's state, frames and RNG state must be the oracle's, and -- `reduce` / `reduce32`, whose policy a host can
     restate exactly -- every recorded action must be what the policy computes from the ORACLE's frame of that step: a consumer that read a frame before the
     sweep (or the step kernel's repaint) had written it would have taken another action."""
     import bench
-    from gym_craftingworld_amd import CraftingWorldVecEnv
     from oracle import OracleBatch
     N, T = 4096, 200
     kw = dict(size=(21, 21), max_steps=37)                # (episodes end inside the run, at spread-out steps once some succeed)
-    keys, pos = _np_states(N, 52000)
-    env = CraftingWorldVecEnv(N, obs_mode=obs_mode, **kw)
-    env.set_rng_states(keys, pos)
+    env, keys, pos = make_env(N, *np_states(N, 52000), obs_mode=obs_mode, **kw)
     policy = bench.make_consumer(consumer, N, env.frame_shape, env.device)
     obs = env.reset()
     # spread the episode phases out: envs finish on every step, so frames of freshly reset envs are consumed on every step too
@@ -2199,13 +1924,9 @@ def test_policy_in_the_loop_actions_replay_through_the_oracle(obs_mode, consumer
         a = policy(obs['observation'])
     torch.cuda.synchronize()
     acts, rews, dones = rec_a.cpu().numpy(), rec_r.cpu().numpy(), rec_d.cpu().numpy()
-    final = obs['observation'].cpu().numpy()
-    goal = obs['desired_goal'].cpu().numpy()
     ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **kw)
     ora.reset()
-    for i, e in enumerate(ora.envs):                       # the same phase spread (step_num only)
-        s = e.state()
-        e.set_state(s['grid'], s['init_grid'], s['agent'], s['hold'], s['achieved'], s['desired'], i % 30)
+    set_phase(ora, np.arange(N) % 30)                      # the same phase spread
     ish = ora.envs[0].img_shape
     n_done = 0
     for t in range(T):
@@ -2222,9 +1943,7 @@ def test_policy_in_the_loop_actions_replay_through_the_oracle(obs_mode, consumer
         assert np.array_equal(dones[t], o_done), ('done', t)
         n_done += int(o_done.sum())
     assert n_done > 2 * N                                  # every env was reset several times on the way
-    for i in list(range(0, N, 61)) + [N - 1]:
-        s = ora.envs[i].state()
-        assert np.array_equal(final[i], s['obs']) and np.array_equal(goal[i], s['desired_img']), i
+    same_states(env, ora, frames=tuple(FRAMES))
     assert int(env.counters[1].item()) == n_done
     env.close()
 
@@ -2419,7 +2138,7 @@ def test_checkpoints_cross_lookahead_settings(obs_mode, tmp_path, monkeypatch):
     assert b.tuner_state()['lookahead'] == 0
     b.load_checkpoint(pa)
     ka, qa = a.get_rng_states(); kb, qb = b.get_rng_states()
-    assert np.array_equal(qa % 624, qb % 624) and np.array_equal(ka[:, 1:], kb[:, 1:])
+    assert np.array_equal(qa, qb) and np.array_equal(ka[:, 1:], kb[:, 1:])
     for t in range(37, 90):
         _, ra, da, _ = a.step(acts[t])
         _, rb, db, _ = b.step(acts[t])
@@ -2439,7 +2158,7 @@ def test_checkpoints_cross_lookahead_settings(obs_mode, tmp_path, monkeypatch):
         for k in oa:
             assert torch.equal(oa[k], oc[k]), k
     ka, qa = a.get_rng_states(); kc, qc = c.get_rng_states()
-    assert np.array_equal(qa % 624, qc % 624) and np.array_equal(ka[:, 1:], kc[:, 1:])
+    assert np.array_equal(qa, qc) and np.array_equal(ka[:, 1:], kc[:, 1:])
     assert int(c._counters_raw[5]) < N // 4              # (c found records again after its first refill: no slow resets to speak of)
     for e in (a, b, c):
         e.close()

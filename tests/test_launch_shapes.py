@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle_replay import assert_counters, replay_against_oracle
+from oracle_replay import assert_counters, make_env, record_steps, replay_against_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -19,11 +19,11 @@ EARLY_END = dict(size=(8, 8), max_steps=300, reward_style='subset', selected_tas
 
 
 def _engine(monkeypatch, N, kw, tune=None, **mode):
-    from gym_craftingworld_amd import CraftingWorldVecEnv
+    """-> (engine, keys, pos): created under the CW_TUNE_* variables `tune`, with the RNG states its oracle starts from"""
     with monkeypatch.context() as m:
         for k, v in (tune or {}).items():
             m.setenv(k, str(v))
-        return CraftingWorldVecEnv(N, seed=4242, **mode, **kw)
+        return make_env(N, seed=4242, **mode, **kw)
 
 
 def _actions(T, N, seed, hi=6):
@@ -41,10 +41,8 @@ def _rollout_vs_oracle_and_stepping(monkeypatch, N, kw, T, phase, walker, segmen
     """one engine runs rollout(record=True), a twin of the same batch T x step(); both against each other, the rollout against the oracle.
     -> the rollout engine's counters"""
     tune = {} if segment is None else {'CW_TUNE_ROLLOUT_SEGMENT': segment}
-    rolled = _engine(monkeypatch, N, kw, tune, obs_mode='state')
-    stepped = _engine(monkeypatch, N, kw, obs_mode='state')
-    keys, pos = rolled.get_rng_states()
-    stepped.set_rng_states(keys, pos)
+    rolled, keys, pos = _engine(monkeypatch, N, kw, tune, obs_mode='state')
+    stepped = _engine(monkeypatch, N, kw, keys=keys, pos=pos, obs_mode='state')[0]
     ph = _phase(N, kw) if phase else None
     for e in (rolled, stepped):
         e.reset()
@@ -104,25 +102,15 @@ def test_rollout_whose_rings_run_dry_segmented_and_in_one_launch_against_the_ora
 def _steps_vs_oracle(monkeypatch, N, kw, obs_mode, T, tune=None, keep_terminal_obs=False, phase=True, fixed=False):
     """T steps of random actions with episodes ending on every step (phases spread), every reward and done, and at the end the frames (pixel
     modes; terminal_observation with keep_terminal_obs), the state and the RNG state of every env against the oracle.  -> (engine, counters)"""
-    env = _engine(monkeypatch, N, kw, tune, obs_mode=obs_mode, keep_terminal_obs=keep_terminal_obs)
-    keys, pos = env.get_rng_states()
-    if fixed:                                                                 # (the pool is drawn at construction: redraw it from the states the oracle gets)
-        from gym_craftingworld_amd import _lib as L
-        env.set_rng_states(keys, pos)
-        L.check(env._lib.cw_generate_fixed_states(env._h, env._stream()), 'pool')
+    env, keys, pos = _engine(monkeypatch, N, kw, tune, obs_mode=obs_mode, keep_terminal_obs=keep_terminal_obs)
+    assert fixed == bool(kw.get('fixed_init_state'))                          # (make_env has redrawn the pool from the states the oracle gets)
     env.reset()
     ph = _phase(N, kw) if phase else None
     if phase:
         env.set_state(step_num=ph)
     acts = _actions(T, N, 17)
-    rs = torch.empty((T, N), dtype=torch.int32, device='cuda')
-    ds = torch.empty((T, N), dtype=torch.bool, device='cuda')
-    for t in range(T):
-        _, r, d, _ = env.step(acts[t])
-        rs[t] = r
-        ds[t] = d
-    torch.cuda.synchronize()
-    res = replay_against_oracle(env, keys, pos, kw, acts.cpu().numpy(), rs.cpu().numpy(), ds.cpu().numpy(), phase=ph,
+    rs, ds = record_steps(env, acts)
+    res = replay_against_oracle(env, keys, pos, kw, acts.cpu().numpy(), rs, ds, phase=ph,
                                 frames=obs_mode != 'state', terminal=keep_terminal_obs, pools=fixed)
     c = assert_counters(env, N, T, res)
     assert res['finished'] >= N
