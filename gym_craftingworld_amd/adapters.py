@@ -12,7 +12,7 @@
 import torch
 
 from .sharding import shard_range
-from .vec_env import CraftingWorldVecEnv
+from .vec_env import CraftingWorldVecEnv, reset_mask
 
 
 class GymnasiumVecAdapter:
@@ -25,6 +25,13 @@ class GymnasiumVecAdapter:
         self.action_space = venv.action_space
 
     def reset(self, *, seed=None, options=None):
+        """options={'reset_mask': m} (gymnasium >= 1.0's vector API): only the envs with m[i] set are reset (venv.reset_envs); not together with
+        `seed`, which restarts every env's stream."""
+        if options is not None and options.get('reset_mask') is not None:
+            if seed is not None:
+                raise ValueError("seed= re-seeds every env: it cannot be combined with options['reset_mask']")
+            obs = self.venv.reset_envs(mask=options['reset_mask'])
+            return obs, {'desired_goal': self.venv.hdr[:, 6:8]}
         if seed is not None:
             self.venv.seed(seed)
         obs = self.venv.reset()
@@ -71,6 +78,17 @@ class MultiDeviceVecEnv:
         for sh, st in zip(self.shards, self.streams):
             with torch.cuda.stream(st):
                 out.append(sh.reset())
+        return out
+
+    def reset_envs(self, mask):
+        """reset() of the envs with mask[i] set (CraftingWorldVecEnv.reset_envs): the [num_envs] mask is split along self.ranges, each shard's part
+        goes to that shard on its own stream; per-shard observation dicts as a list, like reset()."""
+        m = mask.cpu().numpy() if torch.is_tensor(mask) else mask
+        m = reset_mask(self.num_envs, mask=m)
+        out = []
+        for (lo, hi), sh, st in zip(self.ranges, self.shards, self.streams):
+            with torch.cuda.stream(st):
+                out.append(sh.reset_envs(mask=m[lo:hi]))
         return out
 
     def step(self, actions):

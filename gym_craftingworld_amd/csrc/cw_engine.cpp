@@ -21,6 +21,7 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
                            hipEvent_t *ev);
 hipError_t cwk_launch_refill(const CwParams *P, const CwTuning *T, int all_envs, hipStream_t st);
 hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mode, hipStream_t st);
+hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st);
 hipError_t cwk_launch_pool(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_seed(const CwParams *P, const uint32_t *seeds_dev, hipStream_t st);
 hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, int paint_dirty, unsigned long long idle_ticks,
@@ -721,6 +722,21 @@ int cw_reset(cw_engine *e, cw_stream_t stream)
         e->la_steps = 0;
     }
     e->has_reset = true;
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// reset() of the envs the caller selects: ONE kernel (cw_reset_masked_kernel) and nothing else.  No refill of its own -- an env that took a record is QUEUED,
+// and the refill that rides on cw_step serves it; la_steps / la_refill_all stay as they are -- so the call is the same whether it is enqueued or captured.
+int cw_reset_masked(cw_engine *e, const uint8_t *mask, cw_stream_t stream)
+{
+    if (!e || !mask) return fail(CW_ERR_INVALID, "cw_reset_masked: null %s", !e ? "engine" : "mask");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_reset_masked called before cw_reset");
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_reset_masked(&e->P, &e->tune, mask, e->obs_mode, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

@@ -7,6 +7,8 @@
 //   cw_refill_kernel  one WAVEFRONT per env: the NEXT reset() of ray.py:156-218, ahead of time and in bulk = task draw, legacy
 //                     Fisher-Yates placement on the env's MT19937 stream (state staged in LDS, lane-parallel rejection sampling),
 //                     imagine_obs().  cw_reset_kernel: the same for every env at once (explicit reset()).
+//   cw_reset_masked_kernel  reset() of the envs a caller's byte mask selects: the waves scan the mask, a selected env takes its look-ahead record or is
+//                     reset by a wave, and its three frames are painted on the spot (no sweep of the arrays).
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -904,6 +906,88 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_kernel(CwPar
             P.hdr[env] = reset_header(P, r, menu_id);
             P.achieved_out[env] = 0;
             P.desired_out[env] = (uint16_t)r.desired;
+        }
+    }
+}
+
+// reset() of the envs the CALLER selects (cw_reset_masked): mask[i] != 0 resets env i, every other env is left exactly as it is.  `mask` is only read
+// (it may be the engine's own `done` array: nothing here writes reward, done, the episode outputs or counters[0..3] -- a forced reset is not a finished
+// episode).  No list and no count: a workgroup SCANS `epb` consecutive mask bytes per round (4 ... 64, cwk_launch_reset_masked: fewer for small batches) --
+// all four waves load the same bytes, one per lane, and hold the same ballot, so they share its set bits without a word of LDS or a barrier: the selected env
+// of rank k goes to wave k mod 4.  A wave that found three selected envs among its 64 would otherwise reset and paint them alone while its neighbours
+// idle (the load balance the step kernel's CwPaintJob queue is for; here whole envs are dealt out, reset and frames together).
+// A selected env takes over the record at the head of its ring if one waits (lane 0; the env is left QUEUED, the next refill tops its ring up), else the
+// whole wave resets it from its stream as cw_reset_kernel does -- on a look-ahead engine counted as a slow reset.  A take-over clears the record's valid
+// bit, and cw_get_mt, the checkpoints and cw_generate_fixed_states work from the valid bits alone: none of them needs to know of this kernel.
+// PAINT (pixel modes): the env's INIT_OBS and observation frames (after a reset both show the same pixels) in one call, then its desired_goal frame, by the
+// wave -- 3 frames per selected env, not a sweep of the arrays.
+template <bool PAINT>
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_masked_kernel(CwParams P, const uint8_t *__restrict__ mask, int epb)
+{
+    __shared__ uint32_t s_mt[CW_RESET_WAVES][CW_MT_WORDS];
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
+    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
+        const int mine = base + lane;
+        const bool in_chunk = lane < epb && mine < P.n_envs;
+        const uint32_t v_sel = in_chunk ? (uint32_t)mask[mine] : 0u;
+        unsigned long long m = CW_BALLOT(v_sel != 0u);
+        for (int rank = 0; m; rank++) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
+            const int env = base + l;
+            const uint4 v_h = P.hdr[env];                                 // in flight beside the MT state
+            const uint32_t menu_id = __builtin_amdgcn_readfirstlane(v_h.x) >> 24;
+            const bool count_episode = (__builtin_amdgcn_readfirstlane(v_h.z) & 0xFFFFu) != 0;   // ray.py:200-201
+            const uint32_t ctl = P.lookahead ? __builtin_amdgcn_readfirstlane(P.nx_ctl[env]) : 0u;
+            uint4 ipos, gpos;                                             // the new episode, wave-uniform: placement, goal state
+            uint32_t iagent, gagent, gcodes;
+            if (P.lookahead && (__builtin_amdgcn_readfirstlane(P.nx_misc[(size_t)(ctl & 0xFFu) * P.n_envs + env].z) >> 31)) {        // the next episode is waiting
+                uint4 h = v_h;
+                uint32_t sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                CwGoalState goal;
+                goal.pos = make_uint4(0, 0, 0, 0); goal.codes = 0; goal.agent = 0;
+                if (lane == 0) {
+                    pop_next_episode(P, env, ctl, h, sp, count_episode, PAINT ? &goal : nullptr);
+                    P.pos[env] = pack_pos(sp);
+                    P.hdr[env] = h;
+                    P.achieved_out[env] = 0;                              // the mask outputs describe the new episode, as after cw_reset
+                    P.desired_out[env] = (uint16_t)(h.y >> 16);
+                }
+                if constexpr (PAINT) {                                    // lane 0's record for the whole wave
+                    const uint4 p0 = pack_pos(sp);
+                    ipos = make_uint4(__builtin_amdgcn_readfirstlane(p0.x), __builtin_amdgcn_readfirstlane(p0.y), __builtin_amdgcn_readfirstlane(p0.z),
+                                      __builtin_amdgcn_readfirstlane(p0.w));
+                    gpos = make_uint4(__builtin_amdgcn_readfirstlane(goal.pos.x), __builtin_amdgcn_readfirstlane(goal.pos.y),
+                                      __builtin_amdgcn_readfirstlane(goal.pos.z), __builtin_amdgcn_readfirstlane(goal.pos.w));
+                    iagent = agent_cell_of(P, __builtin_amdgcn_readfirstlane(h.x));
+                    gagent = __builtin_amdgcn_readfirstlane(goal.agent);
+                    gcodes = __builtin_amdgcn_readfirstlane(goal.codes);
+                }
+            } else {
+                const CwResetOut r = reset_env_wave(P, env, [&]() { return menu_id; }, s_mt[wave_in_block], lane);
+                if (lane == 0) {
+                    store_episode_records(P, env, r, count_episode);
+                    P.pos[env] = r.init_pos;
+                    P.hdr[env] = reset_header(P, r, menu_id);
+                    P.achieved_out[env] = 0;
+                    P.desired_out[env] = (uint16_t)r.desired;
+                    if (P.lookahead) note_slow_reset(P, env, ctl);
+                }
+                ipos = r.init_pos; gpos = r.goal_pos;
+                iagent = r.init_agent; gagent = r.goal_agent; gcodes = r.goal_codes;
+            }
+            if constexpr (PAINT) {
+                const size_t off = (size_t)env * P.frame_bytes;
+                uint32_t jp[8];
+                unpack_pos(ipos, jp);
+                paint_state_frame(P, P.init_img + off, jp, CW_CODES_INITIAL, iagent, 0u, lane, P.obs + off);
+                unpack_pos(gpos, jp);
+                paint_state_frame(P, P.desired_img + off, jp, gcodes, gagent, 0u, lane);
+            } else {
+                (void)ipos; (void)gpos; (void)iagent; (void)gagent; (void)gcodes;
+            }
         }
     }
 }
@@ -1979,6 +2063,19 @@ hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mo
 {
     hipLaunchKernelGGL(cw_reset_kernel, dim3(cw_reset_grid(*T, P->n_envs)), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P);
     if (obs_mode != 0) return cwk_launch_render_restore(P, T, st);
+    return hipGetLastError();
+}
+
+// reset() of the envs with mask[i] != 0 (cw_reset_masked_kernel): one launch, nothing else.  A workgroup scans `epb` mask bytes per round and deals the
+// selected envs out to its four waves: 64 for batches that fill the card with such workgroups, down to 4 (one env per wave, cw_reset_kernel's shape) for small ones
+hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st)
+{
+    const int most = T->n_cu * T->reset_blocks_per_cu;
+    int epb = CW_WAVE;
+    while (epb > CW_RESET_WAVES && (P->n_envs + epb - 1) / epb < most) epb >>= 1;
+    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    if (obs_mode != 0) hipLaunchKernelGGL(cw_reset_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
+    else hipLaunchKernelGGL(cw_reset_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
     return hipGetLastError();
 }
 

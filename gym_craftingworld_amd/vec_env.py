@@ -69,6 +69,34 @@ def _host_view(ptr, shape, dtype):
     return torch.from_numpy(arr)
 
 
+def reset_mask(num_envs, mask=None, indices=None):
+    """The byte mask cw_reset_masked takes, built and validated on the host: -> np.uint8 [num_envs], 1 = reset that env.  Exactly one of
+    `mask` (a bool / integer array of shape [num_envs], non-zero = reset) and `indices` (env ids in -num_envs .. num_envs - 1, duplicates allowed,
+    an empty list selects nothing).  ValueError for a wrong shape or both / neither argument, IndexError for an index outside the batch."""
+    num_envs = int(num_envs)
+    if (mask is None) == (indices is None):
+        raise ValueError('give exactly one of mask and indices')
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.shape != (num_envs,):
+            raise ValueError('mask must have shape (%d,), got %s' % (num_envs, m.shape))
+        if m.dtype != np.bool_ and not np.issubdtype(m.dtype, np.integer):
+            raise ValueError('mask must be a bool or integer array, got %s' % m.dtype)
+        return np.ascontiguousarray(m != 0, dtype=np.uint8)
+    idx = np.asarray(indices)
+    if idx.size == 0:
+        return np.zeros(num_envs, dtype=np.uint8)
+    if idx.ndim > 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError('indices must be a flat list of integer env ids')
+    idx = idx.reshape(-1).astype(np.int64)
+    bad = idx[(idx < -num_envs) | (idx >= num_envs)]
+    if bad.size:
+        raise IndexError('env index %d outside a batch of %d envs' % (int(bad[0]), num_envs))
+    out = np.zeros(num_envs, dtype=np.uint8)
+    out[idx] = 1
+    return out
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -213,6 +241,7 @@ class CraftingWorldVecEnv:
             init_observation=Box(0, 1, (self.size, self.size, 12), np.uint8)))
         self._pending = False
         self._actions_keepalive = None
+        self._mask_keepalive = None
         self._cw_step, self._di = self._lib.cw_step, self.device.index
         self._raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (lambda di: torch.cuda.current_stream(di).cuda_stream)
         self.seed(seed)                                              # ray.py:70 (OS entropy when None)
@@ -332,6 +361,28 @@ class CraftingWorldVecEnv:
     def reset(self):
         self.reset_async()
         return self.reset_wait()
+
+    def reset_envs(self, mask=None, *, indices=None):
+        """reset() of SOME envs (cw_reset_masked): those with mask[i] set, or those listed in `indices` -- exactly one of the two; every other env
+        is left exactly as it is.  -> the observation dict (live views, as reset() returns).  A contiguous torch.bool / torch.uint8 tensor [num_envs]
+        on the env's device is handed to the kernel in place -- no copy, no synchronisation: `env.reset_envs(env.done)` after every step() is the
+        manual-reset loop of an auto_reset=False engine (and can be captured into a graph with the steps).  Anything else (numpy, lists, `indices`)
+        is validated and packed on the host (reset_mask) and copied over.  A selected row afterwards holds what reset() leaves there; reward, done,
+        the episode statistics and the counters are not touched: a forced reset is not a finished episode."""
+        if type(mask) is torch.Tensor and (mask.is_cuda or not self.host_outputs) and mask.device != self.device:
+            raise ValueError('the mask tensor is on %s, the envs are on %s' % (mask.device, self.device))
+        if (type(mask) is torch.Tensor and indices is None and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
+                and tuple(mask.shape) == (self.num_envs,) and mask.is_contiguous()):
+            m = mask
+        else:
+            if torch.is_tensor(mask):
+                mask = mask.cpu().numpy()
+            m = torch.as_tensor(reset_mask(self.num_envs, mask, indices)).to(self.device)
+        self._mask_keepalive = m
+        L.check(self._lib.cw_reset_masked(self._h, C.c_void_p(m.data_ptr()), self._stream()), 'cw_reset_masked', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return self._observation()
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -80,7 +80,7 @@ typedef struct cw_config {
     int32_t fixed_init_state;   /* 0, or pool size K per env (ray.py:116-118), K <= 64 */
     int32_t obs_mode;           /* CW_OBS_* */
     int32_t auto_reset;         /* 1: cw_step resets finished envs itself (gym.vector semantics);
-                                 * 0: finished envs keep stepping until cw_reset (single gym.Env semantics, ray.py:367) */
+                                 * 0: finished envs keep stepping until cw_reset / cw_reset_masked (single gym.Env semantics, ray.py:367) */
     int32_t keep_terminal_obs;  /* 1 (pixel modes + auto_reset): before a finished env is reset, its last frame is
                                  * painted into cw_buffer_table.terminal_obs (gym.vector's info["terminal_observation"]) */
     int32_t raster;             /* CW_RASTER_* (pixel modes) */
@@ -176,6 +176,18 @@ int cw_get_fixed_states(cw_engine *e, uint16_t *out);
 
 /* --- reset() for every env (ray.py:156-218): task draw, placement, imagine_obs, render ------ */
 int cw_reset(cw_engine *e, cw_stream_t stream);
+
+/* --- reset() (ray.py:156-218) for the envs i with mask[i] != 0; every other env is left exactly as it is.  The reference has no counterpart (there it
+ * is one reset() call per env object).  mask: DEVICE pointer (with cw_config.host_outputs: or GPU-mapped host memory) to num_envs bytes, only read;
+ * it may be cw_buffer_table.done itself -- `cw_step(e, a, t, s); cw_reset_masked(e, tab.done, s);` is the manual-reset loop of an engine without
+ * auto_reset, which then computes what an auto_reset engine computes.  Works on auto_reset engines too (an episode cut short by the caller).
+ * A selected row is left as cw_reset leaves it: new state, achieved = 0, desired = the new episode's mask, in the pixel modes its obs, init_obs and
+ * desired_goal frames; reward, done, episode_length, episode_return, terminal_obs and counters[0..3] are NOT written -- a forced reset is not a finished
+ * episode.  Engines that keep look-ahead records hand the env the record at the head of its ring (the refill that rides on cw_step tops the ring up);
+ * an env without one is reset from its stream on the spot and counted in counters[5].
+ * Only enqueues ONE kernel (cw_reset_masked_kernel) on `stream` -- no host synchronisation, no allocation -- so it can be captured into a HIP graph together
+ * with cw_step / cw_step_many.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load. */
+int cw_reset_masked(cw_engine *e, const uint8_t *mask, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
