@@ -77,6 +77,8 @@ ABI = {
     'cw_get_fixed_states': (C.c_int, [_VP, _VP]),
     'cw_reset': (C.c_int, [_VP, _VP]),
     'cw_reset_masked': (C.c_int, [_VP, _VP, _VP]),
+    'cw_imagine_masked': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
+    'cw_sample_state_masked': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),

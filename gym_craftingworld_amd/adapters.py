@@ -91,6 +91,35 @@ class MultiDeviceVecEnv:
                 out.append(sh.reset_envs(mask=m[lo:hi]))
         return out
 
+    def _split_mask(self, mask, indices):
+        if mask is None and indices is None:
+            return [None] * len(self.shards)
+        m = mask.cpu().numpy() if torch.is_tensor(mask) else mask
+        m = reset_mask(self.num_envs, mask=m, indices=indices)
+        return [m[lo:hi] for lo, hi in self.ranges]
+
+    def imagine_obs(self, mask=None, *, indices=None, desired=None, commit=False, one_hot=False):
+        """CraftingWorldVecEnv.imagine_obs over the shards: the [num_envs] mask / indices and `desired` ([num_envs] masks or [num_envs, T] rows) are split
+        along self.ranges, each part goes to its shard on that shard's stream; -> the shards' result tensors as a list."""
+        from .vec_env import desired_bits
+        parts = self._split_mask(mask, indices)
+        d = None
+        if desired is not None:
+            d = desired_bits(self.num_envs, desired.cpu().numpy() if torch.is_tensor(desired) else desired, len(self.shards[0].task_list))
+        out = []
+        for (lo, hi), sh, st, m in zip(self.ranges, self.shards, self.streams, parts):
+            with torch.cuda.stream(st):
+                out.append(sh.imagine_obs(mask=m, desired=None if d is None else d[lo:hi], commit=commit, one_hot=one_hot))
+        return out
+
+    def sample_states(self, mask=None, *, indices=None, pooled=False):
+        """CraftingWorldVecEnv.sample_states over the shards, the selection split as in reset_envs; -> the shards' [n, 9] tensors as a list."""
+        out = []
+        for sh, st, m in zip(self.shards, self.streams, self._split_mask(mask, indices)):
+            with torch.cuda.stream(st):
+                out.append(sh.sample_states(mask=m, pooled=pooled))
+        return out
+
     def step(self, actions):
         """actions: one tensor per device (already resident there), or a single host/device tensor of
         num_envs actions that is split.  Returns per-device lists [(obs, reward, done, info), ...];

@@ -22,6 +22,9 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
 hipError_t cwk_launch_refill(const CwParams *P, const CwTuning *T, int all_envs, hipStream_t st);
 hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mode, hipStream_t st);
 hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st);
+hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, const uint16_t *desired, int commit, int obs_mode,
+                                     uint8_t *out_frames, uint8_t *out_onehot, hipStream_t st);
+hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st);
 hipError_t cwk_launch_pool(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_seed(const CwParams *P, const uint32_t *seeds_dev, hipStream_t st);
 hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, int paint_dirty, unsigned long long idle_ticks,
@@ -737,6 +740,52 @@ int cw_reset_masked(cw_engine *e, const uint8_t *mask, cw_stream_t stream)
     PARK(e);
     if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
     HIP_TRY(cwk_launch_reset_masked(&e->P, &e->tune, mask, e->obs_mode, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// imagine_obs() / sample_state() draw from the envs' streams at their LOGICAL position.  An engine that keeps look-ahead records has run its streams ahead of
+// that: rewind them and drop the records, as cw_generate_fixed_states does (synchronous; the next refill covers the whole batch).
+static int rewind_streams(cw_engine *e, hipStream_t st, const char *who)
+{
+    if (!e->P.lookahead) return CW_OK;
+    if (stream_capturing(st)) return fail(CW_ERR_STATE, "%s: an engine that keeps look-ahead records rewinds its streams through the host and cannot be captured", who);
+    std::vector<uint32_t> keys((size_t)e->n * CW_MT_N);
+    std::vector<int32_t> pos((size_t)e->n);
+    int rc = cw_get_mt(e, keys.data(), pos.data());
+    if (rc == CW_OK) rc = cw_seed_mt(e, keys.data(), pos.data());
+    return rc;
+}
+
+int cw_imagine_masked(cw_engine *e, const uint8_t *mask, const uint16_t *desired, int32_t commit, uint8_t *out_frames, uint8_t *out_onehot,
+                      cw_stream_t stream)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_imagine_masked: null engine");
+    if (!commit && !out_frames && !out_onehot) return fail(CW_ERR_INVALID, "cw_imagine_masked: commit == 0 and no output pointer: nothing to do");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_imagine_masked called before cw_reset");
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    const int rc = rewind_streams(e, (hipStream_t)stream, "cw_imagine_masked");
+    if (rc != CW_OK) return rc;
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_imagine_masked(&e->P, &e->tune, mask, desired, commit != 0, e->obs_mode, out_frames, out_onehot, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, uint16_t *out_cells, cw_stream_t stream)
+{
+    if (!e || !out_cells) return fail(CW_ERR_INVALID, "cw_sample_state_masked: null %s", !e ? "engine" : "out_cells");
+    if (pooled && e->K == 0) return fail(CW_ERR_INVALID, "cw_sample_state_masked: pooled with fixed_init_state == 0");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_sample_state_masked called before cw_reset");
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    const int rc = rewind_streams(e, (hipStream_t)stream, "cw_sample_state_masked");
+    if (rc != CW_OK) return rc;
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_sample_state_masked(&e->P, &e->tune, mask, pooled != 0, out_cells, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

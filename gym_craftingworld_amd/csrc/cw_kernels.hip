@@ -9,6 +9,8 @@
 //                     imagine_obs().  cw_reset_kernel: the same for every env at once (explicit reset()).
 //   cw_reset_masked_kernel  reset() of the envs a caller's byte mask selects: the waves scan the mask, a selected env takes its look-ahead record or is
 //                     reset by a wave, and its three frames are painted on the spot (no sweep of the arrays).
+//   cw_imagine_masked_kernel  imagine_obs() of the selected envs against their RUNNING episode (a new goal state, optionally committed), dealt out the same way;
+//                     cw_sample_state_masked_kernel: sample_state() / generate_fixed_initial_state() from the selected envs' streams.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -722,20 +724,11 @@ struct CwResetOut {
     uint32_t draws;          // raw 32-bit draws taken from the env's stream
 };
 
-// menu_fn() yields the env's task-menu id; it is called after the MT state's loads are in flight, so a caller that
-// still has to fetch the id (cw_reset_kernel: from the header) overlaps that fetch with them.
-template <typename MenuFn>
-__device__ __forceinline__ CwResetOut reset_env_wave(const CwParams &P, int env, MenuFn menu_fn, uint32_t *lds_mt, int lane)
+// The three stages of a reset(), each usable on its own (cw_imagine_masked_kernel, cw_sample_state_masked_kernel); reset_env_wave runs them in the
+// reference's order on one stream.
+// task draw, ray.py:169-174 -> desired_goal_vector as task bits
+__device__ __forceinline__ uint32_t draw_tasks_wave(CwMtWave &mt, const CwMenuDev &M)
 {
-    CW_STAMP(env, 0);
-    const CwMtWave::Pending pend = CwMtWave::load_issue(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
-    const uint32_t menu_id = menu_fn();
-    const CwMenuDev M = P.menus[menu_id];
-    CwMtWave mt;
-    mt.load_commit(lds_mt, pend, lane);
-    CW_STAMP(env, 1);
-
-    // task draw, ray.py:169-174
     const uint32_t ntasks = M.stacking ? mt.randint((uint32_t)M.number_of_tasks) + 1u : 1u;
     unsigned long long perm = 0xFEDCBA9876543210ull;             // task_idx = arange(n_selected)
     for (int i = M.n_selected - 1; i >= 1; i--) {                 // RandomState.shuffle
@@ -749,28 +742,26 @@ __device__ __forceinline__ CwResetOut reset_env_wave(const CwParams &P, int env,
         const uint32_t idx = (uint32_t)((perm >> (4 * q)) & 15ull);
         desired |= 1u << (uint32_t)((M.sel_bits >> (4 * idx)) & 15ull);
     }
-
-    CW_STAMP(env, 2);
-    // placement: sample_state (ray.py:599-628) or a pooled one (ray.py:630-644); lane v < 9 = token v's cell
-    uint32_t v_tok;
-    if (P.pool_k == 0) {
-        v_tok = shuffle_tokens(mt, P.ncell);
-    } else {
-        const uint32_t pk = mt.randint((uint32_t)P.pool_k);
-        const uint16_t *pp = P.pool + ((size_t)env * P.pool_k + pk) * 9;
-        v_tok = lane < 9 ? (uint32_t)pp[lane] : 0u;
-    }
-    uint32_t agent = __builtin_amdgcn_readlane(v_tok, 8);
-    uint32_t v_fp = lane < 8 ? v_tok : (uint32_t)CW_POS_GONE;    // tokens 0..7 are objects 0..7 = slots 0..7
-    uint32_t v_fc = lane < 8 ? (uint32_t)lane + 1u : 0u;
-    uint32_t ip[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) ip[k] = __builtin_amdgcn_readlane(v_tok, k);
-    const uint4 init_packed = pack_pos(ip);
-    const uint32_t init_agent = agent;
-    CW_STAMP(env, 3);
-
-    // imagine_obs, ray.py:220-299, on the slot copy; same code order as the reference
+    return desired;
+}
+// placement: sample_state (ray.py:599-628; pooled == false) or a pooled one (ray.py:630-644); returns a VGPR whose lane v < 9 holds token v's cell
+// (tokens 0..7 = objects 0..7, 8 = the agent)
+__device__ __forceinline__ uint32_t place_env_wave(const CwParams &P, int env, CwMtWave &mt, bool pooled, int lane)
+{
+    if (!pooled) return shuffle_tokens(mt, P.ncell);
+    const uint32_t pk = mt.randint((uint32_t)P.pool_k);
+    const uint16_t *pp = P.pool + ((size_t)env * P.pool_k + pk) * 9;
+    return lane < 9 ? (uint32_t)pp[lane] : 0u;
+}
+// imagine_obs, ray.py:220-299, on the slot copy (v_fp / v_fc: the episode's START state, one of each object); same code order as the reference.
+// `init_agent` is the agent's cell in that start state, `cur_agent` the env's agent_pos at the call: GoToHouse (:274-276) moves channels 8: of the
+// CURRENT cell of the START state to the house, so the agent of the goal state stands on the house only if cur_agent == init_agent (inside reset()
+// always); the house is drawn either way.  Returns the goal state's agent cell; v_fp / v_fc become the goal state's slots.
+__device__ __forceinline__ uint32_t imagine_env_wave(const CwParams &P, CwMtWave &mt, uint32_t &v_fp, uint32_t &v_fc, uint32_t init_agent,
+                                                     uint32_t cur_agent, uint32_t desired)
+{
+    const int lane = mt.lane;
+    uint32_t agent = init_agent;
     if (desired & (1u << T_MAKEBREAD)) {                          // :226-231 the wheat -> bread
         CW_SET_LANE(v_fc, 7, (uint32_t)BREAD);
     }
@@ -803,7 +794,7 @@ __device__ __forceinline__ CwResetOut reset_env_wave(const CwParams &P, int env,
     if (desired & (1u << T_GOTOHOUSE)) {                          // :269-276
         const uint32_t which = mt.randint(count_code(v_fp, v_fc, HOUSE));
         const int sl = nth_with_code(v_fp, v_fc, HOUSE, which);
-        if (sl >= 0) agent = __builtin_amdgcn_readlane(v_fp, sl);
+        if (sl >= 0 && cur_agent == init_agent) agent = __builtin_amdgcn_readlane(v_fp, sl);
     }
     if (desired & (1u << T_MOVEAXE)) {                            // :277-286 (agent cell allowed, :282)
         const uint32_t present = (uint32_t)__popcll(CW_BALLOT(v_fp < CW_POS_HELD));
@@ -817,25 +808,57 @@ __device__ __forceinline__ CwResetOut reset_env_wave(const CwParams &P, int env,
         const uint32_t to = kth_unoccupied(v_fp, -1, which_spot);
         CW_SET_LANE(v_fp, 2, to);
     }
-    uint32_t fp[8], fc[8];
+    return agent;
+}
+// lanes 0..7 of the slot registers as the packed records the engine stores
+__device__ __forceinline__ void pack_goal_wave(uint32_t v_fp, uint32_t v_fc, uint4 &goal_pos, uint32_t &goal_codes)
+{
+    uint32_t fp[8];
+    goal_codes = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         fp[k] = __builtin_amdgcn_readlane(v_fp, k);
-        fc[k] = __builtin_amdgcn_readlane(v_fc, k);
+        goal_codes |= __builtin_amdgcn_readlane(v_fc, k) << (4 * k);
     }
+    goal_pos = pack_pos(fp);
+}
+
+// menu_fn() yields the env's task-menu id; it is called after the MT state's loads are in flight, so a caller that
+// still has to fetch the id (cw_reset_kernel: from the header) overlaps that fetch with them.
+template <typename MenuFn>
+__device__ __forceinline__ CwResetOut reset_env_wave(const CwParams &P, int env, MenuFn menu_fn, uint32_t *lds_mt, int lane)
+{
+    CW_STAMP(env, 0);
+    const CwMtWave::Pending pend = CwMtWave::load_issue(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+    const uint32_t menu_id = menu_fn();
+    const CwMenuDev M = P.menus[menu_id];
+    CwMtWave mt;
+    mt.load_commit(lds_mt, pend, lane);
+    CW_STAMP(env, 1);
+
+    const uint32_t desired = draw_tasks_wave(mt, M);
+
+    CW_STAMP(env, 2);
+    const uint32_t v_tok = place_env_wave(P, env, mt, P.pool_k != 0, lane);
+    const uint32_t init_agent = __builtin_amdgcn_readlane(v_tok, 8);
+    uint32_t v_fp = lane < 8 ? v_tok : (uint32_t)CW_POS_GONE;    // tokens 0..7 are objects 0..7 = slots 0..7
+    uint32_t v_fc = lane < 8 ? (uint32_t)lane + 1u : 0u;
+    uint32_t ip[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) ip[k] = __builtin_amdgcn_readlane(v_tok, k);
+    const uint4 init_packed = pack_pos(ip);
+    CW_STAMP(env, 3);
+
+    const uint32_t agent = imagine_env_wave(P, mt, v_fp, v_fc, init_agent, init_agent, desired);    // (inside reset() the agent stands on its start cell)
 
     CW_STAMP(env, 4);
     const uint32_t draws = mt.draws();
     mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);   // coalesced write-back
     CW_STAMP(env, 5);
     CwResetOut r;
-    uint32_t goal_codes = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) goal_codes |= fc[k] << (4 * k);
     r.init_pos = init_packed;
     r.init_agent = init_agent;
-    r.goal_pos = pack_pos(fp);
-    r.goal_codes = goal_codes;
+    pack_goal_wave(v_fp, v_fc, r.goal_pos, r.goal_codes);
     r.goal_agent = agent;
     r.desired = desired;
     r.subset = M.reward_subset ? 1u : 0u;
@@ -988,6 +1011,113 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_masked_kerne
             } else {
                 (void)ipos; (void)gpos; (void)iagent; (void)gagent; (void)gcodes;
             }
+        }
+    }
+}
+
+// imagine_obs() of the envs the caller selects (cw_imagine_masked), against each env's RUNNING episode: a new goal state drawn from the episode's start
+// state (init_pos / init_agent), the agent's current cell (hdr) and `desired` -- the caller's uint16[N] task bits, or the env's own (hdr bytes 6-7) when
+// desired == NULL; bits at or above n_task_list are masked off, and 0 is legal: the goal is the start state and nothing is drawn.  Envs are dealt out
+// exactly as cw_reset_masked_kernel does it (a ballot over `epb` mask bytes, rank k -> wave k mod 4, MT state in LDS); mask == NULL selects every env.
+// commit: the goal records become the episode's (and, when `desired` was given, hdr bytes 6-7 and desired_out[env]); with paint_goal (pixel modes) the env's
+// desired_goal frame is repainted.  achieved, step_num, flags, the reward / done / episode outputs and counters[0..3] are never written: a new goal is
+// not a new episode.  out_frames / out_onehot (either may be NULL): the goal frame in the engine's raster at out_frames + env * frame_bytes, the goal
+// state at out_onehot[env][S][S][12]; rows of unselected envs are not touched.  The look-ahead records are neither read nor written: the host has
+// rewound the streams and dropped the records before it launches this on an engine that keeps them (cw_imagine_masked).
+// (The start state holds one of each object, a bread and a house among them, so every branch finds its object whatever the mask.)
+// PAINT: some frame is written (out_frames, or commit in a pixel mode).
+template <bool PAINT>
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_imagine_masked_kernel(CwParams P, const uint8_t *__restrict__ mask,
+                                                                                      const uint16_t *__restrict__ desired, int commit, int paint_goal,
+                                                                                      uint8_t *__restrict__ out_frames, uint8_t *__restrict__ out_onehot, int epb)
+{
+    __shared__ uint32_t s_mt[CW_RESET_WAVES][CW_MT_WORDS];
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
+    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
+        const int mine = base + lane;
+        const bool in_chunk = lane < epb && mine < P.n_envs;
+        const uint32_t v_sel = in_chunk ? (mask ? (uint32_t)mask[mine] : 1u) : 0u;
+        unsigned long long m = CW_BALLOT(v_sel != 0u);
+        for (int rank = 0; m; rank++) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
+            const int env = base + l;
+            const CwMtWave::Pending pend = CwMtWave::load_issue(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+            const uint4 v_h = P.hdr[env];                                 // in flight beside the MT state
+            const uint4 v_ip = P.init_pos[env];
+            const uint32_t init_agent = __builtin_amdgcn_readfirstlane((uint32_t)P.init_agent[env]);
+            const uint32_t v_des = desired ? (uint32_t)desired[env] : (v_h.y >> 16);
+            const uint32_t des = __builtin_amdgcn_readfirstlane(v_des) & P.task_mask;
+            const uint32_t cur_agent = agent_cell_of(P, __builtin_amdgcn_readfirstlane(v_h.x));
+            uint32_t ip[8];
+            unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(v_ip.x), __builtin_amdgcn_readfirstlane(v_ip.y), __builtin_amdgcn_readfirstlane(v_ip.z),
+                                  __builtin_amdgcn_readfirstlane(v_ip.w)), ip);
+            uint32_t v_fp = (uint32_t)CW_POS_GONE;                        // the start state: one of each object, lane = slot
+#pragma unroll
+            for (int k = 0; k < 8; k++) v_fp = (lane == k) ? ip[k] : v_fp;
+            uint32_t v_fc = lane < 8 ? (uint32_t)lane + 1u : 0u;
+            CwMtWave mt;
+            mt.load_commit(s_mt[wave_in_block], pend, lane);
+            const uint32_t gagent = imagine_env_wave(P, mt, v_fp, v_fc, init_agent, cur_agent, des);
+            if (mt.gens > 0) mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);      // (no draw taken: the stream is as it was)
+            uint4 gpos;
+            uint32_t gcodes;
+            pack_goal_wave(v_fp, v_fc, gpos, gcodes);
+            if (commit && lane == 0) {
+                P.goal_pos[env] = gpos;
+                P.goal_codes[env] = gcodes;
+                P.goal_agent[env] = (uint16_t)gagent;
+                if (desired) {
+                    ((uint32_t *)(P.hdr + env))[1] = (__builtin_amdgcn_readfirstlane(v_h.y) & 0xFFFFu) | (des << 16);
+                    P.desired_out[env] = (uint16_t)des;
+                }
+            }
+            uint32_t jp[8];
+            unpack_pos(gpos, jp);
+            if constexpr (PAINT) {
+                uint8_t *const own = (commit && paint_goal) ? P.desired_img + (size_t)env * P.frame_bytes : nullptr;
+                uint8_t *const ext = out_frames ? out_frames + (size_t)env * P.frame_bytes : nullptr;
+                if (ext || own) paint_state_frame(P, ext ? ext : own, jp, gcodes, gagent, 0u, lane, ext ? own : nullptr);
+            }
+            if (out_onehot) {
+                uint8_t *const oh = out_onehot + (size_t)env * P.ncell * 12u;
+                for (uint32_t cell = (uint32_t)lane; cell < (uint32_t)P.ncell; cell += CW_WAVE) {
+                    const uint32_t code = code_of(gcodes, slot_at(jp, cell));
+                    uint32_t bits = code ? (1u << (code - 1)) : 0u;
+                    if (cell == gagent) bits |= 1u << 8;                  // a goal state never holds an item
+                    *(u32x3_a4 *)(oh + (size_t)cell * 12u) = onehot_dwords(bits);
+                }
+            }
+        }
+    }
+}
+
+// sample_state() (ray.py:599-628; pooled: generate_fixed_initial_state(), :630-644) of the envs the caller selects, from each env's stream: the nine
+// cells (objects 0..7, agent) to out_cells[env][9], the format of cw_get_fixed_states.  Nothing else of the env is touched.  Envs are dealt out as in
+// cw_reset_masked_kernel; mask == NULL selects every env.
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_sample_state_masked_kernel(CwParams P, const uint8_t *__restrict__ mask, int pooled,
+                                                                                           uint16_t *__restrict__ out_cells, int epb)
+{
+    __shared__ uint32_t s_mt[CW_RESET_WAVES][CW_MT_WORDS];
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
+    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
+        const int mine = base + lane;
+        const bool in_chunk = lane < epb && mine < P.n_envs;
+        const uint32_t v_sel = in_chunk ? (mask ? (uint32_t)mask[mine] : 1u) : 0u;
+        unsigned long long m = CW_BALLOT(v_sel != 0u);
+        for (int rank = 0; m; rank++) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
+            const int env = base + l;
+            CwMtWave mt;
+            mt.load(s_mt[wave_in_block], P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+            const uint32_t v_tok = place_env_wave(P, env, mt, pooled != 0, lane);
+            mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+            if (lane < 9) out_cells[(size_t)env * 9 + lane] = (uint16_t)v_tok;
         }
     }
 }
@@ -2076,6 +2206,36 @@ hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const u
     const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
     if (obs_mode != 0) hipLaunchKernelGGL(cw_reset_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
     else hipLaunchKernelGGL(cw_reset_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
+    return hipGetLastError();
+}
+
+// imagine_obs() / sample_state() of the envs with mask[i] != 0 (NULL: all): one launch each, in cwk_launch_reset_masked's shape
+static int cw_masked_epb(const CwParams *P, const CwTuning *T)
+{
+    const int most = T->n_cu * T->reset_blocks_per_cu;
+    int epb = CW_WAVE;
+    while (epb > CW_RESET_WAVES && (P->n_envs + epb - 1) / epb < most) epb >>= 1;
+    return epb;
+}
+hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, const uint16_t *desired, int commit, int obs_mode,
+                                     uint8_t *out_frames, uint8_t *out_onehot, hipStream_t st)
+{
+    const int epb = cw_masked_epb(P, T);
+    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    const int paint_goal = obs_mode != 0;
+    if (out_frames || (commit && paint_goal))
+        hipLaunchKernelGGL(cw_imagine_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, desired, commit, paint_goal,
+                           out_frames, out_onehot, epb);
+    else
+        hipLaunchKernelGGL(cw_imagine_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, desired, commit, paint_goal,
+                           out_frames, out_onehot, epb);
+    return hipGetLastError();
+}
+hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st)
+{
+    const int epb = cw_masked_epb(P, T);
+    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    hipLaunchKernelGGL(cw_sample_state_masked_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, pooled, out_cells, epb);
     return hipGetLastError();
 }
 

@@ -292,6 +292,49 @@ class CraftingWorldEnv:
         self._rng_device_moved()
         return self.fixed_state_list
 
+    # -- goal drawing on the running episode (ray.py:220-299, 599-644) -------------------------------------------------------------------------
+    _imagine_one_hot = False                        # (the OneHot class returns the goal state itself, onehot.py:310)
+
+    def imagine_obs(self):
+        """ray.py:220-299: a goal for the running episode drawn from INIT_OBS_VECTOR, `self.desired_goal_vector` AS IT STANDS (a caller's edit of the
+        host array counts, as in the reference) and, for GoToHouse, the agent's current cell.  Advances np_random; env.desired_goal, INIT_OBS_VECTOR
+        and everything else of the env stay as they are (nothing is committed).  -> a NEW array per call: the goal image (Ray, Flat, AltObs) or the goal
+        state (OneHot); int64 with reference_dtypes=True, else uint8."""
+        if not self._has_reset:
+            raise AttributeError("'NoneType' object has no attribute 'copy'")      # (INIT_OBS_VECTOR is None before the first reset(), ray.py:225)
+        want = np.asarray(self.desired_goal_vector).reshape(-1)
+        bits = sum(1 << t for t in range(min(len(want), len(self.task_list))) if want[t] == 1)
+        self._rng_flush()
+        out = self._vec.imagine_obs(desired=np.array([bits], dtype=np.uint16), one_hot=self._imagine_one_hot)
+        img = out[0].cpu().numpy().astype(self._dtype)                            # (a copy: the engine's scratch is reused by the next call)
+        self._rng_device_moved()
+        return img
+
+    def _state_of_cells(self, cells):
+        S = self.STATE_W
+        state = np.zeros((S, S, 12), dtype=int)
+        for k in range(9):                          # channels 0-7 the objects, 8 the agent (ray.py:605-608)
+            state[int(cells[k]) // S, int(cells[k]) % S, k] = 1
+        return state, GridPos(int(cells[8]) // S, int(cells[8]) % S, self.STATE_W - 1, self.STATE_H - 1)
+
+    def sample_state(self):
+        """ray.py:599-628: a fresh placement, one of each object -> (state (S,S,12) int, agent position).  One shuffle of S*S tokens from np_random,
+        whatever fixed_init_state is; nothing else of the env moves.  (The engine draws it: after the first reset() only.)"""
+        self._rng_flush()
+        cells = self._vec.sample_states(pooled=False)[0].cpu().numpy()
+        self._rng_device_moved()
+        return self._state_of_cells(cells)
+
+    def generate_fixed_initial_state(self):
+        """ray.py:630-644: a copy of fixed_state_list[np_random.randint(fixed_init_state)] and its agent position.  fixed_init_state == 0: ValueError
+        (randint(0)), the stream stays where it was."""
+        if not self.fixed_init_state:
+            raise ValueError('high <= 0')
+        self._rng_flush()
+        cells = self._vec.sample_states(pooled=True)[0].cpu().numpy()
+        self._rng_device_moved()
+        return self._state_of_cells(cells)
+
     # -- np_random: one stream, two homes (the device's MT19937 record and a numpy RandomState on the host) -------------------------------------
     @property
     def np_random(self):
@@ -693,6 +736,8 @@ class CraftingWorldEnvOneHot(CraftingWorldEnv):
     """carftingworld_onehot.py:53-389: observations are the (S,S,12) one-hot states instead of
     images (observation/achieved_goal = current, desired_goal = imagine_obs final state,
     init_observation = state at reset); dynamics identical."""
+
+    _imagine_one_hot = True
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)

@@ -97,6 +97,29 @@ def reset_mask(num_envs, mask=None, indices=None):
     return out
 
 
+def desired_bits(num_envs, desired, n_tasks):
+    """The uint16 task masks cw_imagine_masked takes, built and validated on the host: -> np.uint16 [num_envs], bit t = task_list[t].  `desired` is either
+    those masks already (an integer array [num_envs], every value below 1 << n_tasks) or the reference's desired_goal_vector layout, one 0/1 row per
+    env: [num_envs, n_tasks] (a single row [1, n_tasks] or [n_tasks] is taken for a batch of one).  ValueError for any other shape, dtype or value."""
+    num_envs, n_tasks = int(num_envs), int(n_tasks)
+    d = np.asarray(desired)
+    if d.dtype != np.bool_ and not np.issubdtype(d.dtype, np.integer):
+        raise ValueError('desired must be a bool or integer array, got %s' % d.dtype)
+    if d.shape == (num_envs,) and not (num_envs == n_tasks == 1 and d.dtype == np.bool_):
+        d = d.astype(np.int64)
+        if ((d < 0) | (d >= (1 << n_tasks))).any():
+            raise ValueError('a desired mask outside 0 .. %d (%d tasks)' % ((1 << n_tasks) - 1, n_tasks))
+        return np.ascontiguousarray(d, dtype=np.uint16)
+    if num_envs == 1 and d.shape == (n_tasks,):
+        d = d.reshape(1, n_tasks)
+    if d.shape != (num_envs, n_tasks):
+        raise ValueError('desired must have shape (%d,) or (%d, %d), got %s' % (num_envs, num_envs, n_tasks, d.shape))
+    d = d.astype(np.int64)
+    if ((d != 0) & (d != 1)).any():
+        raise ValueError('a desired vector holds 0 and 1 only')
+    return np.ascontiguousarray((d << np.arange(n_tasks, dtype=np.int64)).sum(axis=1), dtype=np.uint16)
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -383,6 +406,77 @@ class CraftingWorldVecEnv:
         if self.host_outputs:
             self._sync()
         return self._observation()
+
+    def _select(self, mask, indices):
+        """mask / indices as reset_envs takes them -> the byte tensor the masked kernels read; None (every env) when neither is given."""
+        if mask is None and indices is None:
+            return None
+        if type(mask) is torch.Tensor and (mask.is_cuda or not self.host_outputs) and mask.device != self.device:
+            raise ValueError('the mask tensor is on %s, the envs are on %s' % (mask.device, self.device))
+        if (type(mask) is torch.Tensor and indices is None and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
+                and tuple(mask.shape) == (self.num_envs,) and mask.is_contiguous()):
+            return mask
+        if torch.is_tensor(mask):
+            mask = mask.cpu().numpy()
+        return torch.as_tensor(reset_mask(self.num_envs, mask, indices)).to(self.device)
+
+    def imagine_obs(self, mask=None, *, indices=None, desired=None, commit=False, out=None, one_hot=False):
+        """imagine_obs() (ray.py:220-299) of the selected envs against their RUNNING episode (cw_imagine_masked): a goal state drawn from each env's
+        start state, its task bits and -- for GoToHouse -- whether the agent stands on its start cell; each selected env's stream advances by its draws.
+        mask / indices select as in reset_envs (neither: every env).  desired: the task bits to imagine, a uint16 / int16 device tensor [N] handed over
+        in place, or anything desired_bits() packs ([N] masks, [N, len(task_list)] 0/1 rows); None: each env's own desired mask.
+        -> the goal frames uint8 [N, ...frame_shape] in the engine's raster (every obs_mode), or with one_hot=True the goal states uint8 [N,S,S,12]
+        (CraftingWorldEnvOneHot's return).  Rows of unselected envs are NOT written.  Without `out` the tensor is engine-owned scratch, reused by the next
+        call: copy what you keep.
+        commit=True is the batch relabel: the drawn goal (and `desired`, when given) becomes the episode's -- desired_mask, get_state()['goal_grid'],
+        one_hot(which='goal') and the desired_goal frames show it; achieved, step counts, reward, done and the counters are untouched.
+        On an engine that keeps look-ahead records (auto_reset=True on the device) the call rewinds every stream through the host first: correct, but off
+        the hot path and not capturable; relabel on an auto_reset=False engine with reset_envs(env.done)."""
+        m = self._select(mask, indices)
+        d = None
+        if desired is not None:
+            if (type(desired) is torch.Tensor and desired.is_cuda and desired.device == self.device and desired.dtype in (torch.uint16, torch.int16)
+                    and tuple(desired.shape) == (self.num_envs,) and desired.is_contiguous()):
+                d = desired
+            else:
+                if torch.is_tensor(desired):
+                    desired = desired.cpu().numpy()
+                d = torch.as_tensor(desired_bits(self.num_envs, desired, len(self.task_list)).view(np.int16)).to(self.device)
+        shape = (self.num_envs, self.size, self.size, 12) if one_hot else (self.num_envs,) + self.frame_shape
+        if out is None:
+            key = '_imagine_oh' if one_hot else '_imagine_frames'
+            out = getattr(self, key, None)
+            if out is None:
+                out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+                setattr(self, key, out)
+        elif not (type(out) is torch.Tensor and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
+                  and out.device == self.device):
+            raise ValueError('out must be a contiguous uint8 tensor of shape %s on %s' % (shape, self.device))
+        self._imagine_keepalive = (m, d)
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        L.check(self._lib.cw_imagine_masked(self._h, vp(m), vp(d), 1 if commit else 0, None if one_hot else vp(out), vp(out) if one_hot else None,
+                                            self._stream()), 'cw_imagine_masked', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
+
+    def sample_states(self, mask=None, *, indices=None, pooled=False):
+        """sample_state() (ray.py:599-628; pooled=True: generate_fixed_initial_state(), :630-644) from the selected envs' streams
+        (cw_sample_state_masked) -> uint16 tensor [N, 9]: the cells (row * S + col) of objects 0..7 and of the agent, fixed_states()' format.
+        Engine-owned scratch, reused by the next call; rows of unselected envs are not written.  Nothing of an env but its stream moves.
+        ValueError for pooled with fixed_init_state == 0 (the reference's randint(0))."""
+        if pooled and not self.fixed_init_state:
+            raise ValueError('sample_states(pooled=True) needs fixed_init_state > 0')
+        m = self._select(mask, indices)
+        out = getattr(self, '_sample_cells', None)
+        if out is None:
+            out = self._sample_cells = torch.zeros((self.num_envs, 9), dtype=torch.int16, device=self.device).view(torch.uint16)
+        self._imagine_keepalive = (m, None)
+        L.check(self._lib.cw_sample_state_masked(self._h, C.c_void_p(m.data_ptr()) if m is not None else None, 1 if pooled else 0,
+                                                 C.c_void_p(out.data_ptr()), self._stream()), 'cw_sample_state_masked', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -188,6 +188,36 @@ int cw_reset(cw_engine *e, cw_stream_t stream);
  * Only enqueues ONE kernel (cw_reset_masked_kernel) on `stream` -- no host synchronisation, no allocation -- so it can be captured into a HIP graph together
  * with cw_step / cw_step_many.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load. */
 int cw_reset_masked(cw_engine *e, const uint8_t *mask, cw_stream_t stream);
+
+/* --- imagine_obs() (ray.py:220-299) for the envs i with mask[i] != 0 (mask == NULL: every env), against each env's RUNNING episode: a new goal state drawn
+ * from the episode's start state (INIT_OBS_VECTOR), the task bits in `desired` and -- in the GoToHouse branch, ray.py:274-276 -- the agent's CURRENT cell:
+ * the goal's agent stands on the drawn house only while the agent stands on its start cell, else it stays on the start cell; the house is drawn either way.
+ * Each selected env's stream advances by the draws its goal took.
+ * mask, desired, out_frames, out_onehot: DEVICE pointers (with cw_config.host_outputs: or GPU-mapped host memory).
+ * desired: uint16[num_envs] task bits (bit t = task_list[t]; bits at or above len(task_list) are ignored), or NULL: each env's own desired mask.  0 is
+ *   legal: the goal is the start state and nothing is drawn.  (The start state holds one of each object, a bread and a house among them: every branch finds
+ *   its object whatever the mask.)
+ * commit != 0: the goal state becomes the episode's (cw_get_state goal_*, cw_export_onehot_of CW_STATE_GOAL, in the pixel modes the env's desired_goal
+ *   frame is repainted); when `desired` was given the env's desired mask (hdr bytes 6-7, cw_buffer_table.desired) takes it too.  achieved, step_num, the
+ *   flags, reward, done, the episode outputs and counters[0..3] are not written: a new goal is not a new episode.
+ * out_frames (or NULL): the goal frame of env i at out_frames + i * frame_bytes, in the engine's raster and in every obs_mode (as cw_render);
+ * out_onehot (or NULL): the goal state at out_onehot[i][S][S][12] (the OneHot variant's return, onehot.py:310).  Rows of unselected envs are not touched.
+ * commit == 0 with neither output is CW_ERR_INVALID (nothing to do).  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.
+ * Engines WITHOUT look-ahead records (auto_reset == 0, or host_outputs): enqueues ONE kernel (cw_imagine_masked_kernel) on `stream` -- no host synchronisation,
+ * no allocation -- and can be captured into a HIP graph with cw_step / cw_reset_masked.
+ * Engines that KEEP look-ahead records: their streams stand ahead of the envs' logical position, so the call first rewinds them as cw_generate_fixed_states
+ * does (cw_get_mt + cw_seed_mt: every record is dropped, the next refill covers the whole batch), then launches.  That is synchronous, moves every env's
+ * 2.5 KB of stream through the host and cannot be captured (CW_ERR_STATE while `stream` is capturing): it is OFF THE HOT PATH
+ * (not timed yet: tools/measure_imagine.py).  A relabelling loop belongs on an auto_reset == 0 engine with cw_step + cw_reset_masked(done), which computes the same episodes. */
+int cw_imagine_masked(cw_engine *e, const uint8_t *mask, const uint16_t *desired, int32_t commit,
+                      uint8_t *out_frames, uint8_t *out_onehot, cw_stream_t stream);
+
+/* --- sample_state() (ray.py:599-628; pooled != 0: generate_fixed_initial_state(), ray.py:630-644) for the envs i with mask[i] != 0 (NULL: every env), from
+ * each env's stream: one shuffle of S*S tokens (pooled: one randint(K) and that row of the env's pool).  out_cells: DEVICE uint16[num_envs][9] = the cells
+ * (row*S+col) of objects 0..7 and of the agent, the format of cw_get_fixed_states; rows of unselected envs are not touched, and nothing of an env but its
+ * stream moves.  pooled with fixed_init_state == 0 is CW_ERR_INVALID (the reference's randint(0) raises before any draw).  Look-ahead records, capture and
+ * call order as for cw_imagine_masked. */
+int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, uint16_t *out_cells, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,

@@ -9,6 +9,7 @@ through the C oracle; tests/test_hip_parity.py (gpu) replays them through the HI
 
     python tools/gen_golden.py            # regenerate every fixture
     python tools/gen_golden.py flat8_random onehot5_random   # only these
+    python tools/gen_golden.py imagine_ray5_alias            # an op-script fixture of kind 'imagine' (IMAGINE_SCENARIOS)
 """
 import json
 import os
@@ -244,7 +245,101 @@ def capture_alias(cls, kwargs, seed, policy_seed):
                 ops=ops, args=args, rows=rows)
 
 
+# kind 'imagine': the op script of tests/imagine_model.py (reset / step a / imagine_obs with or without an edited desired_goal_vector / sample_state /
+# generate_fixed_initial_state, draws by the caller in between) run through the reference class.  Per op the fixture holds the CRC, dtype and shape of
+# what was returned, the goal (or sampled) state as codes and agent cell -- small grids: the arrays too -- and np_random's (pos, CRC of key) afterwards.
+# name, class key, env name, kwargs
+IMAGINE_SCENARIOS = [
+    ('imagine_ray5_alias',      'ray',    'CraftingWorldEnvRay',    dict(size=(5, 5), max_steps=30)),
+    ('imagine_ray8_alias',      'ray',    'CraftingWorldEnvRay',    dict(size=(8, 8), max_steps=60, stacking=False,
+                                                                         selected_tasks=['MoveAxe', 'EatBread', 'GoToHouse', 'ChopTree'])),
+    ('imagine_ray6_alias',      'ray',    'CraftingWorldEnvRay',    dict(size=(6, 6), max_steps=40, fixed_init_state=3)),
+    ('imagine_ray21_alias',     'ray',    'CraftingWorldEnvRay',    dict(size=(21, 21))),
+    ('imagine_altobs5_alias',   'altobs', 'CraftingWorldEnvAltObs', dict(size=(5, 5), max_steps=30)),
+    ('imagine_onehot5_alias',   'onehot', 'CraftingWorldEnvOneHot', dict(size=(5, 5), max_steps=30)),
+    ('imagine_flat_alias',      'flat',   'CraftingWorldEnvFlat',   dict()),
+]
+# (the names end in _alias like the other op-script fixtures: tests/golden_util.fixture_names() lists the trajectory fixtures by leaving those out)
+
+
+def capture_imagine(cls, env_name, kwargs, seed):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import imagine_model as M
+    onehot = env_name == 'CraftingWorldEnvOneHot'
+
+    def run(policy_seed, burn):
+        rng = np.random.RandomState(seed)
+        rng.randint(1 << 30, size=burn)               # (where in its 624-draw generation the stream starts: searched, so that a call crosses the boundary)
+        st = rng.get_state()
+        env = make_ref_env(cls, rng, **kwargs)
+        seen, crossing = [], []
+        inner, inner_imagine = env.render, env.imagine_obs
+        env.render = lambda state=None, *a, **k: (seen.append(None if state is None else np.array(state)), inner(state, *a, **k))[1]
+
+        def imagine_obs():
+            before = int(env.np_random.get_state()[2])
+            ret = inner_imagine()
+            crossing.append(int(env.np_random.get_state()[2]) < before)
+            return ret
+        env.imagine_obs = imagine_obs
+
+        def probe(e, ret):
+            return ret if onehot else seen[-1]
+        ops, args = M.script(policy_seed)
+        rows, states = M.run_script(env, ops, args, probe)
+        return st, env, ops, args, rows, states, crossing[1:]      # (the first call is reset()'s own)
+
+    def search():
+        for policy_seed in range(40):
+            for burn in range(0, 624, 5):
+                got = run(policy_seed, burn)
+                ops, rows = got[2], got[4]
+                im = rows[ops == M.I_IMAGINE]
+                want = lambda t: (im[:, M.COL_DESIRED] >> t) & 1  # noqa: E731
+                ok = all(want(t).any() for t in range(9))
+                goto = want(M.T_GOTOHOUSE) == 1
+                first_off = np.flatnonzero(goto & (im[:, M.COL_HOME] == 0))
+                # GoToHouse off the start cell, and back on it after having moved
+                ok = ok and len(first_off) > 0 and (goto & (im[:, M.COL_HOME] == 1))[first_off[0]:].any()
+                ok = ok and (goto & (want(M.T_BUILDHOUSE) == 1) & (want(M.T_CHOPTREE) == 1)).any() and (im[:, M.COL_DESIRED] == 0).any()
+                resets = np.flatnonzero(ops == M.I_RESET)
+                imagines = np.flatnonzero(ops == M.I_IMAGINE)
+                assert len(got[6]) == len(imagines) + len(resets) - 1
+                # (reset() calls imagine_obs itself: leave those calls out)
+                calls = sorted([(i, 'r') for i in resets[1:]] + [(i, 'i') for i in imagines])
+                crossed = any(c for (_, kind), c in zip(calls, got[6]) if kind == 'i')
+                if ok and crossed:
+                    return (policy_seed,) + got
+        raise SystemExit('no policy seed meets the conditions')
+    policy_seed, st, env, ops, args, rows, states, _ = search()
+    im = rows[ops == M.I_IMAGINE]
+    assert (im[:, M.COL_FLAGS] == (M.F_NEW | M.F_GOAL_KEPT | M.F_INIT_KEPT)).all(), 'the reference returns a new image and leaves desired_goal / INIT_OBS_VECTOR alone'
+    kw = dict(kwargs)
+    if 'size' in kw:
+        kw['size'] = list(kw['size'])
+    eff = dict(kw, size=[env.STATE_W, env.STATE_H], max_steps=env.MAX_STEPS)
+    meta = dict(kwargs=eff, ctor_kwargs=kw, seed=seed, policy_seed=policy_seed, env=env_name, kind='imagine')
+    out = dict(meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8), key0=st[1].astype(np.uint32), pos0=np.int32(st[2]), ops=ops, args=args, rows=rows)
+    if env.STATE_W <= 8:
+        out['state_codes'] = np.array([c for c, _ in states], np.uint8)
+        out['state_agent'] = np.array([a for _, a in states], np.uint8)
+    return out
+
+
 def main():
+    only_ = set(sys.argv[1:])
+    if not only_ or any(n.startswith('imagine_') for n in only_):
+        classes_ = import_reference()
+        os.makedirs(OUT, exist_ok=True)
+        for k, (name, key, env_name, kwargs) in enumerate(IMAGINE_SCENARIOS):
+            if only_ and name not in only_:
+                continue
+            out = capture_imagine(classes_[key], env_name, kwargs, 9100 + k)
+            path = os.path.join(OUT, name + '.npz')
+            np.savez_compressed(path, **out)
+            print('%-24s ops=%4d  %6.1f KB' % (name, len(out['ops']), os.path.getsize(path) / 1024))
+        if only_ and all(n.startswith('imagine_') for n in only_):
+            return
     classes = import_reference()
     os.makedirs(OUT, exist_ok=True)
     for name, key, kwargs, seed, pseed in ALIAS_SCENARIOS:
