@@ -2197,7 +2197,9 @@ hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mo
 }
 
 // reset() of the envs with mask[i] != 0 (cw_reset_masked_kernel): one launch, nothing else.  A workgroup scans `epb` mask bytes per round and deals the
-// selected envs out to its four waves: 64 for batches that fill the card with such workgroups, down to 4 (one env per wave, cw_reset_kernel's shape) for small ones
+// selected envs out to its four waves: 64, halved down to 4 (one env per wave, cw_reset_kernel's shape) while the ceil(N / epb) chunks would not fill
+// most = n_cu * reset_blocks_per_cu workgroups; min(chunks, most) workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...  With
+// CW_TUNE_RESET_BLOCKS=4 on 256 CUs: 4 below 8 185 envs, 64 from 65 473 (tests/test_masked_shapes.py runs every width with the value 1)
 hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st)
 {
     const int most = T->n_cu * T->reset_blocks_per_cu;

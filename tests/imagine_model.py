@@ -25,12 +25,13 @@ def crc(a):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the model
-def imagine(init_codes, init_agent, cur_agent, desired, rs, gotohouse_ignores_position=False):
+def imagine(init_codes, init_agent, cur_agent, desired, rs, gotohouse_ignores_position=False, movesticks_ignores_agent=False):
     """ray.py:220-299 on cell codes.  init_codes (S,S): the episode's start state (INIT_OBS_VECTOR: one of each of the eight objects -- a bread and a house among them, so every
     branch finds its object -- and nothing held), init_agent its
     agent cell (r, c), cur_agent the env's agent_pos at the call, desired the task bits, rs the numpy RandomState drawn from (same calls, same order).
     -> (goal codes (S,S) uint8, goal agent (r, c)).  np.where walks row-major, as the reference's does.
-    gotohouse_ignores_position=True is a deliberately WRONG model (the agent always lands on the house): the tests show that the fixtures catch it."""
+    gotohouse_ignores_position=True is a deliberately WRONG model (the agent always lands on the house), movesticks_ignores_agent=True another (the sticks
+    may land on the agent's cell, as the axe and the hammer may): the tests show that the fixtures catch them."""
     g = np.array(init_codes, dtype=np.uint8)
     agent = (int(init_agent[0]), int(init_agent[1]))
     want = lambda t: (int(desired) >> t) & 1  # noqa: E731
@@ -48,7 +49,8 @@ def imagine(init_codes, init_agent, cur_agent, desired, rs, gotohouse_ignores_po
         r, c = np.where(g == STICKS)
         k = rs.randint(len(r))
         free = g == 0
-        free[agent] = False
+        if not movesticks_ignores_agent:
+            free[agent] = False
         fr, fc = np.where(free)
         j = rs.randint(len(fr))
         g[r[k], c[k]] = 0
@@ -183,6 +185,14 @@ def script(policy_seed, rounds=5):
     return np.array([s[0] for s in S], np.int8), np.array([s[1] for s in S], np.int64)
 
 
+def sweep_script(step_actions):
+    """the op list of a sweep fixture (tests/golden/sweep_imagine*_alias.npz): every desired mask 0..511 with the agent on its start cell, the steps
+    that take it off (the generator searches a seed at which they do, and asserts it), every mask again"""
+    S = [(I_RESET, 0)] + [(I_IMAGINE, m) for m in range(ALL_TASKS + 1)] + [(I_STEP, int(a)) for a in step_actions] + \
+        [(I_IMAGINE, m) for m in range(ALL_TASKS + 1)]
+    return np.array([s[0] for s in S], np.int8), np.array([s[1] for s in S], np.int64)
+
+
 def run_script(env, ops, args, state_probe=None):
     """-> (rows int64 [n_ops, COLS], states: the (codes, agent) of every I_IMAGINE / I_SAMPLE / I_GENFIXED op that returned, in order -- filled only with a
     state_probe(env, ret) -> one-hot state or None; without one the STATE_COLS stay 0)."""
@@ -251,6 +261,10 @@ def fixture_names():
     return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN, 'imagine_*.npz')))
 
 
+def sweep_fixture_names():
+    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN, 'sweep_imagine*_alias.npz')))
+
+
 def load(name):
     z = np.load(os.path.join(GOLDEN, name + '.npz'))
     d = {k: z[k] for k in z.files}
@@ -272,6 +286,7 @@ class ModelEnv:
     goal-drawing methods by the model above on a numpy RandomState that carries the oracle's stream across each call."""
 
     def __init__(self, env_name, key, pos, wrong=False, **kw):
+        """wrong: False, True / 'gotohouse' or 'movesticks' -- which deliberately wrong variant of imagine() to run"""
         from oracle import OracleEnv
         self._alt, self._onehot = env_name == 'CraftingWorldEnvAltObs', env_name == 'CraftingWorldEnvOneHot'
         kw = dict(kw)
@@ -316,7 +331,8 @@ class ModelEnv:
 
     def imagine_obs(self):
         bits = int(sum(int(b) << t for t, b in enumerate(self.desired_goal_vector[0])))
-        codes, agent = imagine(self._init[0], self._init[1], self._ora.state()['agent'], bits, self.np_random, gotohouse_ignores_position=self._wrong)
+        codes, agent = imagine(self._init[0], self._init[1], self._ora.state()['agent'], bits, self.np_random,
+                               gotohouse_ignores_position=self._wrong in (True, 'gotohouse'), movesticks_ignores_agent=self._wrong == 'movesticks')
         self._push_rng()
         self.last_state = one_hot(codes, agent)
         return self.last_state.astype(np.int64) if self._onehot else render(codes, agent, self._alt).astype(np.int64)

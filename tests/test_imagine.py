@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import imagine_model as M
+from masked_check import device_side as _device_side, model_imagine as _model, spread as _spread
 from oracle_replay import make_env, np_states, oracle_arrays, oracle_kw, same
 
 pytestmark = pytest.mark.gpu
@@ -23,22 +24,6 @@ CLASSES = {'CraftingWorldEnvRay': 'CraftingWorldEnv', 'CraftingWorldEnvFlat': 'C
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ helpers
-def _model(st, keys, pos, rows, desired):
-    """imagine_obs of engine rows `rows` by the model, from get_state() `st` and the streams (keys, pos) -> (goal_grid [n,S,S], goal_agent_rc [n,2], the
-    streams afterwards as numpy holds them)"""
-    S = st['grid'].shape[1]
-    g = np.zeros((len(rows), S, S), np.uint8)
-    a = np.zeros((len(rows), 2), np.uint8)
-    k2, p2 = np.empty((len(rows), 624), np.uint32), np.empty(len(rows), np.int32)
-    rs = np.random.RandomState()
-    for j, i in enumerate(rows):
-        rs.set_state(('MT19937', keys[i], int(pos[i]), 0, 0.0))
-        g[j], a[j] = M.imagine(st['init_grid'][i], st['init_agent_rc'][i], st['agent_rc'][i], int(desired[i]), rs)
-        s = rs.get_state()
-        k2[j], p2[j] = s[1], s[2]
-    return g, a, k2, p2
-
-
 def _frames_equal(got, rows, grids, agents, alt, what):
     """device frames got[rows] == the oracle's render of the model's goal states, in chunks (a 65 536-env frame array is 1.4 GB)"""
     for lo in range(0, len(rows), 4096):
@@ -48,31 +33,11 @@ def _frames_equal(got, rows, grids, agents, alt, what):
         same(what, rows[sl], have, want)
 
 
-def _device_side(env):
-    """clones of every device buffer a masked call must leave alone in unselected rows"""
-    out = {k: getattr(env, k).clone() for k in ('hdr', 'slot_pos', 'reward', 'done', 'achieved_mask', 'desired_mask', 'episode_length', 'episode_return')}
-    out['counters'] = env._counters_raw.clone()
-    if env.obs_mode != 'state':
-        out.update({k: v.clone() for k, v in env._observation().items() if k != 'achieved_goal'})
-    return out
-
-
 def _rows_equal(a, b, rows, tag):
     r = None if rows is None else torch.as_tensor(rows, device=a['hdr'].device)
     for k in a:
         x, y = (a[k], b[k]) if r is None or k == 'counters' else (a[k][r], b[k][r])
         assert torch.equal(x, y), tag + k
-
-
-def _spread(env, T, seed, moves_only=False):
-    gen = torch.Generator(device='cuda').manual_seed(seed)
-    acts = torch.randint(0, 4 if moves_only else 6, (T, env.num_envs), device='cuda', dtype=torch.uint8, generator=gen)
-    for t in range(T):
-        env.step(acts[t])
-        if not env.auto_reset:
-            env.reset_envs(env.done)
-    torch.cuda.synchronize()
-    return acts.cpu().numpy()
 
 
 def _state_equal(st, st0, rows, skip=()):

@@ -10,6 +10,7 @@ through the C oracle; tests/test_hip_parity.py (gpu) replays them through the HI
     python tools/gen_golden.py            # regenerate every fixture
     python tools/gen_golden.py flat8_random onehot5_random   # only these
     python tools/gen_golden.py imagine_ray5_alias            # an op-script fixture of kind 'imagine' (IMAGINE_SCENARIOS)
+    python tools/gen_golden.py sweep_imagine4_alias          # ... of kind 'imagine_sweep' (SWEEP_SCENARIOS): all 512 desired masks, on and off the start cell
 """
 import json
 import os
@@ -326,20 +327,61 @@ def capture_imagine(cls, env_name, kwargs, seed):
     return out
 
 
+# kind 'imagine_sweep': the same op format and runner, the script of imagine_model.sweep_script -- reset, imagine_obs for every desired mask 0..511 with
+# the agent on its start cell, steps that take it off, every mask again.  Dense grids on purpose: 4x4 has 7 free cells of 16.
+# name, class key, env name, kwargs, the steps
+SWEEP_SCENARIOS = [
+    ('sweep_imagine4_alias', 'ray', 'CraftingWorldEnvRay', dict(size=(4, 4), max_steps=30), (1, 2)),
+    ('sweep_imagine5_alias', 'ray', 'CraftingWorldEnvRay', dict(size=(5, 5), max_steps=30), (2, 3, 3)),
+]
+
+
+def capture_sweep(cls, env_name, kwargs, steps, seed0):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import imagine_model as M
+    ops, args = M.sweep_script(steps)
+    for seed in range(seed0, seed0 + 200):
+        rng = np.random.RandomState(seed)
+        st = rng.get_state()
+        env = make_ref_env(cls, rng, **kwargs)
+        seen = []
+        inner = env.render
+        env.render = lambda state=None, *a, **k: (seen.append(None if state is None else np.array(state)), inner(state, *a, **k))[1]
+        rows, states = M.run_script(env, ops, args, lambda e, ret: seen[-1])
+        im, stp = rows[ops == M.I_IMAGINE], rows[ops == M.I_STEP]
+        if (im[512:, M.COL_HOME] == 0).all() and (stp[:, 1] == 0).all():      # the steps left the start cell, and the episode goes on
+            break
+    else:
+        raise SystemExit('no seed at which the steps leave the start cell')
+    assert (im[:512, M.COL_HOME] == 1).all() and (im[512:, M.COL_HOME] == 0).all(), 'every mask on the start cell, then every mask off it'
+    assert np.array_equal(im[:512, M.COL_DESIRED], np.arange(512)) and np.array_equal(im[512:, M.COL_DESIRED], np.arange(512))
+    assert (im[:, M.COL_FLAGS] == (M.F_NEW | M.F_GOAL_KEPT | M.F_INIT_KEPT)).all()
+    assert len(states) == 1024
+    kw = dict(kwargs, size=list(kwargs['size']))
+    meta = dict(kwargs=kw, ctor_kwargs=kw, seed=seed, steps=list(steps), env=env_name, kind='imagine_sweep')
+    return dict(meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8), key0=st[1].astype(np.uint32), pos0=np.int32(st[2]), ops=ops, args=args,
+                rows=rows, state_codes=np.array([c for c, _ in states], np.uint8), state_agent=np.array([a for _, a in states], np.uint8))
+
+
 def main():
     only_ = set(sys.argv[1:])
-    if not only_ or any(n.startswith('imagine_') for n in only_):
+    # the op-script kinds of tests/imagine_model.py: (name prefix, scenarios, capture of scenario k -> the fixture's arrays)
+    scripted = [('sweep_', SWEEP_SCENARIOS, lambda cl, k, sc: capture_sweep(cl[sc[1]], sc[2], sc[3], sc[4], 9300 + 1000 * k)),
+                ('imagine_', IMAGINE_SCENARIOS, lambda cl, k, sc: capture_imagine(cl[sc[1]], sc[2], sc[3], 9100 + k))]
+    for prefix, scenarios, capture_k in scripted:
+        if only_ and not any(n.startswith(prefix) for n in only_):
+            continue
         classes_ = import_reference()
         os.makedirs(OUT, exist_ok=True)
-        for k, (name, key, env_name, kwargs) in enumerate(IMAGINE_SCENARIOS):
-            if only_ and name not in only_:
+        for k, sc in enumerate(scenarios):
+            if only_ and sc[0] not in only_:
                 continue
-            out = capture_imagine(classes_[key], env_name, kwargs, 9100 + k)
-            path = os.path.join(OUT, name + '.npz')
+            out = capture_k(classes_, k, sc)
+            path = os.path.join(OUT, sc[0] + '.npz')
             np.savez_compressed(path, **out)
-            print('%-24s ops=%4d  %6.1f KB' % (name, len(out['ops']), os.path.getsize(path) / 1024))
-        if only_ and all(n.startswith('imagine_') for n in only_):
-            return
+            print('%-24s ops=%4d  seed=%d  %6.1f KB' % (sc[0], len(out['ops']), json.loads(bytes(out['meta']).decode())['seed'], os.path.getsize(path) / 1024))
+    if only_ and all(n.startswith(tuple(p for p, _, _ in scripted)) for n in only_):
+        return
     classes = import_reference()
     os.makedirs(OUT, exist_ok=True)
     for name, key, kwargs, seed, pseed in ALIAS_SCENARIOS:
