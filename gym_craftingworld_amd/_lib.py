@@ -79,6 +79,10 @@ ABI = {
     'cw_reset_masked': (C.c_int, [_VP, _VP, _VP]),
     'cw_imagine_masked': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
     'cw_sample_state_masked': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP]),
+    'cw_snapshot_reserve': (C.c_int, [_VP, C.c_int32]),
+    'cw_snapshot_row_bytes': (C.c_size_t, [_VP]),
+    'cw_snapshot_save': (C.c_int, [_VP, _VP, _VP]),
+    'cw_snapshot_load': (C.c_int, [_VP, _VP, C.c_int32, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
@@ -123,6 +127,7 @@ cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variabl
 
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
 CWH_CKPT_SECTIONS = 22
+CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 
 # the engine's HIP-free host logic (csrc/cw_host.h: MT19937 state conversion, DLPack, dense views, checkpoint sizes, the guard's decisions), exported for
 # the tests of the host logic -- the same table binds libcw_host_asan.so, the ASAN/UBSAN build of cw_host.cpp alone (bind_host_helpers)
@@ -135,6 +140,9 @@ HOST_HELPERS = {
     'cwh_dlpack_make': (_VP, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     'cwh_slots_to_grid': (None, [_VP, C.c_uint32, C.c_int, _VP]),
     'cwh_ckpt_section_bytes': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    'cwh_snapshot_section_bytes': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)]),
+    'cwh_snapshot_row_in_bank': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),
     'cwh_sweep_periods': (None, [C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

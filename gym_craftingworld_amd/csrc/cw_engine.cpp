@@ -25,6 +25,8 @@ hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const u
 hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, const uint16_t *desired, int commit, int obs_mode,
                                      uint8_t *out_frames, uint8_t *out_onehot, hipStream_t st);
 hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st);
+hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st);
+hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st);
 hipError_t cwk_launch_pool(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_seed(const CwParams *P, const uint32_t *seeds_dev, hipStream_t st);
 hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, int paint_dirty, unsigned long long idle_ticks,
@@ -86,6 +88,9 @@ struct cw_engine {
     int32_t *host_actions = nullptr;
     std::vector<CwMenuDev> menus;
     uint32_t *seed_scratch = nullptr;  // [N] device: seeds of cw_seed_int
+    void *bank = nullptr;              // the snapshot bank's one allocation (cw_snapshot_reserve), or null: none reserved
+    CwBank B{};                        // ... its sections (cw_host.cpp: cwh_snapshot_section_bytes)
+    size_t bank_row_bytes = 0;
     int n = 0, S = 0, ncell = 0, K = 0;
     // resident stepper of the single-env loop (cw_step_resident; cw_kernels.hip: cw_resident_kernel)
     CwResident *res = nullptr;         // pinned coherent host memory, or null (engine not eligible)
@@ -609,6 +614,7 @@ int cw_destroy(cw_engine *e)
     if (e->last_work) (void)hipEventDestroy(e->last_work);
     for (auto &smp : e->guard_ring) for (hipEvent_t ev : smp.ev) if (ev) (void)hipEventDestroy(ev);
     for (void *p : e->allocs) (void)hipFree(p);
+    if (e->bank) (void)hipFree(e->bank);
     for (void *p : e->host_allocs) (void)hipHostFree(p);
     delete e;
     return CW_OK;
@@ -786,6 +792,91 @@ int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, ui
     if (rc != CW_OK) return rc;
     if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
     HIP_TRY(cwk_launch_sample_state_masked(&e->P, &e->tune, mask, pooled != 0, out_cells, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// ------------------------------------------------------------------------------ snapshot bank
+// The bank is one allocation of the engine's, outside every checkpoint blob; cw_checkpoint_load, cw_seed_* and cw_generate_fixed_states leave it alone (a row
+// is self-contained: it carries its own stream, ring and pool row).  Re-allocating drops every saved row: the new bank's valid bytes are zero.
+static void bank_free(cw_engine *e)
+{
+    if (e->bank) (void)hipFree(e->bank);
+    e->bank = nullptr;
+    e->B = CwBank{};
+    e->bank_row_bytes = 0;
+}
+
+int cw_snapshot_reserve(cw_engine *e, int32_t rows)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: null engine");
+    if (rows < 0) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: rows = %d must be >= 0", rows);
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    HIP_TRY(quiesce(e));                              // (the engine's own work: a save or load in flight uses the bank about to go)
+    bank_free(e);
+    if (rows == 0) return CW_OK;
+    size_t bytes[CWH_SNAP_SECTIONS], at[CWH_SNAP_SECTIONS];
+    uint64_t total = 0, row_bytes = 0;
+    cwh_snapshot_section_bytes(rows, e->K, e->P.lookahead ? CW_LA_DEPTH : 0, bytes, at, &total, &row_bytes);
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CW_ERR_HIP, "cw_snapshot_reserve: no device memory for %d rows of %llu bytes", rows, (unsigned long long)row_bytes);
+    }
+    if (hipMemsetAsync((char *)p + at[CWH_SNAP_VALID], 0, bytes[CWH_SNAP_VALID], e->aux) != hipSuccess || hipStreamSynchronize(e->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return fail(CW_ERR_HIP, "cw_snapshot_reserve: clearing the valid bytes failed");
+    }
+    char *const b = (char *)p;
+    CwBank &B = e->B;
+    B.hdr = (uint4 *)(b + at[CWH_SNAP_HDR]); B.pos = (uint4 *)(b + at[CWH_SNAP_POS]);
+    B.init_pos = (uint4 *)(b + at[CWH_SNAP_INIT_POS]); B.goal_pos = (uint4 *)(b + at[CWH_SNAP_GOAL_POS]);
+    B.goal_codes = (uint32_t *)(b + at[CWH_SNAP_GOAL_CODES]); B.ep_no = (int32_t *)(b + at[CWH_SNAP_EP_NO]);
+    B.init_agent = (uint16_t *)(b + at[CWH_SNAP_INIT_AGENT]); B.goal_agent = (uint16_t *)(b + at[CWH_SNAP_GOAL_AGENT]);
+    B.mt = (uint32_t *)(b + at[CWH_SNAP_MT]); B.mt_idx = (int32_t *)(b + at[CWH_SNAP_MT_IDX]);
+    B.nx_init_pos = (uint4 *)(b + at[CWH_SNAP_NX_INIT_POS]); B.nx_goal_pos = (uint4 *)(b + at[CWH_SNAP_NX_GOAL_POS]);
+    B.nx_misc = (uint4 *)(b + at[CWH_SNAP_NX_MISC]); B.nx_ctl = (uint32_t *)(b + at[CWH_SNAP_NX_CTL]);
+    B.pool = (uint16_t *)(b + at[CWH_SNAP_POOL]); B.valid = (uint8_t *)(b + at[CWH_SNAP_VALID]);
+    B.rows = rows;
+    e->bank = p;
+    e->bank_row_bytes = (size_t)row_bytes;
+    return CW_OK;
+}
+
+size_t cw_snapshot_row_bytes(const cw_engine *e)
+{
+    if (!e) { (void)fail(CW_ERR_INVALID, "cw_snapshot_row_bytes: null engine"); return 0; }
+    return e->bank ? e->bank_row_bytes : 0;
+}
+
+// Both only enqueue ONE kernel: no wait, no allocation, the same call whether it runs or is captured.
+int cw_snapshot_save(cw_engine *e, const int32_t *rows, cw_stream_t stream)
+{
+    if (!e || !rows) return fail(CW_ERR_INVALID, "cw_snapshot_save: null %s", !e ? "engine" : "rows");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_snapshot_save called before cw_reset");
+    if (!e->bank) return fail(CW_ERR_STATE, "cw_snapshot_save: no bank reserved (cw_snapshot_reserve)");
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_snapshot_save(&e->P, &e->tune, &e->B, rows, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_stream_t stream)
+{
+    if (!e || !rows) return fail(CW_ERR_INVALID, "cw_snapshot_load: null %s", !e ? "engine" : "rows");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_snapshot_load called before cw_reset");
+    if (!e->bank) return fail(CW_ERR_STATE, "cw_snapshot_load: no bank reserved (cw_snapshot_reserve)");
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_snapshot_load(&e->P, &e->tune, &e->B, rows, with_stream != 0, e->obs_mode, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

@@ -157,6 +157,24 @@ int cwh_ckpt_section_bytes(int64_t n, int32_t k, int32_t la_depth, size_t *sizes
     return CWH_CKPT_SECTIONS;
 }
 
+// ------------------------------------------------------------------------------ snapshot bank sections (cw_engine.cpp: cw_snapshot_reserve pairs them with pointers)
+int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t *sizes, size_t *offsets, uint64_t *total, uint64_t *row_bytes)
+{
+    const size_t R = rows > 0 ? (size_t)rows : 0, K = k > 0 ? (size_t)k : 0, D = la_depth > 0 ? (size_t)la_depth : 0, la = D ? 1 : 0;
+    const size_t per_row[CWH_SNAP_SECTIONS] = {16, 16, 16, 16, 4, 4, 2, 2, CWH_MT_N * 4, 4, D * 16, D * 16, D * 16, la * 4, K * 9 * 2, 1};
+    uint64_t at = 0, row = 0;
+    for (int i = 0; i < CWH_SNAP_SECTIONS; i++) {
+        if (sizes) sizes[i] = per_row[i] * R;
+        if (offsets) offsets[i] = (size_t)at;
+        at += (per_row[i] * R + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
+        row += per_row[i];
+    }
+    if (total) *total = at;
+    if (row_bytes) *row_bytes = row;
+    return CWH_SNAP_SECTIONS;
+}
+int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity) { return cwh_snapshot_row_ok(row, capacity); }
+
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule
 static double period_ns(int32_t sweep_waves, double tb_per_s) { return (double)sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }
 void cwh_sweep_periods(double rate, int32_t sweep_waves, double head_notch, double busy_notch, int32_t *period16, int32_t *period16_head, int32_t *period16_busy)

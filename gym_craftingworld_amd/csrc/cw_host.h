@@ -30,6 +30,25 @@ void cwh_slots_to_grid(const uint16_t *pos, uint32_t codes, int ncell, uint8_t *
 #define CWH_CKPT_SECTIONS 22
 int cwh_ckpt_section_bytes(int64_t n, int32_t k, int32_t la_depth, size_t *sizes, uint64_t *total);
 
+// ---- snapshot bank (cw_snapshot_reserve / _save / _load): `rows` rows in device memory, each of which holds one env completely, laid out like the engine --
+// one array per field, a row's MT words contiguous, the look-ahead ring as [la_depth][rows].  The sections in bank order: hdr, pos, init_pos, goal_pos (16 B a
+// row), goal_codes, ep_no (4), init_agent, goal_agent (2), mt (624 x 4), mt_idx (4), nx_init_pos, nx_goal_pos, nx_misc (la_depth x 16), nx_ctl (4 with a ring,
+// else 0), pool (k x 9 x 2), valid (1: the row has been saved since the last reserve).  Every section starts on a CWH_SNAP_ALIGN boundary.
+// Writes CWH_SNAP_SECTIONS sizes and offsets (either may be null), returns how many; *total = the allocation, *row_bytes = what one row holds.
+#define CWH_SNAP_SECTIONS 16
+#define CWH_SNAP_ALIGN 256
+enum { CWH_SNAP_HDR = 0, CWH_SNAP_POS, CWH_SNAP_INIT_POS, CWH_SNAP_GOAL_POS, CWH_SNAP_GOAL_CODES, CWH_SNAP_EP_NO, CWH_SNAP_INIT_AGENT, CWH_SNAP_GOAL_AGENT,
+       CWH_SNAP_MT, CWH_SNAP_MT_IDX, CWH_SNAP_NX_INIT_POS, CWH_SNAP_NX_GOAL_POS, CWH_SNAP_NX_MISC, CWH_SNAP_NX_CTL, CWH_SNAP_POOL, CWH_SNAP_VALID };
+int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t *sizes, size_t *offsets, uint64_t *total, uint64_t *row_bytes);
+// THE row check of the snapshot kernels, shared by host and device: a row number from the caller's array may index the bank only if this says so
+#if defined(__HIP__) || defined(__HIPCC__)
+#define CWH_HOST_DEVICE __host__ __device__
+#else
+#define CWH_HOST_DEVICE
+#endif
+static inline CWH_HOST_DEVICE int cwh_snapshot_row_ok(int32_t row, int32_t capacity) { return row >= 0 && row < capacity; }
+int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity);       // (the same, exported for the CPU tests)
+
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).
 typedef struct cwh_guard {

@@ -11,6 +11,8 @@
 //                     reset by a wave, and its three frames are painted on the spot (no sweep of the arrays).
 //   cw_imagine_masked_kernel  imagine_obs() of the selected envs against their RUNNING episode (a new goal state, optionally committed), dealt out the same way;
 //                     cw_sample_state_masked_kernel: sample_state() / generate_fixed_initial_state() from the selected envs' streams.
+//   cw_snapshot_save_kernel / cw_snapshot_load_kernel  envs into rows of the engine's device-resident snapshot bank and back (restore, fork), dealt out the
+//                     same way by a device array of row numbers.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -23,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cw_host.h"
 #include "cw_layout.h"
 #include "cw_mt.h"
 
@@ -1118,6 +1121,151 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_sample_state_maske
             const uint32_t v_tok = place_env_wave(P, env, mt, pooled != 0, lane);
             mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
             if (lane < 9) out_cells[(size_t)env * 9 + lane] = (uint16_t)v_tok;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------ snapshot bank
+// cw_snapshot_save / cw_snapshot_load: envs into rows of the engine's bank (CwBank, cw_layout.h) and rows back into envs, driven by a device array
+// rows[N] -- bank row rows[i] for env i, negative: env i takes no part.  Dealt out like the masked kernels: a workgroup ballots `epb` entries for "takes part
+// and passes the row check" (cwh_snapshot_row_ok: the ONLY way a row number becomes an index; on load also the row's valid byte, read behind that check),
+// rank k goes to wave k mod 4, a wave copies one env at a time, grid-stride over the chunks.  An env whose row number is >= 0 but fails the check is left
+// exactly as it is and counted in counters[6], once (by wave 0 of the workgroup that balloted it).  No LDS.
+// An env is two groups.  The EPISODE: hdr, pos, init_pos, init_agent, goal_pos, goal_codes, goal_agent, ep_no -- uniform loads, lane 0 stores.  Its SOURCE OF
+// FUTURE EPISODES: the MT19937 words (156 uint4 per env: 2 496 B is a multiple of 16 on both sides) and index, on engines that keep look-ahead records the
+// whole ring verbatim (the stream in HBM stands ahead of the env's logical position by the waiting records: copied together they stay consistent, and
+// cw_get_mt, the refill and the checkpoints need not know of these kernels), the pool row, and the menu id (hdr byte 3).
+__device__ __forceinline__ CwBank engine_as_bank(const CwParams &P)
+{
+    CwBank E;
+    E.hdr = P.hdr; E.pos = P.pos; E.init_pos = P.init_pos; E.goal_pos = P.goal_pos;
+    E.goal_codes = P.goal_codes; E.ep_no = P.ep_no; E.init_agent = P.init_agent; E.goal_agent = P.goal_agent;
+    E.mt = P.mt; E.mt_idx = P.mt_idx;
+    E.nx_init_pos = P.nx_init_pos; E.nx_goal_pos = P.nx_goal_pos; E.nx_misc = P.nx_misc; E.nx_ctl = P.nx_ctl;
+    E.pool = P.pool; E.valid = nullptr; E.rows = P.n_envs;
+    return E;
+}
+// row `si` of s -> row `di` of d: stream, ring and pool, by the wave
+__device__ __forceinline__ void copy_stream_group(const CwParams &P, const CwBank &d, size_t di, const CwBank &s, size_t si, int lane)
+{
+    const uint4 *const ms = (const uint4 *)(s.mt + si * CW_MT_WORDS);
+    uint4 *const md = (uint4 *)(d.mt + di * CW_MT_WORDS);
+    constexpr int TAIL = CW_MT_WORDS / 4 - 2 * CW_WAVE;               // 156 = 64 + 64 + 28
+    const uint4 a = ms[lane], b = ms[lane + CW_WAVE];
+    const uint4 c = lane < TAIL ? ms[lane + 2 * CW_WAVE] : make_uint4(0, 0, 0, 0);
+    const int32_t v_idx = s.mt_idx[si];
+    md[lane] = a;
+    md[lane + CW_WAVE] = b;
+    if (lane < TAIL) md[lane + 2 * CW_WAVE] = c;
+    if (lane == 0) d.mt_idx[di] = v_idx;
+    if (P.lookahead) {
+        if (lane < CW_LA_DEPTH) {                                     // the ring, slot = lane
+            const size_t as = (size_t)lane * s.rows + si, ad = (size_t)lane * d.rows + di;
+            const uint4 ip = s.nx_init_pos[as], gp = s.nx_goal_pos[as], mi = s.nx_misc[as];
+            d.nx_init_pos[ad] = ip;
+            d.nx_goal_pos[ad] = gp;
+            d.nx_misc[ad] = mi;
+        }
+        const uint32_t v_ctl = s.nx_ctl[si];
+        if (lane == 0) d.nx_ctl[di] = v_ctl;                          // (head slot and the QUEUED bit)
+    }
+    const int pool_words = P.pool_k * 9;
+    for (int j = lane; j < pool_words; j += CW_WAVE) d.pool[di * pool_words + j] = s.pool[si * pool_words + j];
+}
+
+// bank row rows[i] <- env i.  Writes nothing of the engine (but counters[6] for a row number at or above the capacity).  Two envs that name the same row leave
+// an unspecified mix of the two there.  The row's valid byte is written after its data, by the same wave.
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_snapshot_save_kernel(CwParams P, CwBank B, const int32_t *__restrict__ rows, int epb)
+{
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
+    const CwBank E = engine_as_bank(P);
+    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
+        const int mine = base + lane;
+        const bool in_chunk = lane < epb && mine < P.n_envs;
+        const int32_t v_row = in_chunk ? rows[mine] : -1;
+        const bool v_ok = cwh_snapshot_row_ok(v_row, B.rows) != 0;
+        unsigned long long m = CW_BALLOT(v_ok);
+        const unsigned long long skipped = CW_BALLOT(v_row >= 0 && !v_ok);
+        if (skipped && wave_in_block == 0 && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
+        for (int rank = 0; m; rank++) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
+            const int env = base + l;
+            const size_t row = (size_t)__builtin_amdgcn_readlane(v_row, l);       // (passed the check in lane l)
+            const uint4 h = P.hdr[env], ps = P.pos[env], ip = P.init_pos[env], gp = P.goal_pos[env];
+            const uint32_t gc = P.goal_codes[env];
+            const int32_t ep = P.ep_no[env];
+            const uint16_t ia = P.init_agent[env], ga = P.goal_agent[env];
+            copy_stream_group(P, B, row, E, (size_t)env, lane);
+            if (lane == 0) {
+                B.hdr[row] = h; B.pos[row] = ps; B.init_pos[row] = ip; B.goal_pos[row] = gp;
+                B.goal_codes[row] = gc; B.ep_no[row] = ep; B.init_agent[row] = ia; B.goal_agent[row] = ga;
+            }
+            __threadfence();                                                      // the row's data, then its valid byte
+            if (lane == 0) B.valid[row] = 1;
+        }
+    }
+}
+
+// env i <- bank row rows[i]; any number of envs may name the same row (the fork).  A row at or above the capacity, or one never saved since the last reserve,
+// is skipped and counted.  with_stream: both groups -- the env becomes an exact twin of the saved one.  Without: the episode only; the env keeps its own
+// stream, ring, pool and menu id (everything else in hdr, the subset-reward flag and the success count among it, is the row's), plays the saved episode to
+// its end and goes on with episodes of its own.  achieved_out / desired_out take the restored masks, as after cw_reset_masked; PAINT (pixel modes): the env's
+// obs (with the held item), init_obs and desired_goal frames by the wave, so that all three are right without a step.  reward, done, the episode outputs,
+// terminal_obs and counters[0..5] are not written: a restore is not a step and not a finished episode.
+template <bool PAINT>
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_snapshot_load_kernel(CwParams P, CwBank B, const int32_t *__restrict__ rows, int with_stream,
+                                                                                     int epb)
+{
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
+    const CwBank E = engine_as_bank(P);
+    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
+        const int mine = base + lane;
+        const bool in_chunk = lane < epb && mine < P.n_envs;
+        const int32_t v_row = in_chunk ? rows[mine] : -1;
+        const bool v_in = cwh_snapshot_row_ok(v_row, B.rows) != 0;
+        uint32_t v_valid = 0u;
+        if (v_in) v_valid = B.valid[v_row];                                       // (an address only behind the check)
+        const bool v_ok = v_valid != 0u;
+        unsigned long long m = CW_BALLOT(v_ok);
+        const unsigned long long skipped = CW_BALLOT(v_row >= 0 && !v_ok);
+        if (skipped && wave_in_block == 0 && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
+        for (int rank = 0; m; rank++) {
+            const int l = __builtin_ctzll(m);
+            m &= m - 1;
+            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
+            const int env = base + l;
+            const size_t row = (size_t)__builtin_amdgcn_readlane(v_row, l);       // (passed the check in lane l)
+            uint4 h = B.hdr[row];
+            const uint4 ps = B.pos[row], ip = B.init_pos[row], gp = B.goal_pos[row];
+            const uint32_t gc = B.goal_codes[row];
+            const int32_t ep = B.ep_no[row];
+            const uint32_t ia = B.init_agent[row], ga = B.goal_agent[row];
+            if (with_stream) copy_stream_group(P, E, (size_t)env, B, row, lane);
+            else h.x = (h.x & 0x00FFFFFFu) | (P.hdr[env].x & 0xFF000000u);        // (the env's own menu id)
+            if (lane == 0) {
+                P.hdr[env] = h; P.pos[env] = ps; P.init_pos[env] = ip; P.goal_pos[env] = gp;
+                P.goal_codes[env] = gc; P.ep_no[env] = ep; P.init_agent[env] = (uint16_t)ia; P.goal_agent[env] = (uint16_t)ga;
+                P.achieved_out[env] = (uint16_t)(h.y & 0xFFFFu);
+                P.desired_out[env] = (uint16_t)(h.y >> 16);
+            }
+            if constexpr (PAINT) {
+                const size_t off = (size_t)env * P.frame_bytes;
+                const uint32_t hx = __builtin_amdgcn_readfirstlane(h.x);
+                uint32_t jp[8];
+                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(ps.x), __builtin_amdgcn_readfirstlane(ps.y), __builtin_amdgcn_readfirstlane(ps.z),
+                                      __builtin_amdgcn_readfirstlane(ps.w)), jp);
+                paint_state_frame(P, P.obs + off, jp, __builtin_amdgcn_readfirstlane(h.w), agent_cell_of(P, hx), hold_of(hx), lane);
+                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(ip.x), __builtin_amdgcn_readfirstlane(ip.y), __builtin_amdgcn_readfirstlane(ip.z),
+                                      __builtin_amdgcn_readfirstlane(ip.w)), jp);
+                paint_state_frame(P, P.init_img + off, jp, CW_CODES_INITIAL, __builtin_amdgcn_readfirstlane(ia), 0u, lane);
+                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(gp.x), __builtin_amdgcn_readfirstlane(gp.y), __builtin_amdgcn_readfirstlane(gp.z),
+                                      __builtin_amdgcn_readfirstlane(gp.w)), jp);
+                paint_state_frame(P, P.desired_img + off, jp, __builtin_amdgcn_readfirstlane(gc), __builtin_amdgcn_readfirstlane(ga), 0u, lane);
+            }
         }
     }
 }
@@ -2238,6 +2386,23 @@ hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, 
     const int epb = cw_masked_epb(P, T);
     const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
     hipLaunchKernelGGL(cw_sample_state_masked_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, pooled, out_cells, epb);
+    return hipGetLastError();
+}
+
+// snapshot save / load of the envs with rows[i] >= 0: one launch each, in the masked kernels' shape (cw_masked_epb, cw_reset_grid)
+hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st)
+{
+    const int epb = cw_masked_epb(P, T);
+    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    hipLaunchKernelGGL(cw_snapshot_save_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, epb);
+    return hipGetLastError();
+}
+hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st)
+{
+    const int epb = cw_masked_epb(P, T);
+    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    if (obs_mode != 0) hipLaunchKernelGGL(cw_snapshot_load_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
+    else hipLaunchKernelGGL(cw_snapshot_load_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
     return hipGetLastError();
 }
 

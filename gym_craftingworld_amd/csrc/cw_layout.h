@@ -73,6 +73,24 @@ struct CwResident {
     uint32_t pad1[30];
 };
 
+// The SNAPSHOT BANK of an engine (cw_snapshot_reserve): `rows` rows in device memory, each of which can hold one env completely -- the arrays of CwParams
+// that make up an env, with `rows` in the place of n_envs (the ring as [CW_LA_DEPTH][rows], the pool as [rows][K][9]), plus one byte per row: the row has
+// been saved since the last reserve.  One allocation; the sections' sizes and offsets are cw_host.cpp's (cwh_snapshot_section_bytes).  The snapshot kernels
+// also describe the ENGINE's own arrays with this struct (rows = n_envs, valid = null), so that one device function copies either way.
+struct CwBank {
+    uint4 *hdr, *pos, *init_pos, *goal_pos;
+    uint32_t *goal_codes;
+    int32_t *ep_no;
+    uint16_t *init_agent, *goal_agent;
+    uint32_t *mt;            // [rows][624]
+    int32_t *mt_idx;
+    uint4 *nx_init_pos, *nx_goal_pos, *nx_misc;      // [CW_LA_DEPTH][rows] (engines that keep look-ahead records)
+    uint32_t *nx_ctl;
+    uint16_t *pool;          // [rows][K][9]
+    uint8_t *valid;          // [rows]
+    int32_t rows;            // the capacity: a row number is an index only after cwh_snapshot_row_ok(row, rows) (cw_host.h)
+};
+
 // Everything the kernels need, passed by value.
 struct CwParams {
     // per-env state (SoA of 16-byte records unless noted)
@@ -117,7 +135,8 @@ struct CwParams {
                                        // adapts its refill period to it without ever waiting for the card (cw_engine.cpp: cw_step)
     unsigned long long *counters; // [4] public: steps, finished, successes, invalid actions; [4] PRIVATE: the finished count the last sweep of the
                                   // observation array saw (cw_render_pieces_kernel: what kind of step does it follow?), [5] PRIVATE: resets of
-                                  // look-ahead engines that found no record and were taken the slow way; 8 words allocated
+                                  // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot save / load
+                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); 8 words allocated
     const CwMenuDev *menus;
     // constants
     int32_t n_envs;

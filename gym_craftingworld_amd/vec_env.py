@@ -120,6 +120,46 @@ def desired_bits(num_envs, desired, n_tasks):
     return np.ascontiguousarray((d << np.arange(n_tasks, dtype=np.int64)).sum(axis=1), dtype=np.uint16)
 
 
+def snapshot_rows(num_envs, capacity, rows, envs=None, fork=False):
+    """The row numbers cw_snapshot_save / cw_snapshot_load take, built and validated on the host: -> np.int32 [num_envs], entry i = the bank row of env i,
+    -1 = env i takes no part.  `rows` alone: one entry per env (length num_envs; a negative entry = no part).  With `envs`: envs[j] is paired with
+    rows[j] (env ids in -num_envs .. num_envs - 1), every env not listed takes no part.  ValueError for lengths that differ, an env listed twice, a row
+    at or above `capacity`, anything that is not a flat integer list and -- unless fork=True (a load: many envs may continue from one row) -- a row listed
+    twice; IndexError for an env outside the batch."""
+    num_envs, capacity = int(num_envs), int(capacity)
+    if rows is None:
+        raise ValueError('give rows (one per env), or envs and rows')
+    r = np.asarray(rows)
+    if r.ndim != 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+        raise ValueError('rows must be a flat list of integer row numbers')
+    r = r.astype(np.int64)
+    if envs is None:
+        if len(r) != num_envs:
+            raise ValueError('rows must hold one entry per env (%d), got %d' % (num_envs, len(r)))
+        out = np.where(r < 0, -1, r)
+    else:
+        e = np.asarray(envs)
+        if e.ndim != 1 or (e.size and not np.issubdtype(e.dtype, np.integer)):
+            raise ValueError('envs must be a flat list of integer env ids')
+        e = e.astype(np.int64)
+        if len(e) != len(r):
+            raise ValueError('%d envs but %d rows' % (len(e), len(r)))
+        bad = e[(e < -num_envs) | (e >= num_envs)]
+        if bad.size:
+            raise IndexError('env index %d outside a batch of %d envs' % (int(bad[0]), num_envs))
+        e = np.where(e < 0, e + num_envs, e)
+        if len(np.unique(e)) != len(e):
+            raise ValueError('an env is listed twice')
+        out = np.full(num_envs, -1, np.int64)
+        out[e] = np.where(r < 0, -1, r)
+    used = out[out >= 0]
+    if used.size and used.max() >= capacity:
+        raise ValueError('row %d is outside a bank of %d rows' % (int(used.max()), capacity))
+    if not fork and len(np.unique(used)) != len(used):
+        raise ValueError('a row is listed twice: two envs cannot be saved into one row')
+    return np.ascontiguousarray(out, dtype=np.int32)
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -477,6 +517,63 @@ class CraftingWorldVecEnv:
         if self.host_outputs:
             self._sync()
         return out
+
+    # ------------------------------------------------------------------ device-resident snapshots
+    def snapshot_reserve(self, rows):
+        """Allocate (or re-allocate: every saved row is dropped; 0 frees it) the engine's snapshot bank of `rows` rows in device memory, each of which
+        holds one env completely (cw_snapshot_reserve; synchronises this engine's work).  ValueError for rows < 0."""
+        self._settle()
+        L.check(self._lib.cw_snapshot_reserve(self._h, int(rows)), 'cw_snapshot_reserve', self._lib)
+        self._snapshot_capacity = int(rows)
+
+    @property
+    def snapshot_row_bytes(self):
+        """bytes one bank row holds (0 without a bank)"""
+        return int(self._lib.cw_snapshot_row_bytes(self._h))
+
+    @property
+    def snapshot_skipped(self):
+        """how many envs snapshot_save / snapshot_load have skipped so far for a bad row number (counters[6]; reading it synchronises)"""
+        return int(self._counters_raw[6].item())
+
+    def _snapshot_rows(self, rows, envs, fork):
+        if (type(rows) is torch.Tensor and envs is None and rows.is_cuda and rows.dtype == torch.int32 and tuple(rows.shape) == (self.num_envs,)
+                and rows.is_contiguous()):
+            if rows.device != self.device:
+                raise ValueError('the rows tensor is on %s, the envs are on %s' % (rows.device, self.device))
+            r = rows
+        else:
+            if torch.is_tensor(rows):
+                rows = rows.cpu().numpy()
+            if torch.is_tensor(envs):
+                envs = envs.cpu().numpy()
+            cap = getattr(self, '_snapshot_capacity', 0) if self.snapshot_row_bytes else 2 ** 31 - 1      # (no bank: the library reports the call order)
+            r = torch.as_tensor(snapshot_rows(self.num_envs, cap, rows, envs, fork)).to(self.device)
+        self._rows_keepalive = r
+        return C.c_void_p(r.data_ptr())
+
+    def snapshot_save(self, rows=None, *, envs=None):
+        """Save envs into rows of the bank (cw_snapshot_save: one kernel, no host round trip, capturable): env i into row rows[i].  A contiguous
+        torch.int32 tensor [num_envs] on the env's device is handed over in place -- no copy, no synchronisation; a negative entry = env i takes no
+        part, an entry at or above the capacity is skipped and counted (snapshot_skipped).  Anything else is validated and packed on the host
+        (snapshot_rows): `rows` alone holds one entry per env, `envs=[3, 5], rows=[0, 1]` pairs envs with rows.  Nothing of the envs changes."""
+        p = self._snapshot_rows(rows, envs, False)
+        L.check(self._lib.cw_snapshot_save(self._h, p, self._stream()), 'cw_snapshot_save', self._lib)
+        if self.host_outputs:
+            self._sync()
+
+    def snapshot_load(self, rows=None, *, envs=None, with_stream=True):
+        """Load rows of the bank into envs (cw_snapshot_load): env i from row rows[i], `rows` / `envs` as in snapshot_save; any number of envs may name
+        the same row -- the fork.  with_stream=True: the env becomes an exact twin of the saved one, its later resets included.  with_stream=False: the
+        saved episode only -- the env keeps its own RNG stream, look-ahead records, pool and task menu, plays the saved episode to its end and goes
+        on with episodes of its own.  A row never saved since snapshot_reserve is skipped and counted like a row outside the bank.  reward, done, the
+        episode statistics and counters[0..5] are not touched; achieved_mask / desired_mask and, in the pixel modes, the three frames show the
+        restored state at once.  -> the observation dict (live views, as reset_envs returns)."""
+        p = self._snapshot_rows(rows, envs, True)
+        L.check(self._lib.cw_snapshot_load(self._h, p, 1 if with_stream else 0, self._stream()), 'cw_snapshot_load', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return self._observation()
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+#define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
+                            * cw_snapshot_load, cw_snapshot_row_bytes); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -124,7 +125,8 @@ typedef struct cw_buffer_table {
     uint64_t *counters;      /* [4]  {env-steps, episodes finished, successes (reward==max_steps), invalid actions}; the allocation holds
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
-                              *      found no record waiting (performance diagnostics), [6..7] unused.  Read-only for callers. */
+                              *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
+                              *      for a bad row number, [7] unused.  Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
     uint8_t *host_onehot;    /* [S][S][12] engines that can run cw_step_resident only (else NULL): obs_one_hot (ray.py:119) of the env in pinned host
@@ -218,6 +220,36 @@ int cw_imagine_masked(cw_engine *e, const uint8_t *mask, const uint16_t *desired
  * stream moves.  pooled with fixed_init_state == 0 is CW_ERR_INVALID (the reference's randint(0) raises before any draw).  Look-ahead records, capture and
  * call order as for cw_imagine_masked. */
 int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, uint16_t *out_cells, cw_stream_t stream);
+
+/* --- device-resident snapshots: put an env back where it was, or let many envs continue from one env's state (tree search, "return, then explore",
+ * branching rollouts, curriculum restarts).  The reference has no counterpart but copy.deepcopy of an env object.  Every engine can hold one snapshot
+ * BANK in device memory: `rows` rows, each of which holds one env completely.
+ * cw_snapshot_reserve allocates the bank, or re-allocates it: every saved row is dropped (a row loads only after it has been saved since the last reserve);
+ *   rows == 0 frees it.  Synchronous; waits for this engine's own work only, as the other synchronous calls do (replays of a captured graph that uses the
+ *   bank are the caller's to wait for).  CW_ERR_INVALID for rows < 0, CW_ERR_HIP when the allocation fails -- the engine is then left WITHOUT a bank.
+ *   cw_snapshot_row_bytes: what one row holds (0 without a bank): 2 577 bytes + 196 on engines that keep look-ahead records + 18 per fixed_init_state.
+ * rows (save and load): DEVICE int32[num_envs] (with cw_config.host_outputs: or GPU-mapped host memory), only read: the bank row of env i; rows[i] < 0:
+ *   env i takes no part.  A row number at or above the capacity -- and on load a row never saved since the last reserve -- is SKIPPED: the env is left
+ *   exactly as it is and counters[6] is incremented once.  No row number becomes an address without that check.
+ * cw_snapshot_save: bank row rows[i] receives env i.  Writes nothing of the engine but the bank (and counters[6] for a skipped env).  Two envs naming the
+ *   same row are the caller's error: the row then holds an unspecified mix of the two, nothing else is harmed.
+ * cw_snapshot_load: env i receives bank row rows[i]; any number of envs may name the same row -- the fork.
+ *   A row holds the EPISODE (current state and header, the start and goal states, ep_no) and the env's SOURCE OF FUTURE EPISODES (its MT19937 stream, on
+ *   engines that keep look-ahead records its whole ring of them, its menu id -- hdr byte 3 -- and with fixed_init_state > 0 its pool row).
+ *   with_stream != 0 restores both: the env becomes an exact twin of the saved one, and all its later resets are the saved env's.
+ *   with_stream == 0 restores the episode only: the env keeps its own stream, ring, pool and menu id (everything else in hdr is the row's, the subset-reward
+ *   flag and the success count among it), plays the saved episode to its end and goes on with episodes of its own -- what a caller wants who forks one
+ *   state into 64 envs and does not want 64 identical next episodes.
+ *   cw_buffer_table.achieved / .desired take the restored masks, as after cw_reset_masked; in the pixel modes the env's obs (held item included), init_obs and
+ *   desired_goal frames are repainted.  reward, done, episode_length, episode_return, terminal_obs and counters[0..5] are NOT written: a restore is not
+ *   a step and not a finished episode.
+ * Both enqueue ONE kernel (cw_snapshot_save_kernel / cw_snapshot_load_kernel) on `stream` -- no host synchronisation, no allocation -- and can be captured
+ * into a HIP graph with cw_step / cw_step_many / cw_reset_masked.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load and without a bank.
+ * The bank is not part of a checkpoint blob; cw_checkpoint_load, cw_seed_* and cw_generate_fixed_states leave it alone.  (Not timed: tools/measure_snapshot.py.) */
+int cw_snapshot_reserve(cw_engine *e, int32_t rows);
+size_t cw_snapshot_row_bytes(const cw_engine *e);
+int cw_snapshot_save(cw_engine *e, const int32_t *rows, cw_stream_t stream);
+int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
