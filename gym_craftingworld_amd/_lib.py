@@ -19,6 +19,7 @@ CW_ABI_VERSION = 5
 CW_MT_N = 624
 CW_MAX_TASKS = 16
 CW_MAX_MENUS = 256
+CW_NUM_ACTIONS = 6
 
 CW_OK, CW_ERR_INVALID, CW_ERR_HIP, CW_ERR_STATE = 0, -1, -2, -3
 CW_OBS_STATE, CW_OBS_PIXELS_FULL, CW_OBS_PIXELS_DIRTY = 0, 1, 2
@@ -54,6 +55,11 @@ class cw_state_view(C.Structure):
                 ('step_num', C.c_void_p), ('ep_no', C.c_void_p)]
 
 
+class cw_expand_out(C.Structure):
+    _fields_ = [('reward', C.c_void_p), ('done', C.c_void_p), ('changed', C.c_void_p), ('achieved', C.c_void_p), ('hdr', C.c_void_p),
+                ('slot_pos', C.c_void_p)]
+
+
 class cw_profile(C.Structure):
     _fields_ = [('steps', C.c_int32), ('ms_step_kernel', C.c_float), ('ms_reset_kernel', C.c_float),
                 ('ms_render_kernel', C.c_float), ('ms_render_kernel_max', C.c_float), ('ms_render_kernel_min', C.c_float),
@@ -83,6 +89,8 @@ ABI = {
     'cw_snapshot_row_bytes': (C.c_size_t, [_VP]),
     'cw_snapshot_save': (C.c_int, [_VP, _VP, _VP]),
     'cw_snapshot_load': (C.c_int, [_VP, _VP, C.c_int32, _VP]),
+    'cw_expand': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_expand_out), _VP]),
+    'cw_export_onehot_states': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
@@ -143,6 +151,7 @@ HOST_HELPERS = {
     'cwh_snapshot_section_bytes': (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]),
     'cwh_snapshot_row_in_bank': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_expand_env_in_batch': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),
     'cwh_sweep_periods': (None, [C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -27,6 +27,8 @@ hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const
 hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st);
 hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st);
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st);
+hipError_t cwk_launch_expand(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, const CwExpandOut *O, hipStream_t st);
+hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, int n_states, uint8_t *out, hipStream_t st);
 hipError_t cwk_launch_pool(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_seed(const CwParams *P, const uint32_t *seeds_dev, hipStream_t st);
 hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, int paint_dirty, unsigned long long idle_ticks,
@@ -877,6 +879,59 @@ int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_
     PARK(e);
     if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
     HIP_TRY(cwk_launch_snapshot_load(&e->P, &e->tune, &e->B, rows, with_stream != 0, e->obs_mode, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// ------------------------------------------------------------------------------ expand: the six successors of every state
+#define CW_EXPAND_MAX_STATES (1 << 27)
+static bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
+
+// Only enqueues ONE kernel: no wait, no allocation, the same call whether it runs or is captured.  Writes nothing of the engine but counters[7].
+int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, const cw_expand_out *out,
+              cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_expand: null %s", !e ? "engine" : "out");
+    if (!out->reward && !out->done && !out->changed && !out->achieved && !out->hdr && !out->slot_pos)
+        return fail(CW_ERR_INVALID, "cw_expand: every field of out is null");
+    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES) return fail(CW_ERR_INVALID, "cw_expand: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
+    if (!hdr_in != !slot_pos_in) return fail(CW_ERR_INVALID, "cw_expand: %s given without %s", hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
+    if (env_of && !hdr_in) return fail(CW_ERR_INVALID, "cw_expand: env_of given without hdr_in");
+    if (!hdr_in && n_states != e->n) return fail(CW_ERR_INVALID, "cw_expand: n_states = %d must be num_envs = %d without hdr_in", n_states, e->n);
+    if (misaligned16(hdr_in)) return fail(CW_ERR_INVALID, "cw_expand: hdr_in is not 16-byte aligned");
+    if (misaligned16(slot_pos_in)) return fail(CW_ERR_INVALID, "cw_expand: slot_pos_in is not 16-byte aligned");
+    if (misaligned16(out->hdr)) return fail(CW_ERR_INVALID, "cw_expand: out->hdr is not 16-byte aligned");
+    if (misaligned16(out->slot_pos)) return fail(CW_ERR_INVALID, "cw_expand: out->slot_pos is not 16-byte aligned");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_expand called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    CwExpandOut O;
+    O.reward = out->reward; O.done = out->done; O.changed = out->changed; O.achieved = out->achieved;
+    O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos;
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    HIP_TRY(cwk_launch_expand(&e->P, env_of, h, p, n_states, &O, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, uint8_t *out, cw_stream_t stream)
+{
+    if (!e || !hdr || !slot_pos || !out)
+        return fail(CW_ERR_INVALID, "cw_export_onehot_states: null %s", !e ? "engine" : !hdr ? "hdr" : !slot_pos ? "slot_pos" : "out");
+    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES)
+        return fail(CW_ERR_INVALID, "cw_export_onehot_states: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
+    if (misaligned16(hdr)) return fail(CW_ERR_INVALID, "cw_export_onehot_states: hdr is not 16-byte aligned");
+    if (misaligned16(slot_pos)) return fail(CW_ERR_INVALID, "cw_export_onehot_states: slot_pos is not 16-byte aligned");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_export_onehot_states called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_export_onehot_states(&e->P, &e->tune, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

@@ -174,6 +174,7 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
     return CWH_SNAP_SECTIONS;
 }
 int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity) { return cwh_snapshot_row_ok(row, capacity); }
+int cwh_expand_env_in_batch(int32_t env, int32_t num_envs) { return cwh_expand_env_ok(env, num_envs); }
 
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule
 static double period_ns(int32_t sweep_waves, double tb_per_s) { return (double)sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }

@@ -48,6 +48,9 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
 #endif
 static inline CWH_HOST_DEVICE int cwh_snapshot_row_ok(int32_t row, int32_t capacity) { return row >= 0 && row < capacity; }
 int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity);       // (the same, exported for the CPU tests)
+// THE env check of cw_expand_kernel, shared by host and device: an entry of the caller's env_of array may index the engine's per-env arrays only if this says so
+static inline CWH_HOST_DEVICE int cwh_expand_env_ok(int32_t env, int32_t num_envs) { return env >= 0 && env < num_envs; }
+int cwh_expand_env_in_batch(int32_t env, int32_t num_envs);        // (the same, exported for the CPU tests)
 
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).

@@ -13,6 +13,8 @@
 //                     cw_sample_state_masked_kernel: sample_state() / generate_fixed_initial_state() from the selected envs' streams.
 //   cw_snapshot_save_kernel / cw_snapshot_load_kernel  envs into rows of the engine's device-resident snapshot bank and back (restore, fork), dealt out the
 //                     same way by a device array of row numbers.
+//   cw_expand_kernel  the successors of all six actions of M states (the engine's own or packed records of the caller's), one lane per (action, state) pair with
+//                     the action uniform across a wave; writes nothing of the engine.  cw_export_onehot_states_kernel: the one-hot view of such records.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -588,6 +590,65 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwParams P, const void *ac
         if (m_done) atomicAdd(&P.counters[1], (unsigned long long)__popcll(m_done));
         if (m_succ) atomicAdd(&P.counters[2], (unsigned long long)__popcll(m_succ));
         if (m_inv) atomicAdd(&P.counters[3], (unsigned long long)__popcll(m_inv));
+    }
+}
+
+// ------------------------------------------------------------------------------------ expand
+// cw_expand: step_env as the pure function it is -- the successors of ALL SIX actions of n_states states, with no env touched.  One lane per (action, state)
+// pair: blockIdx.y is the action, the lanes of a wave are 64 consecutive states.  The action is therefore uniform across a wave, and handed to step_env as a
+// LITERAL (expand_one<A> behind a uniform switch): every `a == ...` of step_env is folded away, where the step kernels -- each lane with an action of its
+// own -- run both sides.  Loads: hdr, pos and (while something is held) init_pos[env], 16 bytes a lane each; with env_of == null and n_states <= n_envs all
+// three are one contiguous KiB per wave, and the six action waves of a state re-read the same lines from L2.  Stores: the outputs are action-major, row
+// a * n_states + j, so every store of a wave is one contiguous run.  No LDS.
+// Which env a record belongs to (it supplies init_pos): env_of == null: j % n_envs; else env_of[j] -- negative: the state takes no part; an index only behind
+// cwh_expand_env_ok, else the state is skipped and counted in counters[7], once a wave by ballot and by the action-0 waves only.  Rows of states that take
+// no part or are skipped are not written.  The records themselves are only ever compared, never used as addresses.
+template <int A>
+__device__ __forceinline__ void expand_one(const CwParams &P, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int j, int env, size_t row,
+                                           const CwExpandOut &O)
+{
+    uint4 h = hdr_in[j];
+    uint32_t sp[8];
+    unpack_pos(pos_in[j], sp);
+    const CwStepOut o = step_env(P, h, sp, A, [&]() { return P.init_pos[env]; });
+    if (O.reward) O.reward[row] = o.reward;
+    if (O.done) O.done[row] = o.done ? 1 : 0;
+    if (O.changed) O.changed[row] = o.changed ? 1 : 0;
+    if (O.achieved) O.achieved[row] = (uint16_t)o.achieved;
+    if (O.hdr) O.hdr[row] = h;
+    if (O.pos) O.pos[row] = pack_pos(sp);
+}
+
+__global__ __launch_bounds__(256) void cw_expand_kernel(CwParams P, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                        const uint4 *__restrict__ pos_in, int n_states, CwExpandOut O)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
+    const int a = (int)blockIdx.y;
+    int env = -1;
+    bool skipped = false;
+    if (j < n_states) {
+        if (env_of) {
+            const int32_t v = env_of[j];
+            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
+            else skipped = v >= 0;
+        } else {
+            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
+        }
+    }
+    if (a == 0) {
+        const unsigned long long m_skip = CW_BALLOT(skipped);
+        if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
+    }
+    if (env < 0) return;
+    const size_t row = (size_t)a * (size_t)n_states + (size_t)j;
+    switch (a) {
+    case 0: expand_one<0>(P, hdr_in, pos_in, j, env, row, O); break;
+    case 1: expand_one<1>(P, hdr_in, pos_in, j, env, row, O); break;
+    case 2: expand_one<2>(P, hdr_in, pos_in, j, env, row, O); break;
+    case 3: expand_one<3>(P, hdr_in, pos_in, j, env, row, O); break;
+    case 4: expand_one<4>(P, hdr_in, pos_in, j, env, row, O); break;
+    case 5: expand_one<5>(P, hdr_in, pos_in, j, env, row, O); break;
+    default: break;
     }
 }
 
@@ -2061,6 +2122,27 @@ __global__ __launch_bounds__(256) void cw_export_onehot_kernel(CwParams P, uint8
     }
 }
 
+// the same for n_states packed records of the caller's (cw_export_onehot_states): hdr [n_states] / pos [n_states] in the engine's formats; the records are
+// only compared with cell numbers, never used as addresses
+__global__ __launch_bounds__(256) void cw_export_onehot_states_kernel(CwParams P, const uint4 *__restrict__ hdr, const uint4 *__restrict__ pos, int n_states,
+                                                                      uint8_t *out)
+{
+    const size_t total = (size_t)n_states * P.ncell;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
+        const uint32_t st = (uint32_t)(g / P.ncell);
+        const uint32_t cell = (uint32_t)(g - (size_t)st * P.ncell);
+        const uint4 h = hdr[st];
+        uint32_t sp[8];
+        unpack_pos(pos[st], sp);
+        const uint32_t code = code_of(h.w, slot_at(sp, cell));
+        const uint32_t hold = hold_of(h.x);
+        uint32_t bits = code ? (1u << (code - 1)) : 0u;
+        if (cell == agent_cell_of(P, h.x)) bits |= (1u << 8) | (hold ? (1u << ((8 + hold) & 31u)) : 0u);
+        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(bits);
+    }
+}
+
 // ------------------------------------------------------------------------------------ render(state) for ANY one-hot state
 // render(state=...) of ray.py:442-486 on caller-supplied (S,S,12) one-hot states, whatever they hold (several objects in a cell,
 // more than eight objects, hold flags away from the agent): img = sum over object channels of COLORS_N (the reference's tensordot;
@@ -2403,6 +2485,22 @@ hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const 
     const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
     if (obs_mode != 0) hipLaunchKernelGGL(cw_snapshot_load_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
     else hipLaunchKernelGGL(cw_snapshot_load_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
+    return hipGetLastError();
+}
+
+// cw_expand: one launch, grid = (ceil(n_states / 256), 6 actions)
+hipError_t cwk_launch_expand(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, const CwExpandOut *O, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_expand_kernel, dim3((unsigned)((n_states + 255) / 256), 6u), dim3(256), 0, st, *P, env_of, hdr_in, pos_in, n_states, *O);
+    return hipGetLastError();
+}
+hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, int n_states, uint8_t *out, hipStream_t st)
+{
+    const size_t total = (size_t)n_states * P->ncell;
+    const size_t cap = (size_t)T->n_cu * 32;
+    int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(cw_export_onehot_states_kernel, dim3(blocks), dim3(256), 0, st, *P, hdr, pos, n_states, out);
     return hipGetLastError();
 }
 

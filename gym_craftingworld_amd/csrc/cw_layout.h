@@ -91,6 +91,17 @@ struct CwBank {
     int32_t rows;            // the capacity: a row number is an index only after cwh_snapshot_row_ok(row, rows) (cw_host.h)
 };
 
+// Where cw_expand_kernel leaves the six successors of M states (the public cw_expand_out with the records typed): every array ACTION-MAJOR, row a * M + j =
+// action a on input state j.  A null field is not written.
+struct CwExpandOut {
+    int32_t *reward;         // [6][M]
+    uint8_t *done;           // [6][M]
+    uint8_t *changed;        // [6][M]
+    uint16_t *achieved;      // [6][M]
+    uint4 *hdr;              // [6][M] successor headers
+    uint4 *pos;              // [6][M] successor slot positions
+};
+
 // Everything the kernels need, passed by value.
 struct CwParams {
     // per-env state (SoA of 16-byte records unless noted)
@@ -136,7 +147,8 @@ struct CwParams {
     unsigned long long *counters; // [4] public: steps, finished, successes, invalid actions; [4] PRIVATE: the finished count the last sweep of the
                                   // observation array saw (cw_render_pieces_kernel: what kind of step does it follow?), [5] PRIVATE: resets of
                                   // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot save / load
-                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); 8 words allocated
+                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); [7] public: states cw_expand_kernel
+                                  // skipped for an env index at or above n_envs; 8 words allocated
     const CwMenuDev *menus;
     // constants
     int32_t n_envs;

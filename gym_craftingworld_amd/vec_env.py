@@ -160,6 +160,50 @@ def snapshot_rows(num_envs, capacity, rows, envs=None, fork=False):
     return np.ascontiguousarray(out, dtype=np.int32)
 
 
+EXPAND_FIELDS = ('reward', 'done', 'changed', 'achieved_mask', 'hdr', 'slot_pos')
+
+
+def _expand_m(num_envs, hdr, slot_pos, env_of):
+    """expand_args on (shape, numpy dtype) pairs (or None): what both of expand()'s paths share -- a device tensor is checked without being copied"""
+    num_envs = int(num_envs)
+    if (hdr is None) != (slot_pos is None):
+        raise ValueError('hdr and slot_pos go together: %s given without %s' % (('slot_pos', 'hdr') if hdr is None else ('hdr', 'slot_pos')))
+    if hdr is None:
+        if env_of is not None:
+            raise ValueError('env_of needs hdr and slot_pos: the engine\'s own states are env 0 .. num_envs - 1')
+        return num_envs
+    (hs, hd), (ps, pd) = hdr, slot_pos
+    if len(hs) < 1 or hs[-1] != 16 or np.dtype(hd) != np.uint8:
+        raise ValueError('hdr must be uint8 [..., 16], got %s %s' % (np.dtype(hd), tuple(hs)))
+    if len(ps) < 1 or ps[-1] != 8 or np.dtype(pd) not in (np.dtype(np.int16), np.dtype(np.uint16)):
+        raise ValueError('slot_pos must be int16 [..., 8], got %s %s' % (np.dtype(pd), tuple(ps)))
+    if tuple(hs[:-1]) != tuple(ps[:-1]):
+        raise ValueError('hdr holds %s records, slot_pos %s' % (tuple(hs[:-1]), tuple(ps[:-1])))
+    m = int(np.prod(hs[:-1], dtype=np.int64))
+    if m > 2 ** 27:
+        raise ValueError('%d states: at most 2**27 in one call' % m)
+    if env_of is not None:
+        es, ed = env_of
+        if len(es) != 1 or not np.issubdtype(np.dtype(ed), np.integer) or es[0] != m:
+            raise ValueError('env_of must be a flat integer list with one entry per state (%d), got %s %s' % (m, np.dtype(ed), tuple(es)))
+    return m
+
+
+def expand_args(num_envs, hdr, slot_pos, env_of):
+    """What cw_expand is handed, validated on the host (numpy inputs): -> M, the number of input states.  hdr uint8 [..., 16] and slot_pos int16 / uint16
+    [..., 8] with the same leading shape (flattened to M), or both None: the engine's own states, M = num_envs -- nothing else can be asked of them, so
+    env_of must be None too.  env_of: None (state j belongs to env j % num_envs), or a flat integer list of M env ids; a negative entry = the state
+    takes no part.  ValueError for one of hdr / slot_pos without the other, env_of without them, leading shapes that differ, a wrong dtype or last
+    dimension, an env_of that is not flat, not integer or not of length M; IndexError for an env_of entry >= num_envs (a device tensor handed over in
+    place is not read on the host: there the kernel skips such an entry and counts it)."""
+    sd = lambda a: None if a is None else (np.shape(a), np.asarray(a).dtype)  # noqa: E731
+    e = None if env_of is None else np.asarray(env_of)
+    m = _expand_m(num_envs, sd(hdr), sd(slot_pos), None if e is None else (e.shape, e.dtype if e.size else np.dtype(np.int32)))
+    if e is not None and e.size and int(e.max()) >= int(num_envs):
+        raise IndexError('env index %d outside a batch of %d envs' % (int(e.max()), int(num_envs)))
+    return m
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -574,6 +618,116 @@ class CraftingWorldVecEnv:
         if self.host_outputs:
             self._sync()
         return self._observation()
+
+    # ------------------------------------------------------------------ looking one step ahead
+    @property
+    def expand_skipped(self):
+        """how many states expand() has skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
+        return int(self._counters_raw[7].item())
+
+    _NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.int8: np.int8}
+
+    def _in_place(self, t, dtypes):
+        """a contiguous tensor on the env's device of one of `dtypes` goes to the kernel as it is"""
+        if type(t) is not torch.Tensor or not t.is_cuda:
+            return False
+        if t.device != self.device:
+            raise ValueError('the tensor is on %s, the envs are on %s' % (t.device, self.device))
+        return t.dtype in dtypes and t.is_contiguous()
+
+    def _records(self, hdr, slot_pos, env_of):
+        """hdr / slot_pos / env_of as expand() and one_hot_states() take them -> (M, leading shape, device tensors or None)"""
+        if hdr is None or slot_pos is None:
+            return _expand_m(self.num_envs, None if hdr is None else ((16,), np.uint8), None if slot_pos is None else ((8,), np.int16),
+                             None if env_of is None else ((0,), np.int32)), (self.num_envs,), None, None, None
+        h_dev, p_dev = self._in_place(hdr, (torch.uint8,)), self._in_place(slot_pos, (torch.int16,))
+        e_dev = env_of is not None and self._in_place(env_of, (torch.int32,))
+        as_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+        if not h_dev:
+            hdr = as_np(hdr)
+        if not p_dev:
+            slot_pos = as_np(slot_pos)
+        if env_of is not None and not e_dev:
+            env_of = as_np(env_of)
+        def sd(a, empty=None):          # (shape, numpy dtype) of a device tensor or a numpy array; an empty env_of list is an empty list of ints
+            if torch.is_tensor(a):
+                return tuple(a.shape), self._NP_OF.get(a.dtype, np.float64)
+            return tuple(a.shape), a.dtype if a.size or empty is None else empty
+        m = _expand_m(self.num_envs, sd(hdr), sd(slot_pos), None if env_of is None else sd(env_of, np.dtype(np.int32)))
+        lead = tuple(hdr.shape[:-1])
+        if not h_dev:
+            hdr = torch.as_tensor(np.ascontiguousarray(hdr)).to(self.device)
+        if not p_dev:
+            slot_pos = torch.as_tensor(np.ascontiguousarray(slot_pos).view(np.int16)).to(self.device)
+        if env_of is not None and not e_dev:
+            if env_of.size and int(env_of.max()) >= self.num_envs:
+                raise IndexError('env index %d outside a batch of %d envs' % (int(env_of.max()), self.num_envs))
+            env_of = torch.as_tensor(np.ascontiguousarray(np.maximum(env_of.astype(np.int64), -1), dtype=np.int32)).to(self.device)
+        return m, lead, hdr, slot_pos, env_of
+
+    def expand(self, hdr=None, slot_pos=None, env_of=None, *, fields=None, out=None):
+        """What would each of the six actions do from here?  (cw_expand: one kernel, no host round trip, capturable; no env is touched.)  -> a dict of
+        device tensors, ACTION-MAJOR: entry [a, j] is action a (0..5 = Up, Right, Down, Left, PickUp, Drop) applied to input state j:
+        'reward' int32 [6, M] (what step() would return), 'done' and 'changed' bool [6, M] (the action changed the state: the reference's reward gate),
+        'achieved_mask' int16 [6, M], 'hdr' uint8 [6, M, 16] and 'slot_pos' int16 [6, M, 8]: the successor as a packed record -- byte for byte what
+        step() leaves on an auto_reset=False engine; on an auto-reset engine therefore the terminal state a step would have replaced.
+        Without arguments: the envs' current states, M = num_envs.  With hdr [..., 16] / slot_pos [..., 8] (both, same leading shape, flattened to M):
+        those states -- env.hdr / env.slot_pos, a pruned frontier, or an earlier result: `expand(hdr=r['hdr'], slot_pos=r['slot_pos'])` is depth 2 with
+        shape [6, 6 * N], and so on.  A record supplies agent, hold, both masks, step_num and the reward rule; the env it belongs to supplies its episode's
+        start positions: env j % num_envs, or env_of[j] (int32 [M]; negative: the state takes no part and its rows are not written).
+        Contiguous tensors on the env's device go over in place -- no copy, no synchronisation; an env_of entry >= num_envs is then skipped by the kernel
+        and counted (expand_skipped).  Anything else is validated on the host (expand_args: ValueError, IndexError).
+        fields: a subset of EXPAND_FIELDS to compute (default all).  out: a dict returned by an earlier call with the same M and fields, written again."""
+        names = EXPAND_FIELDS if fields is None else tuple(fields)
+        if not names or any(f not in EXPAND_FIELDS for f in names) or len(set(names)) != len(names):
+            raise ValueError('fields must be a non-empty subset of %s' % (EXPAND_FIELDS,))
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        spec = {'reward': ((6, m), torch.int32), 'done': ((6, m), torch.bool), 'changed': ((6, m), torch.bool),
+                'achieved_mask': ((6, m), self.achieved_mask.dtype), 'hdr': ((6, m, 16), torch.uint8), 'slot_pos': ((6, m, 8), self.slot_pos.dtype)}
+        if out is None:
+            out = {f: torch.empty(spec[f][0], dtype=torch.uint8 if spec[f][1] is torch.bool else spec[f][1], device=self.device) for f in names}
+            out = {f: t.view(torch.bool) if spec[f][1] is torch.bool else t for f, t in out.items()}
+        else:
+            if set(out) != set(names):
+                raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names)))
+            for f in names:
+                t = out[f]
+                if (type(t) is not torch.Tensor or tuple(t.shape) != spec[f][0] or t.dtype != spec[f][1] or t.device != self.device
+                        or not t.is_contiguous()):
+                    raise ValueError('out[%r] must be a contiguous %s tensor %s on %s' % (f, spec[f][1], spec[f][0], self.device))
+        if m == 0:
+            return out
+        ptr = lambda f: C.c_void_p(out[f].data_ptr()) if f in out else None  # noqa: E731
+        o = L.cw_expand_out(reward=ptr('reward'), done=ptr('done'), changed=ptr('changed'), achieved=ptr('achieved_mask'), hdr=ptr('hdr'),
+                            slot_pos=ptr('slot_pos'))
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self._expand_keepalive = (hdr, slot_pos, env_of, out)
+        L.check(self._lib.cw_expand(self._h, vp(env_of), vp(hdr), vp(slot_pos), m, C.byref(o), self._stream()), 'cw_expand', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
+
+    def one_hot_states(self, hdr, slot_pos, out=None):
+        """obs_one_hot (ray.py:119) of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() takes and returns them):
+        -> uint8 [..., S, S, 12], the held item's channel 9-11 at the agent's cell (cw_export_onehot_states).  render_states() of the result is the
+        frame a pixel policy would see of that state.  Does not touch the envs."""
+        if hdr is None or slot_pos is None:
+            raise ValueError('one_hot_states needs hdr and slot_pos')
+        m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
+        shape = lead + (self.size, self.size, 12)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (type(out) is not torch.Tensor or tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous uint8 tensor %s on %s' % (shape, self.device))
+        if m == 0:
+            return out
+        self._onehot_states_keepalive = (hdr, slot_pos, out)
+        L.check(self._lib.cw_export_onehot_states(self._h, C.c_void_p(hdr.data_ptr()), C.c_void_p(slot_pos.data_ptr()), m, C.c_void_p(out.data_ptr()),
+                                                  self._stream()), 'cw_export_onehot_states', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

@@ -24,13 +24,14 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
 #define CW_MAX_TASKS 16    /* len(task_list) upper bound (bits of the goal masks)  */
 #define CW_MAX_MENUS 256   /* distinct ordered selected_tasks lists per engine     */
 #define CW_NUM_OBJECTS 8   /* OBJECTS, ray.py:21                                   */
+#define CW_NUM_ACTIONS 6   /* ACTIONS, ray.py:130-131: Up, Right, Down, Left, PickUp, Drop */
 
 /* status codes */
 #define CW_OK 0
@@ -126,7 +127,8 @@ typedef struct cw_buffer_table {
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
                               *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
-                              *      for a bad row number, [7] unused.  Read-only for callers. */
+                              *      for a bad row number, [7] counts the states a cw_expand skipped for an env index at or above num_envs.
+                              *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
     uint8_t *host_onehot;    /* [S][S][12] engines that can run cw_step_resident only (else NULL): obs_one_hot (ray.py:119) of the env in pinned host
@@ -250,6 +252,50 @@ int cw_snapshot_reserve(cw_engine *e, int32_t rows);
 size_t cw_snapshot_row_bytes(const cw_engine *e);
 int cw_snapshot_save(cw_engine *e, const int32_t *rows, cw_stream_t stream);
 int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_stream_t stream);
+
+/* --- looking one step ahead: the successors of ALL SIX actions, of the engine's current states or of any states the caller hands in as packed records
+ * (planners, greedy and one-step-lookahead policies, action masks, Q-bootstraps, tree search of any depth on the device).  The reference has no counterpart
+ * but copy.deepcopy of an env object and six step() calls.  step() is a pure function of an env's header, its eight slot positions and its episode's
+ * start positions (eval_task_edit, ray.py:672-702); it draws nothing from the RNG stream.  cw_expand is that function, with no env touched.
+ * M = n_states.  Every output is ACTION-MAJOR: row a * M + j is action a (0..5 = Up, Right, Down, Left, PickUp, Drop) applied to input state j. */
+typedef struct cw_expand_out {   /* DEVICE pointers (cw_config.host_outputs engines: or GPU-mapped host memory); a NULL field is not written; all NULL: CW_ERR_INVALID */
+    int32_t  *reward;    /* [6][M]      what cw_step would return: -1 or max_steps                                  */
+    uint8_t  *done;      /* [6][M]      step_num reached max_steps, or success (ray.py:367)                         */
+    uint8_t  *changed;   /* [6][M]      the action changed the state (the reference's reward gate, ray.py:348-363)  */
+    uint16_t *achieved;  /* [6][M]      achieved mask after the step                                                */
+    uint8_t  *hdr;       /* [6][M][16]  successor header, the format of cw_buffer_table.hdr; 16-byte aligned        */
+    uint16_t *slot_pos;  /* [6][M][8]   successor slots, the format of cw_buffer_table.slot_pos; 16-byte aligned    */
+} cw_expand_out;
+/* hdr_in == NULL: the engine's CURRENT states.  slot_pos_in and env_of must be NULL too and n_states must equal num_envs; input state j is env j.
+ * hdr_in != NULL: n_states records of the caller's in the public packed formats, hdr_in [M][16] and slot_pos_in [M][8] (both required, both 16-byte
+ *   aligned, device memory, only read): the engine's own hdr / slot_pos buffers, an earlier call's out->hdr / out->slot_pos, a pruned frontier.  The header
+ *   supplies agent, hold, achieved, desired, step_num and the subset-reward flag; the ENV a record belongs to supplies what a record does not hold: its
+ *   episode's start positions, and the engine its max_steps, size and task mask.
+ *   env_of == NULL: state j belongs to env j % num_envs -- the action-major output of an engine-state call feeds back as n_states = 6 * num_envs with no
+ *   index array, and again at 36 x and beyond.
+ *   env_of != NULL: DEVICE int32[n_states], only read.  A negative entry: the state takes no part, its output rows are not written.  An entry >= num_envs
+ *   is SKIPPED: its output rows are not written either and counters[7] is incremented once (not once per action).  No entry becomes an address
+ *   without that check.
+ * Records are never used as addresses: the step only compares cells.  An impossible record (an agent outside the grid, a hold above 3, a slot position
+ * outside the grid) gives unspecified successor VALUES and never an out-of-bounds access.  out->hdr / out->slot_pos must not overlap the inputs.
+ * Successor (a, j) is byte for byte what cw_step leaves in hdr / slot_pos for that env and action on an auto_reset == 0 engine: step_num + 1 (saturating),
+ *   flag bit 0 cleared, the success count in flag bits 2-15 updated, the menu byte kept.  On auto-reset engines it is therefore the state BEFORE the reset --
+ *   the terminal state the caller otherwise never sees.  A done state can be expanded again: like the reference (ray.py:367) it just keeps stepping.
+ * PURE: nothing of the engine is written except counters[7], and that only for a skipped state -- no state, stream, look-ahead record, pool, bank, reward /
+ *   done / mask / episode output, frame, or counters[0..6].
+ * Enqueues ONE kernel (cw_expand_kernel: one lane per (action, state) pair, the action uniform across a wave) on `stream` -- no host synchronisation, no
+ *   allocation -- and can be captured into a HIP graph with cw_step / cw_reset_masked / cw_snapshot_*.  Every obs_mode, with and without auto_reset,
+ *   host_outputs engines included.  n_states == 0: CW_OK, nothing enqueued.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID:
+ *   a null engine or out, all six fields NULL, n_states < 0 or above 2^27, n_states != num_envs without hdr_in, hdr_in without slot_pos_in or the reverse,
+ *   env_of without hdr_in, a misaligned hdr_in / slot_pos_in / out->hdr / out->slot_pos.  (13 us per call at 4 096 and at 65 536 states, launch included: tools/measure_expand.py, profiles/r07_expand.txt.) */
+int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in,
+              int32_t n_states, const cw_expand_out *out, cw_stream_t stream);
+/* cw_export_onehot for caller-supplied packed records instead of the engine's arrays: hdr [n_states][16], slot_pos [n_states][8] (16-byte aligned, device)
+ * -> out [n_states][S][S][12], hold channels 9-11 at the agent's cell.  With cw_render_onehot it turns any successor into the frame a pixel policy would
+ * see.  One kernel (cw_export_onehot_states_kernel); the engine contributes only S.  n_states == 0: CW_OK, nothing enqueued; CW_ERR_INVALID for a null
+ * argument, n_states < 0 or above 2^27, a misaligned hdr / slot_pos; CW_ERR_STATE before the first cw_reset / cw_checkpoint_load. */
+int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states,
+                            uint8_t *out /* [n_states][S][S][12] */, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,

@@ -1,0 +1,375 @@
+"""GPU tier of the one-step look-ahead: cw_expand_kernel / cw_export_onehot_states_kernel through CraftingWorldVecEnv.expand / one_hot_states.  Every call is
+checked row by row with expand_check.check_expand (itself tested on the CPU, tests/test_expand_logic.py): every written row against the CPU oracle's
+set_state + step, every row that must not be written against a sentinel, and the engine before and after the call byte for byte.  Everything is
+bit-exact.  No timing."""
+import ctypes as C
+import functools
+from itertools import product
+
+import numpy as np
+import pytest
+import torch
+
+from expand_check import DENSE, FIELDS, check_expand, decode, oracle_successors
+from masked_check import spread, take
+from oracle_replay import make_env, np_states, one_hot_of, same
+from test_snapshot import ENGINES, K5, N1
+
+pytestmark = pytest.mark.gpu
+
+SENT = 0xA5
+INT32_MAX = 2 ** 31 - 1
+_WIDTH = {'reward': 4, 'done': 1, 'changed': 1, 'achieved_mask': 2, 'hdr': 16, 'slot_pos': 16}
+_DTYPE = {'reward': torch.int32, 'done': torch.bool, 'changed': torch.bool, 'achieved_mask': torch.int16, 'hdr': torch.uint8, 'slot_pos': torch.int16}
+
+
+def _sentinel_out(M, fields=FIELDS):
+    """output buffers as expand(out=...) takes them, every byte SENT"""
+    out = {}
+    for f in fields:
+        raw = torch.full((6, M, _WIDTH[f]), SENT, dtype=torch.uint8, device='cuda')
+        t = raw.view(_DTYPE[f])
+        out[f] = t if f == 'hdr' or f == 'slot_pos' else t.squeeze(-1)
+        assert out[f].is_contiguous() and out[f].shape[:2] == (6, M)
+    return out
+
+
+def _host(r):
+    """an expand() result as numpy, done / changed as the bytes the kernel wrote"""
+    return {f: (t.view(torch.uint8) if t.dtype is torch.bool else t).cpu().numpy() for f, t in r.items()}
+
+
+def _dense_of(snap):
+    return decode(snap['hdr'], snap['slot_pos'], snap['state_grid'].shape[1])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 1. the whole local transition table
+S1, MAX1 = 5, 9
+DR = [(-1, 0), (0, 1), (1, 0), (0, -1)]
+
+
+@functools.lru_cache(maxsize=None)
+def _table():
+    """The states of test_hip_parity.test_systematic_transition_table without its action dimension: (object in the target cell 0..8) x (object under the
+    agent) x (hold) x (the side 0..3 on which the target cell lies) x (where the init grid put sticks / axe / hammer / tree relative to the two cells) x
+    (achieved bits) x (agent interior / in the corner); target and under never the same non-empty code.  -> grid, init_grid [n, 5, 5], agent [n, 2], hold,
+    achieved [n]"""
+    S = S1
+    cases = []
+    for tgt, under, hold, side, initv, achv, wall in product(range(9), (0, 1, 2, 3, 7, 8), range(4), range(4), range(4), range(3), (0, 1)):
+        if tgt and tgt == under:
+            continue
+        ar, ac = (0, 0) if wall else (2, 2)
+        g = np.zeros((S, S), np.uint8)
+        g[ar, ac] = under
+        tr, tc = ar + DR[side][0], ac + DR[side][1]
+        if 0 <= tr < S and 0 <= tc < S:
+            g[tr, tc] = tgt
+        else:
+            tr, tc = ar, ac                      # the wall: target == own cell
+        ig = np.zeros((S, S), np.uint8)          # one of each object; objects 1, 2, 3, 5 placed per initv
+        spots = {0: [(4, 0), (4, 1), (4, 2), (4, 3)],
+                 1: [(tr, tc), (4, 1), (4, 2), (4, 3)],
+                 2: [(4, 0), (tr, tc), (4, 2), (4, 3)] if hold != 3 else [(4, 0), (4, 1), (tr, tc), (4, 3)],
+                 3: [(4, 0), (4, 1), (4, 2), (tr, tc)]}[initv]
+        for code, (r, c) in zip((1, 2, 3, 5), spots):
+            ig[r, c] = code
+        for code, (r, c) in zip((4, 6, 7, 8), [(3, 4), (2, 4), (1, 4), (0, 4)]):
+            ig[r, c] = code
+        cases.append((g, ig, (ar, ac), hold, (0, 1 << 3, 0x1FF)[achv]))
+    assert len(cases) == 18816
+    return (np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), np.array([c[2] for c in cases], np.int64),
+            np.array([c[3] for c in cases], np.int64), np.array([c[4] for c in cases], np.int64))
+
+
+@functools.lru_cache(maxsize=None)
+def _table_desired():
+    """desired of env i: for half of the envs (RandomState(1)) the achieved mask the oracle gets for action i % 6, else randint(1, 512)"""
+    grid, init, agent, hold, ach = _table()
+    n = len(hold)
+    z = np.zeros(n, np.int64)
+    suc = oracle_successors(dict(grid=grid, agent=agent, hold=hold, achieved=ach, desired=z + 1, step_num=z + 3, flags=z), init, dict(size=(S1, S1), max_steps=MAX1))
+    rng = np.random.RandomState(1)
+    return np.array([int(suc['achieved'][i % 6, i]) if rng.rand() < 0.5 else rng.randint(1, 512) for i in range(n)], np.int64)
+
+
+@pytest.mark.parametrize('step_num', [3, MAX1 - 1])
+@pytest.mark.parametrize('style', [None, 'subset'])
+def test_the_whole_local_transition_table(style, step_num):
+    """18 816 states, one env each, injected with set_state; all six successors of every one against the oracle, under both reward rules, mid-episode and
+    one step before the time-out.  What the table exercises is counted from the oracle's values alone, before anything is compared."""
+    from gym_craftingworld_amd import CraftingWorldVecEnv
+    grid, init, agent, hold, ach = _table()
+    des = _table_desired()
+    n = len(hold)
+    okw = dict(size=(S1, S1), max_steps=MAX1)
+    env = CraftingWorldVecEnv(n, obs_mode='state', reward_style=style, auto_reset=False, seed=5, **okw)
+    env.reset()
+    env.set_state(grid=grid, init_grid=init, agent_rc=agent.astype(np.uint8), hold=hold.astype(np.uint8), achieved=ach.astype(np.uint16),
+                  desired=des.astype(np.uint16), step_num=np.full(n, step_num, np.int32))
+    before = take(env)
+    flags = _dense_of(before)['flags']                                     # (of a record only its flag word is the engine's: the reward rule, no success yet)
+    assert ((flags & ~1) == (2 if style else 0)).all()
+    states = dict(grid=grid, agent=agent, hold=hold, achieved=ach, desired=des, step_num=np.full(n, step_num, np.int64), flags=flags)
+    suc = oracle_successors(states, init, okw)
+    gained, lost = suc['achieved'] & ~ach, ach & ~suc['achieved']
+    gains = [int(((gained >> b) & 1).sum()) for b in range(9)]
+    losses = [int(((lost >> b) & 1).sum()) for b in range(5, 9)]
+    success = int((suc['reward'] == MAX1).sum())
+    timeout_only = int((suc['done'] & (suc['reward'] != MAX1)).sum())
+    print('gains', gains, 'losses of bits 5..8', losses, 'successes', success, 'changed', int(suc['changed'].sum()), 'unchanged', int((~suc['changed']).sum()),
+          'done by time-out alone', timeout_only)
+    assert min(gains) >= 100 and min(losses) >= 400 and success >= 10000
+    assert suc['changed'].sum() >= 50000 and (~suc['changed']).sum() >= 50000
+    if step_num == MAX1 - 1:
+        assert timeout_only >= 80000
+    r = env.expand()
+    after = take(env)
+    assert tuple(r['hdr'].shape) == (6, n, 16) and r['achieved_mask'].dtype == env.achieved_mask.dtype and r['done'].dtype == torch.bool
+    part, skipped = check_expand(before, after, None, None, _host(r), SENT, oracle_kw=okw, successors=(states, suc))
+    assert (part, skipped) == (n, 0)
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 2. against the engine's own step; 6. one-hot and frames
+def _oracle_frame(grid, agent, hold, alt):
+    from oracle.oracle import _lib
+    lib, u8p = _lib(), C.POINTER(C.c_uint8)
+    g = np.ascontiguousarray(grid, dtype=np.uint8)
+    s = g.shape[0]
+    out = np.empty((3 * s + 3, 3 * s, 3) if alt else (4 * s, 4 * s, 3), dtype=np.uint8)
+    fn = lib.cwo_render_alt if alt else lib.cwo_render
+    fn.argtypes = [C.c_int32, u8p, C.c_int32, C.c_int32, C.c_int32, u8p]
+    fn.restype = None
+    fn(s, g.ctypes.data_as(u8p), int(agent[0]), int(agent[1]), int(hold), out.ctypes.data_as(u8p))
+    return out
+
+
+@pytest.mark.parametrize('engine', list(ENGINES))
+def test_against_the_engines_own_step_on_packed_bytes(engine):
+    """expand() of the current states, then the same successors the long way round: snapshot_save once, and for each action snapshot_load(with_stream=True)
+    + step.  Without auto-reset the step's hdr, slot_pos, reward, done and achieved_mask equal row a of the result byte for byte; with auto-reset the
+    outputs do everywhere and the records where the env did not finish -- the finished ones are the terminal states only expand() shows, checked against
+    the oracle.  The one-hot view and the frame of every successor equal the oracle's."""
+    ekw = dict(ENGINES[engine])
+    alt = ekw.get('raster', 'ray') == 'alt'
+    env, _, _ = make_env(N1, *np_states(N1, 52000), **ekw, **K5)
+    env.snapshot_reserve(N1)
+    env.reset()
+    spread(env, 9, 1)
+    sn = env.get_state()['step_num']
+    sn[::5] = K5['max_steps'] - 1                                 # every fifth env one step before the time-out: successors that end the episode
+    env.set_state(step_num=sn)
+    before = take(env)
+    states = _dense_of(before)
+    suc = oracle_successors(states, before['state_init_grid'], K5)
+    assert suc['done'][:, ::5].all() and not suc['done'].all()
+    r = env.expand()
+    after = take(env)                                             # (every buffer, stream, frame and counter: check_expand compares them all)
+    check_expand(before, after, None, None, _host(r), SENT, oracle_kw=K5, successors=(states, suc))
+    rows = torch.arange(N1, dtype=torch.int32, device='cuda')
+    env.snapshot_save(rows)
+    for a in range(6):
+        env.snapshot_load(rows, with_stream=True)
+        _, rew, done, _ = env.step(torch.full((N1,), a, dtype=torch.uint8, device='cuda'))
+        assert torch.equal(rew.to(r['reward'].device), r['reward'][a]) and torch.equal(done.to(r['done'].device), r['done'][a]), a
+        assert torch.equal(env.achieved_mask.to(r['achieved_mask'].device), r['achieved_mask'][a]), a
+        same('done of action %d' % a, 0, done.cpu().numpy(), suc['done'][a])
+        keep = torch.ones(N1, dtype=torch.bool, device='cuda') if not env.auto_reset else ~r['done'][a]
+        assert keep.any()
+        assert torch.equal(env.hdr[keep], r['hdr'][a][keep]) and torch.equal(env.slot_pos[keep], r['slot_pos'][a][keep]), a
+        if env.auto_reset:                                        # the terminal states: the oracle's (check_expand has compared them; here by name)
+            fin = np.flatnonzero(suc['done'][a])
+            got = decode(r['hdr'][a].cpu().numpy()[fin], r['slot_pos'][a].cpu().numpy()[fin], K5['size'][0])
+            for k in DENSE:
+                same('terminal %s of action %d' % (k, a), fin, got[k], suc[k][a][fin])
+    # ---- 6. the one-hot view and the frame of every successor
+    oh = env.one_hot_states(r['hdr'], r['slot_pos'])
+    assert tuple(oh.shape) == (6, N1, 5, 5, 12) and oh.dtype == torch.uint8
+    want = one_hot_of(suc['grid'].reshape(6 * N1, 5, 5), suc['agent'].reshape(6 * N1, 2), suc['hold'].reshape(6 * N1))
+    same('one_hot_states of the successors', 0, oh.cpu().numpy().reshape(6 * N1, 5, 5, 12), want)
+    frames = env.render_states(oh.reshape(6 * N1, 5, 5, 12)[:64])
+    img = np.stack([_oracle_frame(suc['grid'].reshape(-1, 5, 5)[j], suc['agent'].reshape(-1, 2)[j], suc['hold'].reshape(-1)[j], alt) for j in range(64)])
+    same('render_states of the successors', 0, (frames.cpu().numpy() & 0xFF).astype(np.uint8), img)
+    assert torch.equal(env.one_hot_states(env.hdr, env.slot_pos), env.one_hot())
+    env.close()
+
+
+def test_host_outputs_engine():
+    """an engine whose outputs live in mapped host memory: the same call, synchronised on return"""
+    env, _, _ = make_env(4, *np_states(4, 53000), obs_mode='pixels_dirty', host_outputs=True, auto_reset=False, **K5)
+    env.reset()
+    for a in (1, 2, 4, 1, 5, 0):
+        env.step(np.full(4, a, np.int32))
+    before = take(env)
+    r = env.expand()
+    check_expand(before, take(env), None, None, _host(r), SENT, oracle_kw=K5)
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 3. shapes and edges
+def _env_of(M, N):
+    """M entries: random envs (repeats), and from 63 states on -1, -7, N, N + 31 and INT32_MAX, the wave's last lane among their places"""
+    e = np.random.RandomState(M).randint(0, N, M).astype(np.int64)
+    if M >= 63:
+        e[[3, 17, 31, 40, 62]] = [-1, N, -7, N + 31, INT32_MAX]
+        e[5] = e[6] = e[7]
+    if M >= 257:
+        e[[63, 64, 128, 255, 256]] = [N, -1, INT32_MAX, N + 31, N]
+    return e
+
+
+@pytest.fixture(scope='module')
+def engine70():
+    env, _, _ = make_env(N1, *np_states(N1, 54000), obs_mode='state', auto_reset=False, **K5)
+    env.reset()
+    spread(env, 9, 3)
+    yield env
+    env.close()
+
+
+@pytest.mark.parametrize('M', [1, 63, 64, 65, 257, 1000])
+def test_shapes_and_edges(engine70, M):
+    """M states taken from a 70-env engine, env_of on the device and handed over in place: every written and every unwritten row, and the skipped states
+    counted once each -- not once per action"""
+    env = engine70
+    e = _env_of(M, N1)
+    src = np.where((e >= 0) & (e < N1), e, 0)
+    before = take(env)
+    hdr = before['hdr'][src].copy()
+    hdr[:, 8] = (hdr[:, 8] + np.arange(M)) % K5['max_steps']                      # records of the caller's: other step counts than the envs' own
+    hdr[:, 3] = np.arange(M) % 5                                                  # ... and menu bytes, which a successor keeps
+    pos = before['slot_pos'][src].copy()
+    t_hdr, t_pos, t_env = torch.as_tensor(hdr, device='cuda'), torch.as_tensor(pos, device='cuda'), torch.as_tensor(e.astype(np.int32), device='cuda')
+    out = _sentinel_out(M)
+    skipped0 = env.expand_skipped
+    r = env.expand(t_hdr, t_pos, t_env, out=out)
+    assert all(r[f] is out[f] for f in FIELDS)
+    part, skipped = check_expand(before, take(env), dict(hdr=hdr, slot_pos=pos), e, _host(out), SENT, oracle_kw=K5)
+    assert skipped == int((e >= N1).sum()) and part == int(((e >= 0) & (e < N1)).sum())
+    assert env.expand_skipped == skipped0 + skipped
+    with pytest.raises(IndexError) if skipped else pytest.raises(ValueError):     # the host-validated path refuses what the kernel skips
+        env.expand(hdr, pos, e if skipped else e[:-1])
+    if M == 65:                                                                   # every single field: the other buffers stay as they were
+        for f in FIELDS:
+            bufs = _sentinel_out(M)
+            before = take(env)
+            r = env.expand(t_hdr, t_pos, t_env, fields=[f], out={f: bufs[f]})
+            assert list(r) == [f]
+            check_expand(before, take(env), dict(hdr=hdr, slot_pos=pos), e, _host(r), SENT, oracle_kw=K5)
+            for g in FIELDS:
+                if g != f:
+                    assert bool((bufs[g].view(torch.uint8) == SENT).all()), (f, g)
+        r = env.expand(hdr, pos, np.where(e >= N1, -1, e))                        # numpy in: validated and copied by the host
+        live = torch.as_tensor(src == e, device='cuda')
+        assert all(torch.equal(r[f][:, live], out[f][:, live]) for f in FIELDS)
+
+
+def test_no_states_and_bad_arguments_of_the_method(engine70):
+    env = engine70
+    r = env.expand(hdr=torch.empty((0, 16), dtype=torch.uint8, device='cuda'), slot_pos=torch.empty((0, 8), dtype=torch.int16, device='cuda'))
+    assert set(r) == set(FIELDS) and all(t.shape[:2] == (6, 0) and t.device == env.device for t in r.values())
+    assert tuple(env.one_hot_states(np.zeros((0, 16), np.uint8), np.zeros((0, 8), np.int16)).shape) == (0, 5, 5, 12)
+    good = env.expand()
+    for bad in (dict(fields=[]), dict(fields=['reward', 'frames']), dict(fields=['done', 'done']), dict(hdr=env.hdr), dict(slot_pos=env.slot_pos),
+                dict(env_of=torch.zeros(N1, dtype=torch.int32, device='cuda')), dict(out={'reward': good['reward']}),
+                dict(out=dict(good, reward=good['reward'].to(torch.int64))), dict(out=dict(good, hdr=good['hdr'][:, :, :8])),
+                dict(out=dict(good, done=good['done'].cpu())), dict(hdr=env.hdr, slot_pos=env.slot_pos, out=dict(good, done=good['done'][:, :5])),
+                dict(hdr=env.hdr[:5], slot_pos=env.slot_pos)):
+        with pytest.raises(ValueError):
+            env.expand(**bad)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 4. depth 2 with no index array
+def test_depth_two_with_no_index_array():
+    """expand() of expand()'s own records: 36 N rows, each against the oracle stepped twice from the env's state -- a done state just steps on"""
+    env, _, _ = make_env(N1, *np_states(N1, 55000), obs_mode='state', auto_reset=False, **K5)
+    env.reset()
+    spread(env, K5['max_steps'] - 1, 4)                           # envs that have not succeeded on the way stand one step before the time-out
+    before = take(env)
+    s0 = _dense_of(before)
+    suc1 = oracle_successors(s0, before['state_init_grid'], K5)
+    assert suc1['done'].any()                                     # (the oracle alone: first steps that end the episode)
+    s1 = {k: suc1[k].reshape((6 * N1,) + suc1[k].shape[2:]) for k in DENSE}
+    suc2 = oracle_successors(s1, np.tile(before['state_init_grid'], (6, 1, 1)), K5)
+    assert (suc2['step_num'].reshape(6, 6, N1) == s0['step_num'] + 2).all() and suc2['done'].reshape(6, 6, N1)[:, suc1['done']].any()
+    r1 = env.expand()
+    r2 = env.expand(**{k: r1[k] for k in ('hdr', 'slot_pos')})
+    assert tuple(r2['hdr'].shape) == (6, 6 * N1, 16) and tuple(r2['reward'].shape) == (6, 6 * N1)
+    inputs = dict(hdr=r1['hdr'].cpu().numpy().reshape(-1, 16), slot_pos=r1['slot_pos'].cpu().numpy().reshape(-1, 8))
+    part, _ = check_expand(before, take(env), inputs, None, _host(r2), SENT, oracle_kw=K5, successors=(s1, suc2))
+    assert part == 6 * N1
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 5. capture
+def test_captured_into_a_graph():
+    """torch.cuda.graph around one expand(out=...): the call only enqueues; replayed after the env has stepped it equals an eager expand() of the new state"""
+    N = 300
+    env, _, _ = make_env(N, *np_states(N, 56000), obs_mode='state', **K5)
+    env.reset()
+    spread(env, 5, 6)
+    out = _sentinel_out(N)
+    env.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        env.expand(out=out)
+    assert all(bool((t.view(torch.uint8) == SENT).all()) for t in out.values())          # (capturing ran nothing)
+    for rnd in range(3):
+        spread(env, 3, 7 + rnd)
+        g.replay()
+        eager = env.expand()
+        for f in FIELDS:
+            assert torch.equal(out[f], eager[f]), (rnd, f)
+    before = take(env)
+    g.replay()
+    torch.cuda.synchronize()
+    check_expand(before, take(env), None, None, _host(out), SENT, oracle_kw=K5)
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 7. call order and arguments through ctypes
+def test_call_order_and_arguments_through_ctypes():
+    from gym_craftingworld_amd import CraftingWorldVecEnv, _lib as L
+    N = 8
+    env = CraftingWorldVecEnv(N, obs_mode='state', auto_reset=False, seed=3, **K5)
+    lib, h, st = env._lib, env._h, env._stream()
+    bufs = _sentinel_out(N)
+    vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
+    full = L.cw_expand_out(reward=vp(bufs['reward']), done=vp(bufs['done']), changed=vp(bufs['changed']), achieved=vp(bufs['achieved_mask']),
+                           hdr=vp(bufs['hdr']), slot_pos=vp(bufs['slot_pos']))
+    oh = torch.empty((N, 5, 5, 12), dtype=torch.uint8, device='cuda')
+    assert lib.cw_expand(h, None, None, None, N, C.byref(full), st) == L.CW_ERR_STATE and b'before cw_reset' in lib.cw_last_error()
+    assert lib.cw_export_onehot_states(h, vp(env.hdr), vp(env.slot_pos), N, vp(oh), st) == L.CW_ERR_STATE and b'before cw_reset' in lib.cw_last_error()
+    env.reset()
+    hdr, pos, eo = vp(env.hdr), vp(env.slot_pos), vp(torch.zeros(N, dtype=torch.int32, device='cuda'))
+    assert lib.cw_expand(h, None, None, None, N, C.byref(full), st) == L.CW_OK
+    assert lib.cw_expand(h, None, hdr, pos, 0, C.byref(full), st) == L.CW_OK                    # no states: nothing enqueued
+    one = lambda **kw: L.cw_expand_out(**kw)  # noqa: E731
+    invalid = [((None, None, None, None, N, C.byref(full)), b'engine'),
+               ((h, None, None, None, N, None), b'out'),
+               ((h, None, None, None, N, C.byref(one())), b'every field'),
+               ((h, None, hdr, pos, -1, C.byref(full)), b'n_states'),
+               ((h, None, hdr, pos, 2 ** 27 + 1, C.byref(full)), b'n_states'),
+               ((h, None, None, None, N - 1, C.byref(full)), b'num_envs'),
+               ((h, None, None, None, 6 * N, C.byref(full)), b'num_envs'),
+               ((h, None, hdr, None, N, C.byref(full)), b'hdr_in given without slot_pos_in'),
+               ((h, None, None, pos, N, C.byref(full)), b'slot_pos_in given without hdr_in'),
+               ((h, eo, None, None, N, C.byref(full)), b'env_of'),
+               ((h, None, vp(env.hdr, 8), pos, N - 1, C.byref(full)), b'hdr_in is not 16-byte aligned'),
+               ((h, None, hdr, vp(env.slot_pos, 2), N - 1, C.byref(full)), b'slot_pos_in is not 16-byte aligned'),
+               ((h, None, hdr, pos, N - 1, C.byref(one(hdr=vp(bufs['hdr'], 4)))), b'out->hdr is not 16-byte aligned'),
+               ((h, None, hdr, pos, N - 1, C.byref(one(reward=vp(bufs['reward']), slot_pos=vp(bufs['slot_pos'], 8)))), b'out->slot_pos is not 16-byte aligned')]
+    for args, word in invalid:
+        assert lib.cw_expand(*args, st) == L.CW_ERR_INVALID, word
+        assert word in lib.cw_last_error(), (word, lib.cw_last_error())
+    for args, word in [((None, hdr, pos, N, vp(oh)), b'engine'), ((h, None, pos, N, vp(oh)), b'hdr'), ((h, hdr, None, N, vp(oh)), b'slot_pos'),
+                       ((h, hdr, pos, N, None), b'out'), ((h, hdr, pos, -1, vp(oh)), b'n_states'), ((h, hdr, pos, 2 ** 27 + 1, vp(oh)), b'n_states'),
+                       ((h, vp(env.hdr, 1), pos, N - 1, vp(oh)), b'hdr is not 16-byte aligned'),
+                       ((h, hdr, vp(env.slot_pos, 6), N - 1, vp(oh)), b'slot_pos is not 16-byte aligned')]:
+        assert lib.cw_export_onehot_states(*args, st) == L.CW_ERR_INVALID, word
+        assert word in lib.cw_last_error(), (word, lib.cw_last_error())
+    assert lib.cw_export_onehot_states(h, hdr, pos, 0, vp(oh), st) == L.CW_OK
+    torch.cuda.synchronize()
+    assert env.expand_skipped == 0
+    env.close()
