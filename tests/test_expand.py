@@ -10,10 +10,12 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import DENSE, FIELDS, check_expand, decode, oracle_successors
+from expand_check import DENSE, FIELDS, POS_HELD, check_expand, decode, oracle_successors
 from masked_check import spread, take
 from oracle_replay import make_env, np_states, one_hot_of, same
-from test_snapshot import ENGINES, K5, N1
+from state_tables import oracle_frame as _oracle_frame, table_coverage, table_desired, wall_table
+from test_masked_shapes import _n_cu
+from test_snapshot import ENGINES, K5, N1, SIZES, k_of
 
 pytestmark = pytest.mark.gpu
 
@@ -131,42 +133,125 @@ def test_the_whole_local_transition_table(style, step_num):
     env.close()
 
 
+# ------------------------------------------------------------------------------------------------------------------------------ 1b. the table at every wall, and on large grids
+WALL_S = 8
+WALL_ANCHORS = [(0, 0), (0, 7), (7, 0), (7, 7), (0, 4), (4, 7), (7, 4), (4, 0)]     # the four corners and the four mid-edge cells
+
+
+@functools.lru_cache(maxsize=None)
+def _wall_table():
+    table = wall_table(WALL_S, WALL_ANCHORS, 75264, span='full')
+    return table, table_desired(table, dict(size=(WALL_S, WALL_S), max_steps=MAX1))
+
+
+@pytest.mark.parametrize('style', [None, 'subset'])
+def test_the_wall_table_on_every_wall(style):
+    """The table of test_the_whole_local_transition_table with the agent in each corner and in the middle of each edge of an 8 x 8 grid: 8 x 9 408 = 75 264
+    states, one env each.  Every move runs into its wall (the min(.., S - 1) clamp of Right and Down among them) and eval_task_edit follows the blocked
+    move; Right and Down are expand's own instances of the step.  What the table exercises is counted from the oracle's values before anything is compared."""
+    from gym_craftingworld_amd import CraftingWorldVecEnv
+    (grid, init, agent, hold, ach), des = _wall_table()
+    n = len(hold)
+    assert n == 75264
+    okw = dict(size=(WALL_S, WALL_S), max_steps=MAX1)
+    env = CraftingWorldVecEnv(n, obs_mode='state', reward_style=style, auto_reset=False, seed=5, **okw)
+    env.reset()
+    env.set_state(grid=grid, init_grid=init, agent_rc=agent.astype(np.uint8), hold=hold.astype(np.uint8), achieved=ach.astype(np.uint16),
+                  desired=des.astype(np.uint16), step_num=np.full(n, 3, np.int32))
+    before = take(env)
+    flags = _dense_of(before)['flags']
+    assert ((flags & ~1) == (2 if style else 0)).all()
+    states = dict(grid=grid, agent=agent, hold=hold, achieved=ach, desired=des, step_num=np.full(n, 3, np.int64), flags=flags)
+    suc = oracle_successors(states, init, okw)
+    cov = table_coverage(states, suc)
+    success = int((suc['reward'] == MAX1).sum())
+    print(cov, 'successes', success)
+    assert min(cov['gains']) >= 100 and min(cov['losses']) >= 400 and cov['changed'] >= 50000 and cov['unchanged'] >= 50000
+    assert min(cov['blocked_moves']) >= 10000 and success >= 10000
+    r = env.expand()
+    after = take(env)
+    part, skipped = check_expand(before, after, None, None, _host(r), SENT, oracle_kw=okw, successors=(states, suc))
+    assert (part, skipped) == (n, 0)
+    env.close()
+
+
+@pytest.mark.parametrize('S', [182, 255])
+def test_the_far_corner_table_on_large_grids(S):
+    """432 states at the three far corners of a 182 x 182 / 255 x 255 grid, one env each: slot cells above 32 767 (negative in the int16 tensors), rows and
+    columns above 127, the held / gone marks 510 above the largest cell.  Depth 1 against the oracle; depth 2 -- expand() of its own records -- for the
+    successors of Right and Down; the host path (slot_pos as numpy uint16) against the in-place one; one_hot_states of 864 records, several rounds of the
+    export's grid-stride loop; render_states of four of them."""
+    from gym_craftingworld_amd import CraftingWorldVecEnv
+    grid, init, agent, hold, ach = wall_table(S, [(S - 1, S - 1), (0, S - 1), (S - 1, 0)], 512)
+    n = len(hold)
+    assert n == 432
+    okw = dict(size=(S, S), max_steps=MAX1)
+    des = np.where((np.arange(n) % 2 == 0) & (ach != 0), ach, np.random.RandomState(S).randint(1, 512, n))      # every other goal: keep what is achieved
+    env = CraftingWorldVecEnv(n, obs_mode='state', auto_reset=False, seed=6, **okw)
+    env.reset()
+    env.set_state(grid=grid, init_grid=init, agent_rc=agent.astype(np.uint8), hold=hold.astype(np.uint8), achieved=ach.astype(np.uint16),
+                  desired=des.astype(np.uint16), step_num=np.full(n, 3, np.int32))
+    before = take(env)
+    s0 = dict(grid=grid, agent=agent, hold=hold, achieved=ach, desired=des, step_num=np.full(n, 3, np.int64), flags=_dense_of(before)['flags'])
+    suc1 = oracle_successors(s0, init, okw)
+    cov = table_coverage(s0, suc1)
+    above = int(((before['slot_pos'].view(np.uint16) > 32767) & (before['slot_pos'].view(np.uint16) < POS_HELD)).sum())
+    print(S, cov, 'slot cells above 32 767:', above, 'successes', int((suc1['reward'] == MAX1).sum()))
+    assert min(cov['gains']) >= 2 and min(cov['losses']) >= 10 and min(cov['blocked_moves']) >= 100 and cov['pickups'] >= 40 and cov['drops'] >= 40
+    assert above >= 300 and (agent.max(axis=1) >= 128).all() and (before['slot_pos'] < -2).sum() == above and (suc1['reward'] == MAX1).sum() >= 20
+    r1 = env.expand()
+    assert r1['slot_pos'].dtype == torch.int16
+    part, skipped = check_expand(before, take(env), None, None, _host(r1), SENT, oracle_kw=okw, successors=(s0, suc1))
+    assert (part, skipped) == (n, 0)
+    # ---- depth 2: 2 592 input states, the rows of the successors of Right and Down against the oracle
+    r2 = env.expand(hdr=r1['hdr'], slot_pos=r1['slot_pos'])
+    assert tuple(r2['hdr'].shape) == (6, 6 * n, 16)
+    after = take(env)
+    h1, h2 = _host(r1), _host(r2)
+    for a in (1, 2):
+        s1 = {k: suc1[k][a] for k in DENSE}
+        suc2 = oracle_successors(s1, init, okw)
+        part, _ = check_expand(before, after, dict(hdr=h1['hdr'][a], slot_pos=h1['slot_pos'][a]), None, {f: v[:, a * n:(a + 1) * n] for f, v in h2.items()}, SENT,
+                               oracle_kw=okw, successors=(s1, suc2))
+        assert part == n
+    host = env.expand(hdr=r1['hdr'], slot_pos=h1['slot_pos'].view(np.uint16))          # the host path: validated, copied, the same bytes
+    for f in FIELDS:
+        assert torch.equal(host[f], r2[f]), f
+    del r2, host, h2
+    # ---- the one-hot view of the successors of Up and Right: more than one round of the export's grid-stride loop
+    assert 2 * n * S * S > _n_cu() * 32 * 256
+    oh = env.one_hot_states(r1['hdr'][:2], r1['slot_pos'][:2])
+    assert tuple(oh.shape) == (2, n, S, S, 12)
+    for a in range(2):
+        same('one_hot_states of the successors of action %d' % a, 0, oh[a].cpu().numpy(), one_hot_of(suc1['grid'][a], suc1['agent'][a], suc1['hold'][a]))
+    frames = env.render_states(oh[0, :4])
+    img = np.stack([_oracle_frame(suc1['grid'][0, j], suc1['agent'][0, j], suc1['hold'][0, j], False) for j in range(4)])
+    same('render_states of the successors', 0, (frames.cpu().numpy() & 0xFF).astype(np.uint8), img)
+    env.close()
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ 2. against the engine's own step; 6. one-hot and frames
-def _oracle_frame(grid, agent, hold, alt):
-    from oracle.oracle import _lib
-    lib, u8p = _lib(), C.POINTER(C.c_uint8)
-    g = np.ascontiguousarray(grid, dtype=np.uint8)
-    s = g.shape[0]
-    out = np.empty((3 * s + 3, 3 * s, 3) if alt else (4 * s, 4 * s, 3), dtype=np.uint8)
-    fn = lib.cwo_render_alt if alt else lib.cwo_render
-    fn.argtypes = [C.c_int32, u8p, C.c_int32, C.c_int32, C.c_int32, u8p]
-    fn.restype = None
-    fn(s, g.ctypes.data_as(u8p), int(agent[0]), int(agent[1]), int(hold), out.ctypes.data_as(u8p))
-    return out
-
-
-@pytest.mark.parametrize('engine', list(ENGINES))
-def test_against_the_engines_own_step_on_packed_bytes(engine):
+def _against_the_engines_own_step(engine, S):
     """expand() of the current states, then the same successors the long way round: snapshot_save once, and for each action snapshot_load(with_stream=True)
     + step.  Without auto-reset the step's hdr, slot_pos, reward, done and achieved_mask equal row a of the result byte for byte; with auto-reset the
     outputs do everywhere and the records where the env did not finish -- the finished ones are the terminal states only expand() shows, checked against
     the oracle.  The one-hot view and the frame of every successor equal the oracle's."""
-    ekw = dict(ENGINES[engine])
+    ekw, K = dict(ENGINES[engine]), k_of(S)
     alt = ekw.get('raster', 'ray') == 'alt'
-    env, _, _ = make_env(N1, *np_states(N1, 52000), **ekw, **K5)
+    env, _, _ = make_env(N1, *np_states(N1, 52000), **ekw, **K)
     env.snapshot_reserve(N1)
     env.reset()
     spread(env, 9, 1)
     sn = env.get_state()['step_num']
-    sn[::5] = K5['max_steps'] - 1                                 # every fifth env one step before the time-out: successors that end the episode
+    sn[::5] = K['max_steps'] - 1                                 # every fifth env one step before the time-out: successors that end the episode
     env.set_state(step_num=sn)
     before = take(env)
     states = _dense_of(before)
-    suc = oracle_successors(states, before['state_init_grid'], K5)
+    suc = oracle_successors(states, before['state_init_grid'], K)
     assert suc['done'][:, ::5].all() and not suc['done'].all()
     r = env.expand()
     after = take(env)                                             # (every buffer, stream, frame and counter: check_expand compares them all)
-    check_expand(before, after, None, None, _host(r), SENT, oracle_kw=K5, successors=(states, suc))
+    check_expand(before, after, None, None, _host(r), SENT, oracle_kw=K, successors=(states, suc))
     rows = torch.arange(N1, dtype=torch.int32, device='cuda')
     env.snapshot_save(rows)
     for a in range(6):
@@ -180,19 +265,31 @@ def test_against_the_engines_own_step_on_packed_bytes(engine):
         assert torch.equal(env.hdr[keep], r['hdr'][a][keep]) and torch.equal(env.slot_pos[keep], r['slot_pos'][a][keep]), a
         if env.auto_reset:                                        # the terminal states: the oracle's (check_expand has compared them; here by name)
             fin = np.flatnonzero(suc['done'][a])
-            got = decode(r['hdr'][a].cpu().numpy()[fin], r['slot_pos'][a].cpu().numpy()[fin], K5['size'][0])
+            got = decode(r['hdr'][a].cpu().numpy()[fin], r['slot_pos'][a].cpu().numpy()[fin], S)
             for k in DENSE:
                 same('terminal %s of action %d' % (k, a), fin, got[k], suc[k][a][fin])
     # ---- 6. the one-hot view and the frame of every successor
     oh = env.one_hot_states(r['hdr'], r['slot_pos'])
-    assert tuple(oh.shape) == (6, N1, 5, 5, 12) and oh.dtype == torch.uint8
-    want = one_hot_of(suc['grid'].reshape(6 * N1, 5, 5), suc['agent'].reshape(6 * N1, 2), suc['hold'].reshape(6 * N1))
-    same('one_hot_states of the successors', 0, oh.cpu().numpy().reshape(6 * N1, 5, 5, 12), want)
-    frames = env.render_states(oh.reshape(6 * N1, 5, 5, 12)[:64])
-    img = np.stack([_oracle_frame(suc['grid'].reshape(-1, 5, 5)[j], suc['agent'].reshape(-1, 2)[j], suc['hold'].reshape(-1)[j], alt) for j in range(64)])
+    assert tuple(oh.shape) == (6, N1, S, S, 12) and oh.dtype == torch.uint8
+    want = one_hot_of(suc['grid'].reshape(6 * N1, S, S), suc['agent'].reshape(6 * N1, 2), suc['hold'].reshape(6 * N1))
+    same('one_hot_states of the successors', 0, oh.cpu().numpy().reshape(6 * N1, S, S, 12), want)
+    frames = env.render_states(oh.reshape(6 * N1, S, S, 12)[:64])
+    img = np.stack([_oracle_frame(suc['grid'].reshape(-1, S, S)[j], suc['agent'].reshape(-1, 2)[j], suc['hold'].reshape(-1)[j], alt) for j in range(64)])
     same('render_states of the successors', 0, (frames.cpu().numpy() & 0xFF).astype(np.uint8), img)
     assert torch.equal(env.one_hot_states(env.hdr, env.slot_pos), env.one_hot())
     env.close()
+
+
+@pytest.mark.parametrize('engine', list(ENGINES))
+def test_against_the_engines_own_step_on_packed_bytes(engine):
+    _against_the_engines_own_step(engine, 5)
+
+
+@pytest.mark.parametrize('size', [x for x in SIZES if x != 5])
+@pytest.mark.parametrize('engine', list(ENGINES))
+def test_against_the_engines_own_step_on_packed_bytes_at_size(engine, size):
+    """the same on 4 x 4, 7 x 7, 8 x 8 and 21 x 21 grids: below, at and above the size at which the full-frame engine changes painter, and the headline frame"""
+    _against_the_engines_own_step(engine, size)
 
 
 def test_host_outputs_engine():
@@ -372,4 +469,51 @@ def test_call_order_and_arguments_through_ctypes():
     assert lib.cw_export_onehot_states(h, hdr, pos, 0, vp(oh), st) == L.CW_OK
     torch.cuda.synchronize()
     assert env.expand_skipped == 0
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 8. the view kernels past their first round
+def test_grid_and_one_hot_exports_past_their_first_round():
+    """cw_export_grid_kernel / cw_export_onehot_kernel launch at most n_cu * 32 workgroups of 256 threads, one cell each, and loop: on a 255 x 255 grid with
+    3 envs more than one round holds, the second trip of the loop writes the last envs.  grid() and one_hot() of the current, goal and init state
+    against get_state()."""
+    S = 255
+    per_round = _n_cu() * 32 * 256
+    N = -(-per_round // (S * S)) + 3
+    assert N * S * S > per_round and (N - 3) * S * S >= per_round                  # (the last three envs lie wholly in the second round)
+    env, _, _ = make_env(N, *np_states(N, 57000), obs_mode='state', size=(S, S), max_steps=17)
+    env.reset()
+    spread(env, 3, 9)
+    st = env.get_state()
+    assert (st['agent_rc'] != st['init_agent_rc']).any() and len({tuple(a) for a in st['agent_rc'].tolist()}) > N // 2
+    same('grid()', 0, env.grid().cpu().numpy(), st['grid'])
+    for which, g, a, h in (('current', 'grid', 'agent_rc', st['hold']), ('goal', 'goal_grid', 'goal_agent_rc', np.zeros(N, np.uint8)),
+                           ('init', 'init_grid', 'init_agent_rc', np.zeros(N, np.uint8))):
+        same('one_hot(which=%r)' % which, 0, env.one_hot(which=which).cpu().numpy(), one_hot_of(st[g], st[a], h))
+    env.close()
+
+
+@pytest.mark.parametrize('raster', ['ray', 'alt'])
+def test_render_states_past_its_first_round(raster):
+    """cw_render_onehot_kernel / cw_render_onehot_alt_kernel launch at most 1 024 workgroups -- 4 096 waves, one state each -- and loop: 4 099 states of
+    4 x 4 cells, random contents as test_hip_parity.test_render_of_arbitrary_one_hot_states draws them, against the numpy restatements of the reference's
+    render(state); the last three, the second round, by name."""
+    from test_hip_parity import _reference_alt_render_of_any_state, _reference_render_of_any_state
+    ref = _reference_alt_render_of_any_state if raster == 'alt' else _reference_render_of_any_state
+    S, M = 4, 4099
+    assert M > 1024 * 4
+    rng = np.random.RandomState(13)
+    states = (rng.rand(M, S, S, 12) < np.array([0.02, 0.3, 0.08])[np.arange(M) % 3][:, None, None, None]).astype(np.uint8)
+    states[..., 8] = 0
+    for _ in range(3):
+        on = np.flatnonzero(rng.rand(M) < (1.0 if _ == 0 else 0.4))
+        states[on, rng.randint(S, size=len(on)), rng.randint(S, size=len(on)), 8] = 1
+    states[::4, :, :, 9:] = 0
+    env, _, _ = make_env(2, seed=3, obs_mode='state', raster=raster, size=(S, S), max_steps=17)
+    got = env.render_states(states).cpu().numpy().astype(np.int64)
+    want = np.stack([ref(st.astype(np.int64)) for st in states])
+    assert want.max() > 255 and tuple(got.shape) == (M,) + tuple(env.frame_shape)
+    same('render_states', 0, got, want)
+    for j in range(M - 3, M):
+        assert np.array_equal(got[j], want[j]), 'state %d, in the second round of the loop' % j
     env.close()

@@ -12,11 +12,18 @@ import torch
 from masked_check import masked_launch, spread, take
 from oracle_replay import FRAMES, make_env, np_states, oracle_kw, record_steps, same, same_states, snapshot
 from snapshot_check import check_load, check_save
+from state_tables import oracle_frame, painted_batch
 from test_masked_shapes import _engine, _n_cu, _width
 
 pytestmark = pytest.mark.gpu
 
 K5 = dict(size=(5, 5), max_steps=17)
+SIZES = [5, 4, 7, 8, 21]              # 7 / 8: the full-frame engine changes painter (gather up to 7, piece sweep from 8); 21: the headline frame
+
+
+def k_of(S):
+    """the configuration of the round-trip and expand tests at size S: max_steps stays 17, so 2 * 17 + 3 steps reset every env twice at any size"""
+    return dict(K5, size=(S, S))
 MENUS = [dict(), dict(selected_tasks=['ChopTree', 'MoveAxe', 'EatBread', 'GoToHouse'], number_of_tasks=2)]      # (the same reward rule: with_stream=False keeps the row's)
 
 
@@ -44,6 +51,7 @@ ENGINES = {'state_manual': dict(obs_mode='state', auto_reset=False),
            'dirty_ray_auto': dict(obs_mode='pixels_dirty', raster='ray'),
            'pixels_alt_auto': dict(obs_mode='pixels', raster='alt'),
            'state_auto_pool_menus': dict(obs_mode='state', fixed_init_state=3, task_menus=MENUS, env_menu=(np.arange(N1) % 2).astype(np.uint8))}
+SNAPSHOT_ENGINES = dict(ENGINES, pixels_ray_auto=dict(obs_mode='pixels', raster='ray'))      # the full-frame sweep of the ray raster (tests/test_expand.py runs ENGINES)
 
 
 def _rows_of_test_1():
@@ -61,15 +69,19 @@ def _rows_of_test_1():
     return save, load
 
 
-@pytest.mark.parametrize('with_stream', [True, False])
-@pytest.mark.parametrize('engine', list(ENGINES))
-def test_round_trip_and_fork_then_continued_against_the_oracle(engine, with_stream):
+def _frames_of(st, alt):
+    """the three frames of an oracle env's state() by the full-frame rasteriser -> {frame array of the engine: uint8 frame}"""
+    return {'observation': oracle_frame(st['grid'], st['agent'], st['hold'], alt), 'init_observation': oracle_frame(st['init_grid'], st['init_agent'], 0, alt),
+            'desired_goal': oracle_frame(st['goal_grid'], st['goal_agent'], 0, alt)}
+
+
+def _round_trip_and_fork(engine, with_stream, S):
     from oracle import OracleBatch, OracleEnv
-    ekw = dict(ENGINES[engine])
+    ekw, KW = dict(SNAPSHOT_ENGINES[engine]), k_of(S)
     raster, pixels, K = ekw.get('raster', 'ray'), ekw['obs_mode'] != 'state', ekw.get('fixed_init_state', 0)
-    env, keys, pos = make_env(N1, *np_states(N1, 31000), **ekw, **K5)
+    env, keys, pos = make_env(N1, *np_states(N1, 31000), **ekw, **KW)
     assert env.tuner_state()['lookahead'] == (1 if env.auto_reset else 0)
-    okw = oracle_kw(dict(K5, fixed_init_state=K), raster)
+    okw = oracle_kw(dict(KW, fixed_init_state=K), raster)
     per_env = [MENUS[int(m)] for m in ekw['env_menu']] if 'env_menu' in ekw else [dict()] * N1
     ora = OracleBatch(N1, rng_states=list(zip(keys, pos)), per_env_kwargs=per_env, **okw)
     env.snapshot_reserve(CAP1)
@@ -122,7 +134,11 @@ def test_round_trip_and_fork_then_continued_against_the_oracle(engine, with_stre
     ora._handles = (C.c_void_p * N1)(*[e._h for e in ora.envs])
     if with_stream:
         same_states(env, ora, frames=tuple(FRAMES) if pixels else (), tag='right after the load: ')
-    T = 2 * K5['max_steps'] + 3
+    elif pixels:                                                  # the frames the load painted: the oracle's rasteriser on the oracle's saved states
+        want = [_frames_of(o_saved[s], raster == 'alt') for s in src]
+        for k in FRAMES:
+            same('right after the load: ' + k, good, after[k][good], np.stack([w[k] for w in want]))
+    T = 2 * KW['max_steps'] + 3
     acts = torch.randint(0, 6, (T, N1), device='cuda', dtype=torch.uint8, generator=torch.Generator(device='cuda').manual_seed(3))
     r_host, d_host = _step_recorded(env, acts)
     _, o_rew, o_done = ora.rollout(acts.cpu().numpy().astype(np.int8), nthreads=16, record=True)
@@ -133,6 +149,19 @@ def test_round_trip_and_fork_then_continued_against_the_oracle(engine, with_stre
     snap['ep_no'] = snap['ep_no'] - ep_shift                      # (set_state keeps the oracle env's own episode count: the row's differs by a constant)
     same_states(snap, ora, frames=tuple(FRAMES) if pixels else (), tag='%d steps after the fork: ' % T)
     env.close()
+
+
+@pytest.mark.parametrize('with_stream', [True, False])
+@pytest.mark.parametrize('engine', list(ENGINES))
+def test_round_trip_and_fork_then_continued_against_the_oracle(engine, with_stream):
+    _round_trip_and_fork(engine, with_stream, 5)
+
+
+@pytest.mark.parametrize('with_stream', [True, False])
+@pytest.mark.parametrize('engine,size', [(e, s) for s in SIZES for e in SNAPSHOT_ENGINES if s != 5 or e not in ENGINES])
+def test_round_trip_and_fork_then_continued_against_the_oracle_at_size(engine, with_stream, size):
+    """the same on 4 x 4, 7 x 7, 8 x 8 and 21 x 21 grids, and at every size on the full-frame engine of the ray raster"""
+    _round_trip_and_fork(engine, with_stream, size)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ 2. every dealing width
@@ -345,4 +374,120 @@ def test_single_env_with_host_outputs_on_the_resident_path():
     assert again[:2] == first[:2] and np.array_equal(again[3], first[3])
     for k in first[2]:
         assert np.array_equal(again[2][k], first[2][k]), k
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 7. a load paints every state class
+N7 = 48
+PAINT_CASES = [('pixels_dirty', 5), ('pixels_dirty', 8), ('pixels_dirty', 21), ('pixels', 8), ('pixels', 21)]
+
+
+def _oracle_frames(grid, agent, hold, alt):
+    return np.stack([oracle_frame(grid[j], agent[j], hold[j], alt) for j in range(len(grid))])
+
+
+@pytest.mark.parametrize('obs_mode,size', PAINT_CASES)
+@pytest.mark.parametrize('raster', ['ray', 'alt'])
+def test_a_load_paints_every_state_class(raster, obs_mode, size):
+    """cw_snapshot_load_kernel<true> repaints the three frames of an env.  The states are state_tables.painted_states -- every hold on an empty cell and over
+    an object, sticks over sticks (the alt raster's doubled pixel), bread made, a house, rock and bread gone, every corner, cells 0 and S*S - 1 -- injected,
+    saved, stepped away from and loaded into the neighbouring env: the painted frames against the oracle's rasteriser on the injected states, not against
+    frames the engine painted earlier.  The full-frame engines sweep once more after a Drop."""
+    from expand_check import oracle_successors
+    N, S, alt = N7, size, raster == 'alt'
+    names, grid, init, agent, hold = painted_batch(S, N)
+    env, _, _ = make_env(N, *np_states(N, 58000), obs_mode=obs_mode, raster=raster, auto_reset=False, **k_of(S))
+    env.snapshot_reserve(N)
+    env.reset()
+    env.set_state(grid=grid, init_grid=init, agent_rc=agent, init_agent_rc=agent, hold=hold, step_num=np.full(N, 3, np.int32))
+    want_obs, want_init = _oracle_frames(grid, agent, hold, alt), _oracle_frames(init, agent, np.zeros(N, np.uint8), alt)
+    saved = take(env)
+    same('observation of the injected states', 0, saved['observation'], want_obs)
+    same('init_observation of the injected states', 0, saved['init_observation'], want_init)
+    save_rows = (N - 1 - np.arange(N)).astype(np.int32)
+    env.snapshot_save(_dev(save_rows))
+    check_save(saved, take(env))
+    spread(env, 6, 3)
+    before = take(env)
+    assert (before['observation'] != saved['observation']).reshape(N, -1).any(axis=1).sum() > N // 2
+    nxt = (np.arange(N) + 1) % N                                   # env i continues from what env i + 1 saved
+    load_rows = save_rows[nxt]
+    obs = env.snapshot_load(_dev(load_rows), with_stream=True)
+    after = take(env)
+    good, n_bad = check_load(saved, before, after, save_rows, load_rows, True, N)
+    assert len(good) == N and n_bad == 0
+    for j in np.flatnonzero((after['observation'] != want_obs[nxt]).reshape(N, -1).any(axis=1))[:4]:
+        print('observation of env %d differs: %s' % (j, names[nxt[j]]))
+    same('observation painted by the load', 0, obs['observation'].cpu().numpy(), want_obs[nxt])
+    same('init_observation painted by the load', 0, obs['init_observation'].cpu().numpy(), want_init[nxt])
+    same('desired_goal painted by the load', 0, after['desired_goal'], saved['desired_goal'][nxt])
+    if obs_mode == 'pixels':                                       # one sweep from the restored records
+        z = np.zeros(N, np.int64)
+        dense = dict(grid=grid[nxt], agent=agent[nxt].astype(np.int64), hold=hold[nxt].astype(np.int64), achieved=z, desired=z + 1, step_num=z + 3, flags=z)
+        suc = oracle_successors(dense, init[nxt], k_of(S))
+        assert 4 <= suc['changed'][5].sum() < N                    # (the oracle alone: some drop what they hold, most cannot)
+        env.step(torch.full((N,), 5, dtype=torch.uint8, device='cuda'))
+        same('the frame swept after a Drop', 0, env._observation()['observation'].cpu().numpy(),
+             _oracle_frames(suc['grid'][5], suc['agent'][5], suc['hold'][5], alt))
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 8. large grids
+@pytest.mark.parametrize('raster', ['ray', 'alt'])
+@pytest.mark.parametrize('S', [182, 255])
+def test_save_and_load_on_large_grids(S, raster):
+    """182 x 182 and 255 x 255, dirty-cell frames: agents in the far corners (rows and columns up to 254 in the header bytes), slot cells above 32 767, held and
+    gone marks.  Saved, stepped, loaded without the stream from the neighbour's row and with it from the env's own; the painted frames against the
+    oracle's rasteriser; three more steps against an OracleBatch brought to the same states by reset + set_state."""
+    from oracle import OracleBatch
+    N, alt = 6, raster == 'alt'
+    KW = dict(size=(S, S), max_steps=50)
+    names, grid, _, agent, hold = painted_batch(S, 22)
+    far = [j for j in range(22) if names[j].startswith('corner') and max(agent[j]) >= 128]
+    assert len(far) == N and sorted(hold[far].tolist()) == [0, 0, 0, 1, 2, 3]
+    grid, agent, hold = grid[far], agent[far], hold[far]
+    env, keys, pos = make_env(N, *np_states(N, 59000), obs_mode='pixels_dirty', raster=raster, auto_reset=False, **KW)
+    ora = OracleBatch(N, rng_states=list(zip(keys, pos)), **oracle_kw(KW, raster))
+    env.snapshot_reserve(N)
+    env.reset()
+    ora.reset()
+    same_states(env, ora, frames=tuple(FRAMES), tag='after the reset: ')
+    start = env.get_state()
+    env.set_state(grid=grid, agent_rc=agent, hold=hold)
+    want_obs = _oracle_frames(grid, agent, hold, alt)
+    saved = take(env)
+    assert (saved['slot_pos'] < -2).sum() >= N                     # cells above 32 767: negative in the int16 tensor
+    same('observation of the injected states', 0, saved['observation'], want_obs)
+    save_rows = (N - 1 - np.arange(N)).astype(np.int32)
+    env.snapshot_save(_dev(save_rows))
+    check_save(saved, take(env))
+    spread(env, 4, 5)
+    before = take(env)
+    assert not np.array_equal(before['hdr'], saved['hdr'])
+    nxt = (np.arange(N) + 1) % N
+    for with_stream, src in ((False, nxt), (True, np.arange(N))):
+        load_rows = save_rows[src]
+        env.snapshot_load(_dev(load_rows), with_stream=with_stream)
+        after = take(env)
+        good, n_bad = check_load(saved, before, after, save_rows, load_rows, with_stream, N)
+        assert len(good) == N and n_bad == 0
+        same('observation painted by the load', 0, after['observation'], want_obs[src])
+        for k, g, a in (('init_observation', 'init_grid', 'init_agent_rc'), ('desired_goal', 'goal_grid', 'goal_agent_rc')):
+            same(k + ' painted by the load', 0, after[k], _oracle_frames(start[g][src], start[a][src], np.zeros(N, np.uint8), alt))
+        before = after
+    for j, e in enumerate(ora.envs):                               # the oracle: its own episode, the injected state
+        v = e.view()
+        e.set_state(grid[j], e.state()['init_grid'], agent[j], hold[j], v.achieved, v.desired, v.step_num)
+    acts = torch.randint(0, 6, (3, N), device='cuda', dtype=torch.uint8, generator=torch.Generator(device='cuda').manual_seed(6))
+    r_host, d_host = _step_recorded(env, acts)
+    _, o_rew, o_done = ora.rollout(acts.cpu().numpy().astype(np.int8), nthreads=N, record=True)
+    same('reward of the steps after the load', 0, r_host.T, o_rew.T)
+    same('done of the steps after the load', 0, d_host.T, o_done.astype(bool).T)
+    snap = snapshot(env, frames=tuple(FRAMES))
+    same_ep = np.flatnonzero(~d_host.any(axis=0))                  # (the oracle's set_state forgets the agent's start cell until its next reset: there the
+    assert len(same_ep) >= N // 2                                  #  engine's is compared with what the reset gave, which the oracle has confirmed)
+    same('init_agent_rc', same_ep, snap['init_agent_rc'][same_ep], start['init_agent_rc'][same_ep])
+    snap['init_agent_rc'] = snap['init_agent_rc'].astype(np.int64)
+    snap['init_agent_rc'][same_ep] = -1
+    same_states(snap, ora, frames=tuple(FRAMES), tag='3 steps after the load: ')
     env.close()
