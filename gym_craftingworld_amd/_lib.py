@@ -60,6 +60,11 @@ class cw_expand_out(C.Structure):
                 ('slot_pos', C.c_void_p)]
 
 
+class cw_simulate_out(C.Structure):
+    _fields_ = [('ret', C.c_void_p), ('length', C.c_void_p), ('done', C.c_void_p), ('achieved', C.c_void_p), ('hdr', C.c_void_p),
+                ('slot_pos', C.c_void_p), ('rewards', C.c_void_p), ('dones', C.c_void_p)]
+
+
 class cw_profile(C.Structure):
     _fields_ = [('steps', C.c_int32), ('ms_step_kernel', C.c_float), ('ms_reset_kernel', C.c_float),
                 ('ms_render_kernel', C.c_float), ('ms_render_kernel_max', C.c_float), ('ms_render_kernel_min', C.c_float),
@@ -91,6 +96,7 @@ ABI = {
     'cw_snapshot_load': (C.c_int, [_VP, _VP, C.c_int32, _VP]),
     'cw_expand': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_expand_out), _VP]),
     'cw_export_onehot_states': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    'cw_simulate': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.POINTER(cw_simulate_out), _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
@@ -134,6 +140,8 @@ class cwh_tuning(C.Structure):
 cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variable's text or None (a pointer: ctypes cannot return a char* a callback made)
 
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
+CWH_SIM_OK, CWH_SIM_NO_FIELD, CWH_SIM_N_STATES, CWH_SIM_N_STEPS, CWH_SIM_PAIR, CWH_SIM_ENV_OF, CWH_SIM_MULTIPLE = range(7)
+CWH_SIM_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 
@@ -152,6 +160,8 @@ HOST_HELPERS = {
                                              C.POINTER(C.c_uint64)]),
     'cwh_snapshot_row_in_bank': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_expand_env_in_batch': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_simulate_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
+    'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),
     'cwh_sweep_periods': (None, [C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -35,6 +35,8 @@ hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, 
                                unsigned long long life_ticks, hipStream_t st);
 hipError_t cwk_launch_render_onehot(const CwParams *P, const uint8_t *onehot, int n_states, uint16_t *out, hipStream_t st);
 hipError_t cwk_launch_render_restore(const CwParams *P, const CwTuning *T, hipStream_t st);
+hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
+                               int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
 hipError_t cwk_launch_render_ext(const CwParams *P, const CwTuning *T, uint8_t *out, hipStream_t st);
 hipError_t cwk_launch_sweep_calib(const CwParams *P, const CwTuning *T, hipStream_t st);
@@ -913,6 +915,50 @@ int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const 
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos;
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     HIP_TRY(cwk_launch_expand(&e->P, env_of, h, p, n_states, &O, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// ------------------------------------------------------------------------------ simulate: T steps of M states along the caller's action sequences
+// cw_expand's shape: checks (the HIP-free ones are cw_host.cpp's cwh_simulate_args / cwh_ranges_overlap), then ONE kernel.  Writes nothing of the engine
+// but counters[7].
+int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, const uint8_t *actions,
+                int32_t n_steps, int32_t stop_at_done, const cw_simulate_out *out, cw_stream_t stream)
+{
+    if (!e || !out || !actions) return fail(CW_ERR_INVALID, "cw_simulate: null %s", !e ? "engine" : !out ? "out" : "actions");
+    const int n_fields = !!out->ret + !!out->length + !!out->done + !!out->achieved + !!out->hdr + !!out->slot_pos + !!out->rewards + !!out->dones;
+    switch (cwh_simulate_args(e->n, env_of != nullptr, hdr_in != nullptr, slot_pos_in != nullptr, n_states, n_steps, n_fields)) {
+    case CWH_SIM_OK: break;
+    case CWH_SIM_NO_FIELD: return fail(CW_ERR_INVALID, "cw_simulate: every field of out is null");
+    case CWH_SIM_N_STATES: return fail(CW_ERR_INVALID, "cw_simulate: n_states = %d must be 0 .. %d", n_states, CWH_SIM_MAX_STATES);
+    case CWH_SIM_N_STEPS: return fail(CW_ERR_INVALID, "cw_simulate: n_steps = %d must be 1 .. %d", n_steps, CWH_SIM_MAX_STEPS);
+    case CWH_SIM_PAIR:
+        return fail(CW_ERR_INVALID, "cw_simulate: %s given without %s", hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
+    case CWH_SIM_ENV_OF: return fail(CW_ERR_INVALID, "cw_simulate: env_of given without hdr_in");
+    default: return fail(CW_ERR_INVALID, "cw_simulate: n_states = %d must be a positive multiple of num_envs = %d without hdr_in", n_states, e->n);
+    }
+    if (misaligned16(hdr_in)) return fail(CW_ERR_INVALID, "cw_simulate: hdr_in is not 16-byte aligned");
+    if (misaligned16(slot_pos_in)) return fail(CW_ERR_INVALID, "cw_simulate: slot_pos_in is not 16-byte aligned");
+    if (misaligned16(out->hdr)) return fail(CW_ERR_INVALID, "cw_simulate: out->hdr is not 16-byte aligned");
+    if (misaligned16(out->slot_pos)) return fail(CW_ERR_INVALID, "cw_simulate: out->slot_pos is not 16-byte aligned");
+    // the records the kernel reads: the caller's n_states, or the engine's own num_envs
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    const uint64_t in_bytes = 16ull * (uint64_t)(hdr_in ? n_states : e->n), out_bytes = 16ull * (uint64_t)n_states;
+    const void *const outs[2] = {out->hdr, out->slot_pos};
+    for (int k = 0; k < 2; k++)
+        if (outs[k] && (cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k], out_bytes, (uint64_t)(uintptr_t)h, in_bytes) ||
+                        cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k], out_bytes, (uint64_t)(uintptr_t)p, in_bytes)))
+            return fail(CW_ERR_INVALID, "cw_simulate: out->%s overlaps the records read", k ? "slot_pos" : "hdr");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_simulate called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    CwSimulateOut O;
+    O.ret = out->ret; O.length = out->length; O.done = out->done; O.achieved = out->achieved;
+    O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.rewards = out->rewards; O.dones = out->dones;
+    HIP_TRY(cwk_launch_simulate(&e->P, env_of, h, p, hdr_in ? 0 : 1, n_states, actions, n_steps, stop_at_done ? 1 : 0, &O, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

@@ -176,6 +176,25 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
 int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity) { return cwh_snapshot_row_ok(row, capacity); }
 int cwh_expand_env_in_batch(int32_t env, int32_t num_envs) { return cwh_expand_env_ok(env, num_envs); }
 
+// ------------------------------------------------------------------------------ cw_simulate's argument rules
+int cwh_simulate_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields)
+{
+    if (n_out_fields <= 0) return CWH_SIM_NO_FIELD;
+    if (n_states < 0 || n_states > CWH_SIM_MAX_STATES) return CWH_SIM_N_STATES;
+    if (n_steps < 1 || n_steps > CWH_SIM_MAX_STEPS) return CWH_SIM_N_STEPS;
+    if (!has_hdr_in != !has_slot_pos_in) return CWH_SIM_PAIR;
+    if (has_env_of && !has_hdr_in) return CWH_SIM_ENV_OF;
+    if (!has_hdr_in && (num_envs <= 0 || n_states <= 0 || n_states % num_envs != 0)) return CWH_SIM_MULTIPLE;
+    return CWH_SIM_OK;
+}
+
+int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)
+{
+    if (!a_bytes || !b_bytes) return 0;
+    const uint64_t a_end = a + a_bytes < a ? UINT64_MAX : a + a_bytes, b_end = b + b_bytes < b ? UINT64_MAX : b + b_bytes;
+    return a < b_end && b < a_end;
+}
+
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule
 static double period_ns(int32_t sweep_waves, double tb_per_s) { return (double)sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }
 void cwh_sweep_periods(double rate, int32_t sweep_waves, double head_notch, double busy_notch, int32_t *period16, int32_t *period16_head, int32_t *period16_busy)

@@ -52,6 +52,16 @@ int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity);       // (the same,
 static inline CWH_HOST_DEVICE int cwh_expand_env_ok(int32_t env, int32_t num_envs) { return env >= 0 && env < num_envs; }
 int cwh_expand_env_in_batch(int32_t env, int32_t num_envs);        // (the same, exported for the CPU tests)
 
+// ---- cw_simulate's argument rules that need no HIP (cw_engine.cpp: cw_simulate turns the code into its error text), in the order they are tested:
+// some output field, 0 <= n_states <= 2^27, 1 <= n_steps <= 32 767, hdr_in and slot_pos_in together, env_of only with them, and without them (the
+// engine's own states, broadcast) n_states a positive multiple of num_envs.  has_*: the pointer is not null; n_out_fields: how many fields of out are not.
+#define CWH_SIM_MAX_STATES (1 << 27)
+#define CWH_SIM_MAX_STEPS 32767     // with max_steps <= 65 535 the int32 sum of n_steps rewards cannot overflow
+enum { CWH_SIM_OK = 0, CWH_SIM_NO_FIELD = 1, CWH_SIM_N_STATES = 2, CWH_SIM_N_STEPS = 3, CWH_SIM_PAIR = 4, CWH_SIM_ENV_OF = 5, CWH_SIM_MULTIPLE = 6 };
+int cwh_simulate_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields);
+// the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
+int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
+
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).
 typedef struct cwh_guard {

@@ -15,6 +15,8 @@
 //                     same way by a device array of row numbers.
 //   cw_expand_kernel  the successors of all six actions of M states (the engine's own or packed records of the caller's), one lane per (action, state) pair with
 //                     the action uniform across a wave; writes nothing of the engine.  cw_export_onehot_states_kernel: the one-hot view of such records.
+//   cw_simulate_kernel  T steps of M such states along M action sequences of the caller's, one lane per state, the state in registers throughout, the
+//                     action bytes fetched a block of steps ahead; writes nothing of the engine.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -650,6 +652,95 @@ __global__ __launch_bounds__(256) void cw_expand_kernel(CwParams P, const int32_
     case 5: expand_one<5>(P, hdr_in, pos_in, j, env, row, O); break;
     default: break;
     }
+}
+
+// ------------------------------------------------------------------------------------ simulate
+// cw_simulate: T steps of n_states states along the caller's action sequences, with no env touched -- cw_expand's input handling and purity crossed with
+// cw_rollout_kernel's register-resident loop.  One lane per state: its header, eight slots and its env's init_pos (one 16-byte load up front, not lazily
+// inside the loop) stay in registers for the whole call.  No LDS.  The actions differ per lane, so step_env runs both sides of its branches predicated, as
+// in the step kernels.  own != 0: the records are the engine's own, BROADCAST -- state j reads record j % n_envs; else the caller's record j of env
+// j % n_envs or env_of[j], an entry an index only behind cwh_expand_env_ok (cw_expand_kernel's rules: negative = no part, too large = skipped and counted
+// in counters[7] once a wave by ballot).  A state that takes no part writes no row, trace rows included.
+// The ACTION BYTES are the only loads inside the loop, and they do not depend on the state: they are fetched CW_SIM_BLOCK steps at a time, one block AHEAD
+// of the steps that use them -- the eight loads of block b + 1 (each one coalesced 64-byte run per wave in the step-major layout; the last block's clamped
+// to row T - 1) are issued after block b's bytes have been packed into two registers and before block b's first step, so only the very first block's
+// round trip is waited for and T steps cost one memory latency, not T (cw_rollout_kernel loads inside its loop and leaves the overlap to the compiler).
+// The disassembly shows it: the first eight global_load_ubyte stand with the three record loads ahead of the loop; inside it the s_waitcnt vmcnt for a
+// block's bytes sit at its packing, the next block's eight global_load_ubyte follow at once, and the block's eight steps (unrolled by the compiler) come
+// behind them.
+// stop_at_done: a lane whose state has ended is FROZEN by selection -- the step still runs, its results are dropped -- never by a divergent exit; a wave
+// whose lanes have all ended leaves the loop at the next block boundary and writes the reward-0 / done-0 trace rows that remain.
+#define CW_SIM_BLOCK 8
+__global__ __launch_bounds__(256) void cw_simulate_kernel(CwParams P, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                          const uint4 *__restrict__ pos_in, int own, int n_states, const uint8_t *__restrict__ actions,
+                                                          int T, int stop_at_done, CwSimulateOut O)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
+    int env = -1;
+    bool skipped = false;
+    if (j < n_states) {
+        if (env_of) {
+            const int32_t v = env_of[j];
+            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
+            else skipped = v >= 0;
+        } else {
+            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
+        }
+    }
+    const unsigned long long m_skip = CW_BALLOT(skipped);
+    if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
+    if (env < 0) return;
+    const size_t M = (size_t)n_states;
+    const int src = own ? env : j;
+    uint4 h = hdr_in[src];
+    uint32_t sp[8];
+    unpack_pos(pos_in[src], sp);
+    const uint4 ip = P.init_pos[env];
+    const uint8_t *const ap = actions + j;
+    uint32_t raw[CW_SIM_BLOCK];
+#pragma unroll
+    for (int k = 0; k < CW_SIM_BLOCK; k++) raw[k] = ap[(size_t)min(k, T - 1) * M];
+    int32_t ret = 0, length = T;
+    bool active = true, any_done = false;
+    int t0 = 0;
+    for (; t0 < T; t0 += CW_SIM_BLOCK) {
+        const uint32_t lo = raw[0] | (raw[1] << 8) | (raw[2] << 16) | (raw[3] << 24), hi = raw[4] | (raw[5] << 8) | (raw[6] << 16) | (raw[7] << 24);
+        if (t0 + CW_SIM_BLOCK < T) {                                      // the next block's bytes: in flight while this block steps
+#pragma unroll
+            for (int k = 0; k < CW_SIM_BLOCK; k++) raw[k] = ap[(size_t)min(t0 + CW_SIM_BLOCK + k, T - 1) * M];
+        }
+        if (stop_at_done && !CW_BALLOT(active)) break;                    // every state of the wave has ended
+        const int n = min(CW_SIM_BLOCK, T - t0);
+        for (int k = 0; k < n; k++) {
+            const int t = t0 + k;
+            const int a = (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xFFu);
+            uint4 h2 = h;
+            uint32_t sp2[8];
+#pragma unroll
+            for (int s = 0; s < 8; s++) sp2[s] = sp[s];
+            const CwStepOut o = step_env(P, h2, sp2, a, [&]() { return ip; });
+            const bool done_now = active && o.done;
+            h.x = active ? h2.x : h.x; h.y = active ? h2.y : h.y; h.z = active ? h2.z : h.z; h.w = active ? h2.w : h.w;      // (word by word: registers)
+#pragma unroll
+            for (int s = 0; s < 8; s++) sp[s] = active ? sp2[s] : sp[s];
+            ret += active ? o.reward : 0;
+            length = (done_now && !any_done) ? t + 1 : length;
+            any_done = any_done || done_now;
+            if (O.rewards) O.rewards[(size_t)t * M + j] = active ? o.reward : 0;
+            if (O.dones) O.dones[(size_t)t * M + j] = done_now ? 1 : 0;
+            if (stop_at_done) active = active && !o.done;
+        }
+    }
+    for (int t = t0; t < T; t++) {                                        // (a wave that left early: the rows after every state's end)
+        if (O.rewards) O.rewards[(size_t)t * M + j] = 0;
+        if (O.dones) O.dones[(size_t)t * M + j] = 0;
+    }
+    if (O.ret) O.ret[j] = ret;
+    if (O.length) O.length[j] = length;
+    if (O.done) O.done[j] = any_done ? 1 : 0;
+    if (O.achieved) O.achieved[j] = (uint16_t)(h.y & 0xFFFFu);
+    if (O.hdr) O.hdr[j] = h;
+    if (O.pos) O.pos[j] = pack_pos(sp);
 }
 
 // ------------------------------------------------------------------------------------ reset
@@ -2398,6 +2489,15 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
 hipError_t cwk_launch_refill(const CwParams *P, const CwTuning *T, int all_envs, hipStream_t st)
 {
     hipLaunchKernelGGL(cw_refill_kernel, dim3(cw_reset_grid(*T, P->n_envs)), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, all_envs);
+    return hipGetLastError();
+}
+
+// cw_simulate: one launch, one lane per state
+hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
+                               int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_simulate_kernel, dim3((unsigned)((n_states + 255) / 256)), dim3(256), 0, st, *P, env_of, hdr, pos, own, n_states, actions, n_steps,
+                       stop_at_done, *O);
     return hipGetLastError();
 }
 

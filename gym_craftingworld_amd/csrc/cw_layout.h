@@ -102,6 +102,18 @@ struct CwExpandOut {
     uint4 *pos;              // [6][M] successor slot positions
 };
 
+// Where cw_simulate_kernel leaves the outcome of T steps of M states (the public cw_simulate_out with the records typed).  A null field is not written.
+struct CwSimulateOut {
+    int32_t *ret;            // [M] sum of the rewards of the steps taken
+    int32_t *length;         // [M] 1 + index of the first done step, T if none
+    uint8_t *done;           // [M]
+    uint16_t *achieved;      // [M]
+    uint4 *hdr;              // [M] record after the last step taken
+    uint4 *pos;              // [M]
+    int32_t *rewards;        // [T][M] step-major trace
+    uint8_t *dones;          // [T][M]
+};
+
 // Everything the kernels need, passed by value.
 struct CwParams {
     // per-env state (SoA of 16-byte records unless noted)
@@ -148,7 +160,7 @@ struct CwParams {
                                   // observation array saw (cw_render_pieces_kernel: what kind of step does it follow?), [5] PRIVATE: resets of
                                   // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot save / load
                                   // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); [7] public: states cw_expand_kernel
-                                  // skipped for an env index at or above n_envs; 8 words allocated
+                                  // or cw_simulate_kernel skipped for an env index at or above n_envs; 8 words allocated
     const CwMenuDev *menus;
     // constants
     int32_t n_envs;

@@ -204,6 +204,52 @@ def expand_args(num_envs, hdr, slot_pos, env_of):
     return m
 
 
+SIMULATE_FIELDS = ('ret', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'rewards', 'dones')
+SIMULATE_MAX_STEPS = 32767
+
+
+def _simulate_tm(num_envs, shape, dtype, m):
+    """simulate_args on the actions' (shape, numpy dtype): -> T.  m: the number of records, None for the engine's own states (the broadcast form)"""
+    num_envs, shape = int(num_envs), tuple(int(s) for s in shape)
+    if not np.issubdtype(np.dtype(dtype), np.integer):
+        raise ValueError('actions must be integers (uint8 goes over in place), got %s' % np.dtype(dtype))
+    if m is None:
+        if len(shape) == 2 and shape[1] > 0 and shape[1] % num_envs == 0:
+            m = shape[1]
+        elif len(shape) == 3 and shape[1] > 0 and shape[2] == num_envs:
+            m = shape[1] * shape[2]
+        else:
+            raise ValueError('actions must be [T, K * num_envs] or [T, K, num_envs] with K >= 1 and num_envs = %d, got %s' % (num_envs, shape))
+        if m > 2 ** 27:
+            raise ValueError('%d states: at most 2**27 in one call' % m)
+    elif len(shape) < 2 or int(np.prod(shape[1:], dtype=np.int64)) != m:
+        raise ValueError('actions must be [T, M] with one column per record (M = %d), got %s' % (m, shape))
+    if not 1 <= shape[0] <= SIMULATE_MAX_STEPS:
+        raise ValueError('T = %d steps: 1 .. %d in one call' % (shape[0], SIMULATE_MAX_STEPS))
+    return shape[0], m
+
+
+def simulate_actions(a):
+    """actions on the host-validated path of simulate(): integers of any width -> contiguous uint8; ValueError for another dtype or a value outside 0 .. 255
+    (0..5 act, everything above is the no-op; nothing wraps into range)"""
+    a = np.asarray(a)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('actions must be integers (uint8 goes over in place), got %s' % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 255):
+        raise ValueError('actions must lie in 0 .. 255 (0..5 act, the rest is the no-op), got %d .. %d' % (int(a.min()), int(a.max())))
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def simulate_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of):
+    """What cw_simulate is handed, validated on the host: -> (T, M).  actions_shape_dtype: the actions' (shape, dtype) -- integers, [T, M], or without
+    records [T, K * num_envs] / [T, K, num_envs] (the broadcast form: plan k of env i in column k * num_envs + i); T = 1 .. 32 767.  hdr / slot_pos / env_of:
+    numpy inputs under expand_args' rules (both records or neither, env_of only with them, IndexError for an entry >= num_envs); with records M is their
+    number and the actions hold one column each.  ValueError for everything else."""
+    shape, dtype = actions_shape_dtype
+    m = expand_args(num_envs, hdr, slot_pos, env_of)
+    return _simulate_tm(num_envs, shape, dtype, None if hdr is None else m)
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -622,7 +668,7 @@ class CraftingWorldVecEnv:
     # ------------------------------------------------------------------ looking one step ahead
     @property
     def expand_skipped(self):
-        """how many states expand() has skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
+        """how many states expand() and simulate() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
         return int(self._counters_raw[7].item())
 
     _NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.int8: np.int8}
@@ -703,6 +749,58 @@ class CraftingWorldVecEnv:
         vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         self._expand_keepalive = (hdr, slot_pos, env_of, out)
         L.check(self._lib.cw_expand(self._h, vp(env_of), vp(hdr), vp(slot_pos), m, C.byref(o), self._stream()), 'cw_expand', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
+
+    # ------------------------------------------------------------------ trying plans
+    def simulate(self, actions, hdr=None, slot_pos=None, env_of=None, *, stop_at_done=True, fields=None, out=None):
+        """What would these action sequences do from here?  (cw_simulate: one kernel that keeps every state in registers for all T steps, no host round
+        trip, capturable; no env is touched and no RNG stream drawn from.)  actions: uint8 [T, M] -- state j steps through actions[:, j]; an id above 5
+        is step()'s state-preserving no-op.  Without records the envs' current states are BROADCAST: actions [T, K * N] or [T, K, N] try K plans per
+        env, plan k of env i in column k * N + i, with no copy of the records.  With hdr [..., 16] / slot_pos [..., 8] / env_of (expand()'s rules: env
+        j % num_envs or env_of[j], a negative entry takes no part and none of its rows is written, an entry >= num_envs is skipped by the kernel and
+        counted in expand_skipped) the states are the caller's and actions hold one column per record.  A contiguous uint8 tensor on the env's device
+        goes over in place; other integer inputs are validated and converted on the host (a value outside 0..255: ValueError).
+        stop_at_done=True: a state's first done step is its last, as on an auto-reset engine minus the reset; False: every state takes all T steps, as
+        the reference keeps stepping a finished env.  -> a dict of device tensors: 'ret' int32 [M] (sum of the rewards of the steps taken), 'length'
+        int32 [M] (1 + the first done step, T if none), 'done' bool [M], 'achieved_mask' [M], 'hdr' uint8 [M, 16] / 'slot_pos' int16 [M, 8] (the
+        record after the last step taken, byte for byte what step() leaves on an auto_reset=False engine) and, only when named in `fields`, the traces
+        'rewards' int32 [T, M] / 'dones' bool [T, M] (rows after a stopped state's end: 0 / False).  fields: a subset of SIMULATE_FIELDS (default: the
+        six per-state ones).  out: a dict returned by an earlier call with the same T, M and fields, written again."""
+        names = SIMULATE_FIELDS[:6] if fields is None else tuple(fields)
+        if not names or any(f not in SIMULATE_FIELDS for f in names) or len(set(names)) != len(names):
+            raise ValueError('fields must be a non-empty subset of %s' % (SIMULATE_FIELDS,))
+        own = hdr is None and slot_pos is None
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        if self._in_place(actions, (torch.uint8,)):
+            T, m = _simulate_tm(self.num_envs, actions.shape, np.uint8, None if own else m)
+        else:
+            a = actions.cpu().numpy() if torch.is_tensor(actions) else np.asarray(actions)
+            T, m = _simulate_tm(self.num_envs, a.shape, a.dtype, None if own else m)
+            actions = torch.as_tensor(simulate_actions(a)).to(self.device)
+        spec = {'ret': ((m,), torch.int32), 'length': ((m,), torch.int32), 'done': ((m,), torch.bool), 'achieved_mask': ((m,), self.achieved_mask.dtype),
+                'hdr': ((m, 16), torch.uint8), 'slot_pos': ((m, 8), self.slot_pos.dtype), 'rewards': ((T, m), torch.int32), 'dones': ((T, m), torch.bool)}
+        if out is None:
+            out = {f: torch.empty(spec[f][0], dtype=torch.uint8 if spec[f][1] is torch.bool else spec[f][1], device=self.device) for f in names}
+            out = {f: t.view(torch.bool) if spec[f][1] is torch.bool else t for f, t in out.items()}
+        else:
+            if set(out) != set(names):
+                raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names)))
+            for f in names:
+                t = out[f]
+                if (type(t) is not torch.Tensor or tuple(t.shape) != spec[f][0] or t.dtype != spec[f][1] or t.device != self.device
+                        or not t.is_contiguous()):
+                    raise ValueError('out[%r] must be a contiguous %s tensor %s on %s' % (f, spec[f][1], spec[f][0], self.device))
+        if m == 0:
+            return out
+        ptr = lambda f: C.c_void_p(out[f].data_ptr()) if f in out else None  # noqa: E731
+        o = L.cw_simulate_out(ret=ptr('ret'), length=ptr('length'), done=ptr('done'), achieved=ptr('achieved_mask'), hdr=ptr('hdr'),
+                              slot_pos=ptr('slot_pos'), rewards=ptr('rewards'), dones=ptr('dones'))
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self._simulate_keepalive = (actions, hdr, slot_pos, env_of, out)
+        L.check(self._lib.cw_simulate(self._h, vp(env_of), vp(hdr), vp(slot_pos), m, vp(actions), T, 1 if stop_at_done else 0, C.byref(o),
+                                      self._stream()), 'cw_simulate', self._lib)
         if self.host_outputs:
             self._sync()
         return out

@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -127,7 +127,7 @@ typedef struct cw_buffer_table {
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
                               *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
-                              *      for a bad row number, [7] counts the states a cw_expand skipped for an env index at or above num_envs.
+                              *      for a bad row number, [7] counts the states skipped by cw_expand or cw_simulate for an env index at or above num_envs.
                               *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
@@ -296,6 +296,44 @@ int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const 
  * argument, n_states < 0 or above 2^27, a misaligned hdr / slot_pos; CW_ERR_STATE before the first cw_reset / cw_checkpoint_load. */
 int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states,
                             uint8_t *out /* [n_states][S][S][12] */, cw_stream_t stream);
+
+/* --- trying plans: T steps of M states along M action sequences of the caller's, with no env touched (random shooting, CEM, MPC, MCTS leaf rollouts, beam
+ * search).  The multi-step companion of cw_expand: the same pure step function, each state kept in registers for the whole sequence, ONE kernel.
+ * M = n_states, T = n_steps.  State j steps through actions[t * M + j] for t = 0 .. T-1 (DEVICE uint8, step-major like cw_rollout's, only read).  An action
+ * id above 5 is the state-preserving no-op of cw_step (step_num + 1, reward -1); it is not counted anywhere. */
+typedef struct cw_simulate_out {  /* DEVICE pointers (host_outputs engines: or GPU-mapped host memory); NULL = not written; all NULL: CW_ERR_INVALID */
+    int32_t  *ret;       /* [M]      sum of the rewards of the steps TAKEN                                   */
+    int32_t  *length;    /* [M]      1 + index of the first step that returned done; n_steps if none did     */
+    uint8_t  *done;      /* [M]      some step returned done                                                 */
+    uint16_t *achieved;  /* [M]      achieved mask after the last step taken                                 */
+    uint8_t  *hdr;       /* [M][16]  record after the last step taken; 16-byte aligned                       */
+    uint16_t *slot_pos;  /* [M][8]   16-byte aligned                                                         */
+    int32_t  *rewards;   /* [T][M]   per-step trace, step-major like cw_rollout's                            */
+    uint8_t  *dones;     /* [T][M]                                                                           */
+} cw_simulate_out;
+/* hdr_in != NULL: n_states records of the caller's, exactly as cw_expand takes them: hdr_in [M][16] and slot_pos_in [M][8] (both required, both 16-byte
+ *   aligned, device memory, only read); env_of == NULL: state j belongs to env j % num_envs; env_of != NULL: DEVICE int32[n_states] -- a negative entry:
+ *   the state takes no part and NO output row of it is written, its trace rows [t][j] included; an entry >= num_envs is SKIPPED: its rows are not written
+ *   either and counters[7] is incremented once.  No entry becomes an address without that check.
+ * hdr_in == NULL: the engine's CURRENT states, BROADCAST: slot_pos_in and env_of must be NULL, n_states must be a positive multiple of num_envs, and state
+ *   j is env j % num_envs -- K candidate plans per env are n_states = K * num_envs, plan k of env i in row k * num_envs + i, with no copy of the records.
+ * stop_at_done != 0: a state's first done step is its last -- the episode ends there, as on an auto-reset engine, minus the reset.  hdr, slot_pos,
+ *   achieved, ret and length are those of that step; the trace row of the ending step holds its reward and done 1, the rows after it reward 0 and done 0.
+ * stop_at_done == 0: every state takes all T steps, as the reference keeps stepping a finished env (ray.py:367): ret sums all T rewards, length is still
+ *   1 + the first done step (T if none), done: some step returned done.
+ * The final record is byte for byte what the same number of cw_step calls leave in hdr / slot_pos on an auto_reset == 0 engine (step_num saturating, flag
+ *   bit 0 cleared, the success count in flag bits 2-15, the menu byte kept), and what chaining cw_expand and picking the action's row each time gives.
+ *   out->hdr / out->slot_pos must not overlap the records read.  Records are never used as addresses (cw_expand's rule for impossible records holds).
+ * PURE: nothing of the engine is written except counters[7], and that only for a skipped state; nothing is drawn from any RNG stream.
+ * Enqueues ONE kernel (cw_simulate_kernel: one lane per state) on `stream` -- no host synchronisation, no allocation -- and can be captured into a HIP graph
+ *   with cw_step / cw_expand / cw_snapshot_*.  Every obs_mode, with and without auto_reset, host_outputs engines included.  n_states == 0 (with hdr_in):
+ *   CW_OK, nothing enqueued.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID: a null engine, out or actions, all eight fields
+ *   NULL, n_states < 0 or above 2^27, n_steps < 1 or above 32 767 (with max_steps <= 65 535 the int32 sum then cannot overflow), n_states not a positive
+ *   multiple of num_envs without hdr_in, hdr_in without slot_pos_in or the reverse, env_of without hdr_in, a misaligned hdr_in / slot_pos_in / out->hdr /
+ *   out->slot_pos, out->hdr or out->slot_pos overlapping the records read.  (65 536 envs, 21x21, launch included: 22 us for 8 steps, 83 us for 64; 16 plans per env: 62 / 359 us: tools/measure_simulate.py, profiles/r08_simulate.txt.) */
+int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states,
+                const uint8_t *actions /* DEVICE uint8 [n_steps][n_states] */, int32_t n_steps, int32_t stop_at_done,
+                const cw_simulate_out *out, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
