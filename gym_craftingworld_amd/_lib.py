@@ -97,6 +97,7 @@ ABI = {
     'cw_expand': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_expand_out), _VP]),
     'cw_export_onehot_states': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_simulate': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.POINTER(cw_simulate_out), _VP]),
+    'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
@@ -144,6 +145,7 @@ CWH_SIM_OK, CWH_SIM_NO_FIELD, CWH_SIM_N_STATES, CWH_SIM_N_STEPS, CWH_SIM_PAIR, C
 CWH_SIM_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
+CWH_ALT_NO_PIXEL = 0xFFFFFFFF
 
 # the engine's HIP-free host logic (csrc/cw_host.h: MT19937 state conversion, DLPack, dense views, checkpoint sizes, the guard's decisions), exported for
 # the tests of the host logic -- the same table binds libcw_host_asan.so, the ASAN/UBSAN build of cw_host.cpp alone (bind_host_helpers)
@@ -160,6 +162,7 @@ HOST_HELPERS = {
                                              C.POINTER(C.c_uint64)]),
     'cwh_snapshot_row_in_bank': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_expand_env_in_batch': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_alt_pixel_offset_of': (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     'cwh_simulate_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),

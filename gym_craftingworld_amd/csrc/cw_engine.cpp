@@ -29,6 +29,8 @@ hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const 
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st);
 hipError_t cwk_launch_expand(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, const CwExpandOut *O, hipStream_t st);
 hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, int n_states, uint8_t *out, hipStream_t st);
+hipError_t cwk_launch_render_records(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, const uint8_t *mask, int n_states, uint8_t *out,
+                                     hipStream_t st);
 hipError_t cwk_launch_pool(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_seed(const CwParams *P, const uint32_t *seeds_dev, hipStream_t st);
 hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, int paint_dirty, unsigned long long idle_ticks,
@@ -978,6 +980,35 @@ int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *sl
     PARK(e);
     if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
     HIP_TRY(cwk_launch_export_onehot_states(&e->P, &e->tune, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out, (hipStream_t)stream));
+    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    return CW_OK;
+}
+
+// ------------------------------------------------------------------------------ render_records: the frames of packed records, straight from the records
+// cw_export_onehot_states' shape: checks, then ONE kernel.  PURE: of the engine only size and raster are read, nothing of it is written (no counter either).
+int cw_render_records(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, const uint8_t *mask, int32_t n_states, uint8_t *out_frames,
+                      cw_stream_t stream)
+{
+    if (!e || !hdr || !slot_pos || !out_frames)
+        return fail(CW_ERR_INVALID, "cw_render_records: null %s", !e ? "engine" : !hdr ? "hdr" : !slot_pos ? "slot_pos" : "out_frames");
+    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES)
+        return fail(CW_ERR_INVALID, "cw_render_records: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
+    if (misaligned16(hdr)) return fail(CW_ERR_INVALID, "cw_render_records: hdr is not 16-byte aligned");
+    if (misaligned16(slot_pos)) return fail(CW_ERR_INVALID, "cw_render_records: slot_pos is not 16-byte aligned");
+    if (e->P.raster != CW_RASTER_ALT && ((uintptr_t)out_frames & 3u) != 0)      // (the Ray painter's 12-byte stores; AltObs frames start at every alignment anyway)
+        return fail(CW_ERR_INVALID, "cw_render_records: out_frames is not 4-byte aligned");
+    const uint64_t o = (uint64_t)(uintptr_t)out_frames, o_bytes = (uint64_t)n_states * e->P.frame_bytes, rec_bytes = 16ull * (uint64_t)n_states;
+    if (cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)hdr, rec_bytes) || cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)slot_pos, rec_bytes))
+        return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the records read");
+    if (mask && cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)mask, (uint64_t)n_states))
+        return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the mask");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_render_records called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    DeviceGuard guard(e->device);
+    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
+    PARK(e);
+    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    HIP_TRY(cwk_launch_render_records(&e->P, &e->tune, (const uint4 *)hdr, (const uint4 *)slot_pos, mask, n_states, out_frames, (hipStream_t)stream));
     if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
     return CW_OK;
 }

@@ -175,6 +175,7 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
 }
 int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity) { return cwh_snapshot_row_ok(row, capacity); }
 int cwh_expand_env_in_batch(int32_t env, int32_t num_envs) { return cwh_expand_env_ok(env, num_envs); }
+uint32_t cwh_alt_pixel_offset_of(uint32_t size, uint32_t pos, uint32_t item) { return cwh_alt_pixel_offset(size, pos, item); }
 
 // ------------------------------------------------------------------------------ cw_simulate's argument rules
 int cwh_simulate_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields)

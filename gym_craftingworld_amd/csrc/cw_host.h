@@ -51,6 +51,18 @@ int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity);       // (the same,
 // THE env check of cw_expand_kernel, shared by host and device: an entry of the caller's env_of array may index the engine's per-env arrays only if this says so
 static inline CWH_HOST_DEVICE int cwh_expand_env_ok(int32_t env, int32_t num_envs) { return env >= 0 && env < num_envs; }
 int cwh_expand_env_in_batch(int32_t env, int32_t num_envs);        // (the same, exported for the CPU tests)
+// THE pixel offset of cw_render_records_kernel's AltObs painter, shared by host and device: where in a frame of 27 * S * (S + 1) bytes the three bytes of
+// item 1..9 (object code 1..8, 9 = the agent) in cell `pos` of an S x S grid go -- pixel item - 1 of the cell's 3x3 tile (craftingworld_altobs.py:527-543) --
+// or CWH_ALT_NO_PIXEL for every other item and every position at or above S * S (the two markers of a slot, gone and held, included).  A record's bytes
+// become a store address only through this: an offset it returns satisfies offset + 3 <= 27 * S * S, inside the grid part of the frame.
+#define CWH_ALT_NO_PIXEL 0xFFFFFFFFu
+static inline CWH_HOST_DEVICE uint32_t cwh_alt_pixel_offset(uint32_t size, uint32_t pos, uint32_t item)
+{
+    if (size - 1u >= 255u || item - 1u >= 9u || pos >= size * size) return CWH_ALT_NO_PIXEL;
+    const uint32_t r = pos / size, c = pos - r * size, k = item - 1u, k3 = k / 3u;
+    return (3u * r + k3) * (9u * size) + 9u * c + 3u * (k - 3u * k3);
+}
+uint32_t cwh_alt_pixel_offset_of(uint32_t size, uint32_t pos, uint32_t item);     // (the same, exported for the CPU tests)
 
 // ---- cw_simulate's argument rules that need no HIP (cw_engine.cpp: cw_simulate turns the code into its error text), in the order they are tested:
 // some output field, 0 <= n_states <= 2^27, 1 <= n_steps <= 32 767, hdr_in and slot_pos_in together, env_of only with them, and without them (the

@@ -15,6 +15,7 @@
 //                     same way by a device array of row numbers.
 //   cw_expand_kernel  the successors of all six actions of M states (the engine's own or packed records of the caller's), one lane per (action, state) pair with
 //                     the action uniform across a wave; writes nothing of the engine.  cw_export_onehot_states_kernel: the one-hot view of such records.
+//   cw_render_records_kernel  the frames of such records in the engine's raster, one wave per state (paint_state_frame); writes nothing of the engine.
 //   cw_simulate_kernel  T steps of M such states along M action sequences of the caller's, one lane per state, the state in registers throughout, the
 //                     action bytes fetched a block of steps ahead; writes nothing of the engine.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
@@ -196,6 +197,9 @@ __device__ __forceinline__ void alt_paint_strip(uint8_t *frame, int S, uint32_t 
 // 2 x colour in the reference's int image (sticks held over sticks, altobs.py:527-543), here modulo 256: the only pixels
 // that can coincide are the held item's and an object's, and they are merged before they are stored.
 // (The tile-by-tile form, 27 byte stores per cell, reached 4.3 TB/s on L2 write combining.)
+// kRecords: the values are a CALLER's record (cw_render_records_kernel), where an item code or a position can be anything: the offset of a lit pixel then
+// comes from cwh_alt_pixel_offset (cw_host.h), which gives none for an item outside 1..9 or a position outside the grid.
+template <bool kRecords = false>
 __device__ __forceinline__ void render_frame_alt(uint8_t *__restrict__ dst0, uint8_t *__restrict__ dst1, int S, int ncell,
                                                  uint32_t div_magic, const uint32_t sp[8], uint32_t codes,
                                                  uint32_t agent_cell, uint32_t hold, int lane, int pace)
@@ -211,7 +215,10 @@ __device__ __forceinline__ void render_frame_alt(uint8_t *__restrict__ dst0, uin
     if (lane == 8) { pos = agent_cell; item = 9u; }          // the agent: pixel 8 (altobs.py:536)
     if (lane == 9) { pos = agent_cell; item = hold; }        // the held item, on its own object pixel at the agent's cell
     uint32_t p_off = 0xFFFFFFFFu, p_val = 0;
-    if (lane < 10 && item != 0 && pos < (uint32_t)ncell) {
+    if (kRecords && lane < 10) {
+        p_off = cwh_alt_pixel_offset((uint32_t)S, pos, item);
+        if (p_off != CWH_ALT_NO_PIXEL) p_val = cpv_color((int)item - 1);
+    } else if (lane < 10 && item != 0 && pos < (uint32_t)ncell) {
         const uint32_t r = __umulhi(pos, div_magic), c = pos - r * S, k = item - 1u;
         const uint32_t k3 = (k >= 6u) ? 2u : (k >= 3u) ? 1u : 0u;
         p_off = (3u * r + k3) * row_bytes + 9u * c + 3u * (k - 3u * k3);
@@ -287,12 +294,14 @@ __device__ __forceinline__ void render_frame(uint8_t *__restrict__ dst0, uint8_t
         }
     }
 }
-// one frame of either raster from wave-uniform values: slot positions / codes, agent cell, hold
+// one frame of either raster from wave-uniform values: slot positions / codes, agent cell, hold (kRecords: values of a caller's record, see render_frame_alt;
+// the Ray painter only compares cells and selects colours, whatever the values)
+template <bool kRecords = false>
 __device__ __forceinline__ void paint_state_frame(const CwParams &P, uint8_t *dst, const uint32_t sp[8], uint32_t codes, uint32_t agent_cell,
                                                   uint32_t hold, int lane, uint8_t *dst1 = nullptr)
 {
     if (P.raster == 1) {
-        render_frame_alt(dst, dst1, P.size, P.ncell, P.div_magic, sp, codes, agent_cell, hold, lane, CW_ALT_FRAME_PACE);
+        render_frame_alt<kRecords>(dst, dst1, P.size, P.ncell, P.div_magic, sp, codes, agent_cell, hold, lane, CW_ALT_FRAME_PACE);
     } else {
         uint32_t rgb[8];
 #pragma unroll
@@ -1809,6 +1818,28 @@ __global__ __launch_bounds__(256) void cw_render_frames_kernel(CwParams P, uint8
     }
 }
 
+// cw_render_records: the frames of n_states packed records of the CALLER's (hdr [n_states] / pos [n_states] in the engine's formats: cw_expand's and
+// cw_simulate's successors, a pruned frontier), uint8 in the engine's raster, byte for byte what cw_render shows of an env in that state.  One wave per
+// state, grid-stride: the record loaded once and made wave-uniform, then the painter of single frames.  A state with mask[j] == 0 costs that one byte load
+// and no store.  Of the engine only size and raster are read; of a record only the agent's cell, the hold, the slot codes and the slot positions, and none
+// of them becomes an address but through cwh_alt_pixel_offset (AltObs) -- the Ray painter compares cells.  Frame offsets are 64-bit.  No LDS.
+__global__ __launch_bounds__(256) void cw_render_records_kernel(CwParams P, const uint4 *__restrict__ hdr, const uint4 *__restrict__ pos,
+                                                                const uint8_t *__restrict__ mask, int n_states, uint8_t *out)
+{
+    const int lane = threadIdx.x & (CW_WAVE - 1);
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / CW_WAVE;
+    const int n_waves = gridDim.x * blockDim.x / CW_WAVE;
+    for (int j = wave; j < n_states; j += n_waves) {
+        if (mask && __builtin_amdgcn_readfirstlane((uint32_t)mask[j]) == 0u) continue;
+        const uint4 v_h = hdr[j], v_p = pos[j];
+        uint32_t sp[8];
+        unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(v_p.x), __builtin_amdgcn_readfirstlane(v_p.y), __builtin_amdgcn_readfirstlane(v_p.z),
+                              __builtin_amdgcn_readfirstlane(v_p.w)), sp);
+        const uint32_t hx = __builtin_amdgcn_readfirstlane(v_h.x), codes = __builtin_amdgcn_readfirstlane(v_h.w);
+        paint_state_frame<true>(P, out + (size_t)j * P.frame_bytes, sp, codes, agent_cell_of(P, hx), hold_of(hx), lane);
+    }
+}
+
 // ---- a frame array as a sweep of ALIGNED 4-KiB PIECES: the one painter of whole arrays ---------------------------------
 // Both rasters' frames are almost all zeros.  An AltObs frame is a zero fill plus <= 19 lit pixels (render_frame_alt); a Ray frame is
 // black (COLORS_N[0], ray.py:28) except the 4x4-pixel cells of its <= 8 objects and the agent's 2x2 mark (ray.py:476-486).  So the
@@ -2601,6 +2632,15 @@ hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T,
     int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(cw_export_onehot_states_kernel, dim3(blocks), dim3(256), 0, st, *P, hdr, pos, n_states, out);
+    return hipGetLastError();
+}
+
+// cw_render_records: one launch, one wave per state in flight, the grid of the other single-frame painter of whole arrays (cw_render_grid: at most one
+// workgroup of four waves per CU) -> waves = 4 * min(ceil(n_states / 4), n_cu)
+hipError_t cwk_launch_render_records(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, const uint8_t *mask, int n_states, uint8_t *out,
+                                     hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_render_records_kernel, dim3(cw_render_grid(*T, n_states)), dim3(256), 0, st, *P, hdr, pos, mask, n_states, out);
     return hipGetLastError();
 }
 

@@ -250,6 +250,36 @@ def simulate_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of):
     return _simulate_tm(num_envs, shape, dtype, None if hdr is None else m)
 
 
+def _render_records_m(frame_shape, lead, mask, out):
+    """render_records_args on the records' leading shape and the (shape, numpy dtype) of mask and out (None: not given)"""
+    lead, frame_shape = tuple(int(x) for x in lead), tuple(int(x) for x in frame_shape)
+    if mask is not None:
+        ms, md = mask
+        if np.dtype(md) not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+            raise ValueError('mask must be bool or uint8, got %s' % np.dtype(md))
+        if tuple(ms) != lead:
+            raise ValueError('mask must have the records\' leading shape %s, got %s' % (lead, tuple(ms)))
+    if out is not None:
+        os_, od = out
+        if np.dtype(od) != np.uint8 or tuple(os_) != lead + frame_shape:
+            raise ValueError('out must be a contiguous uint8 tensor %s, got %s %s' % (lead + frame_shape, np.dtype(od), tuple(os_)))
+
+
+def render_records_args(frame_shape, hdr, slot_pos, mask=None, out=None):
+    """What cw_render_records is handed, validated on the host (numpy inputs): -> (M, the records' leading shape).  hdr uint8 [..., 16] and slot_pos int16 /
+    uint16 [..., 8] under expand_args' rules, both required; mask: None or bool / uint8 with the records' leading shape; out: None or a C-contiguous uint8
+    array of the leading shape plus frame_shape.  ValueError for everything else."""
+    if hdr is None or slot_pos is None:
+        raise ValueError('render_records needs hdr and slot_pos')
+    m = expand_args(1, hdr, slot_pos, None)
+    lead = tuple(np.shape(hdr)[:-1])
+    if out is not None and not (isinstance(out, np.ndarray) and out.flags['C_CONTIGUOUS']):
+        raise ValueError('out must be a contiguous uint8 array %s' % (lead + tuple(frame_shape),))
+    _render_records_m(frame_shape, lead, None if mask is None else (np.shape(mask), np.asarray(mask).dtype),
+                      None if out is None else (out.shape, out.dtype))
+    return m, lead
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -808,7 +838,7 @@ class CraftingWorldVecEnv:
     def one_hot_states(self, hdr, slot_pos, out=None):
         """obs_one_hot (ray.py:119) of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() takes and returns them):
         -> uint8 [..., S, S, 12], the held item's channel 9-11 at the agent's cell (cw_export_onehot_states).  render_states() of the result is the
-        frame a pixel policy would see of that state.  Does not touch the envs."""
+        reference's int image of that state (int16); the uint8 frame a pixel policy would see is render_records().  Does not touch the envs."""
         if hdr is None or slot_pos is None:
             raise ValueError('one_hot_states needs hdr and slot_pos')
         m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
@@ -823,6 +853,40 @@ class CraftingWorldVecEnv:
         self._onehot_states_keepalive = (hdr, slot_pos, out)
         L.check(self._lib.cw_export_onehot_states(self._h, C.c_void_p(hdr.data_ptr()), C.c_void_p(slot_pos.data_ptr()), m, C.c_void_p(out.data_ptr()),
                                                   self._stream()), 'cw_export_onehot_states', self._lib)
+        if self.host_outputs:
+            self._sync()
+        return out
+
+    def render_records(self, hdr, slot_pos, *, mask=None, out=None):
+        """The frames a pixel policy would see of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() and simulate() return them,
+        env.hdr / env.slot_pos, a pruned frontier) -> uint8 [..., *frame_shape] on the env's device, in the env's raster, in every obs_mode: byte for byte
+        what render() or the observation array shows of an env in that state (cw_render_records: one kernel straight from the records, no one-hot scratch
+        tensor, no host round trip, capturable; no env is touched).  Contiguous tensors on the env's device go over in place; anything else is validated on
+        the host and copied (render_records_args: ValueError).  mask: bool or uint8 with the records' leading shape -- where it is 0 no byte of that
+        state's frame is written; expand()'s 'changed' goes in as it is (an unchanged successor's frame is its parent's).  out: a contiguous uint8 tensor of
+        the leading shape plus frame_shape on the env's device (Ray raster: 4-byte aligned), written in place; without it a fresh torch.empty is returned,
+        whose masked-out rows are UNINITIALISED memory."""
+        if hdr is None or slot_pos is None:
+            raise ValueError('render_records needs hdr and slot_pos')
+        m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
+        m_dev = mask is not None and self._in_place(mask, (torch.bool, torch.uint8))
+        if mask is not None and not m_dev:
+            mask = mask.cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+        if out is not None and (type(out) is not torch.Tensor or out.device != self.device or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous uint8 tensor %s on %s' % (lead + tuple(self.frame_shape), self.device))
+        np_of = lambda t: np.bool_ if t.dtype is torch.bool else self._NP_OF.get(t.dtype, np.float64)  # noqa: E731
+        _render_records_m(self.frame_shape, lead, None if mask is None else (tuple(mask.shape), np_of(mask) if m_dev else mask.dtype),
+                          None if out is None else (tuple(out.shape), np_of(out)))
+        if mask is not None and not m_dev:
+            mask = torch.as_tensor(np.ascontiguousarray(mask).view(np.uint8)).to(self.device)
+        if out is None:
+            out = torch.empty(lead + tuple(self.frame_shape), dtype=torch.uint8, device=self.device)
+        if m == 0:
+            return out
+        self._render_records_keepalive = (hdr, slot_pos, mask, out)
+        L.check(self._lib.cw_render_records(self._h, C.c_void_p(hdr.data_ptr()), C.c_void_p(slot_pos.data_ptr()),
+                                            None if mask is None else C.c_void_p(mask.data_ptr()), m, C.c_void_p(out.data_ptr()), self._stream()),
+                'cw_render_records', self._lib)
         if self.host_outputs:
             self._sync()
         return out

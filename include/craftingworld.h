@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate); 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -291,11 +291,35 @@ typedef struct cw_expand_out {   /* DEVICE pointers (cw_config.host_outputs engi
 int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in,
               int32_t n_states, const cw_expand_out *out, cw_stream_t stream);
 /* cw_export_onehot for caller-supplied packed records instead of the engine's arrays: hdr [n_states][16], slot_pos [n_states][8] (16-byte aligned, device)
- * -> out [n_states][S][S][12], hold channels 9-11 at the agent's cell.  With cw_render_onehot it turns any successor into the frame a pixel policy would
- * see.  One kernel (cw_export_onehot_states_kernel); the engine contributes only S.  n_states == 0: CW_OK, nothing enqueued; CW_ERR_INVALID for a null
+ * -> out [n_states][S][S][12], hold channels 9-11 at the agent's cell.  With cw_render_onehot it gives the reference's exact INT image of any successor
+ * (int16, render(state=...)); the frame a pixel policy would see -- uint8, the engine's own raster, the bytes of `obs` -- is cw_render_records, one kernel
+ * straight from the records.  One kernel (cw_export_onehot_states_kernel); the engine contributes only S.  n_states == 0: CW_OK, nothing enqueued; CW_ERR_INVALID for a null
  * argument, n_states < 0 or above 2^27, a misaligned hdr / slot_pos; CW_ERR_STATE before the first cw_reset / cw_checkpoint_load. */
 int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states,
                             uint8_t *out /* [n_states][S][S][12] */, cw_stream_t stream);
+
+/* --- what a pixel policy would SEE of packed records: frame j = the frame of record j (hdr [M][16], slot_pos [M][8], taken exactly as cw_expand and
+ * cw_export_onehot_states take them: device memory, 16-byte aligned, only read), at out_frames + (size_t)j * frame_bytes.  uint8, in the engine's raster, in
+ * every obs_mode (CW_OBS_STATE included, as cw_render does): byte for byte what cw_render or the obs array shows for an env in that state, the AltObs
+ * modulo-256 pixel (sticks held over sticks) included.  Q(s') for the six successors of cw_expand, the value of the leaf of a cw_simulate plan: no one-hot
+ * scratch tensor, no int16 image, no conversion.
+ * Of a record only the agent's cell (hdr bytes 0-1), the hold (byte 2), the eight slot codes (bytes 12-15) and the slot positions matter; 0xFFFF and 0xFFFE
+ *   (gone, held) are not drawn.  The engine contributes only its size and raster.  PURE: no env, stream, counter or buffer of the engine is read or written
+ *   (unlike cw_expand not even counters[7]).
+ * mask == NULL: every state.  Otherwise DEVICE uint8[M], only read: where mask[j] == 0 no byte of frame j is written, and the state costs one byte load.
+ *   cw_expand's out->changed goes in as it is: an unchanged successor's frame is its parent's, which the caller already has.
+ * Alignment as cw_render's: CW_RASTER_RAY needs a 4-byte aligned out_frames; CW_RASTER_ALT takes any (its frames start at every alignment anyway).  Offsets
+ *   are 64-bit throughout (6 x 65 536 successors at 21x21 are 8.3 GB).  out_frames must not overlap the records or the mask.
+ * An impossible record (an agent off the grid, a hold above 3, a slot code of 9..15, a slot position at or above S*S that is not one of the two markers) gives
+ *   unspecified pixel VALUES inside that state's own frame and never a load or store outside the frame_bytes of frame j: the Ray painter only compares cells
+ *   and selects colours, the AltObs painter turns (position, item) into a byte offset through one checked function (cw_host.h: cwh_alt_pixel_offset).
+ * Enqueues ONE kernel (cw_render_records_kernel: one wave per state, grid-stride) on `stream` -- no host synchronisation, no allocation -- and can be
+ *   captured into a HIP graph together with cw_expand / cw_simulate / cw_step.  host_outputs engines included.  n_states == 0: CW_OK, nothing enqueued.
+ *   CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID: a null engine, hdr, slot_pos or out_frames, n_states < 0 or above 2^27, a
+ *   misaligned hdr / slot_pos, a Ray out_frames that is not 4-byte aligned, out_frames overlapping the records or the mask.
+ *   (6 x 65 536 successors at 21x21, launch included: 1.69 ms for the 8.3 GB of Ray frames (4.9 TB/s), 1.16 ms for the 4.9 GB of AltObs frames; with mask = changed, 63 % of the rows: 1.13 / 0.78 ms; the one-hot route on the same records: 18.7 / 12.0 ms: tools/measure_render_records.py, profiles/r09_render_records.txt.) */
+int cw_render_records(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, const uint8_t *mask /* DEVICE uint8 [n_states] or NULL */,
+                      int32_t n_states, uint8_t *out_frames /* [n_states][frame_bytes] */, cw_stream_t stream);
 
 /* --- trying plans: T steps of M states along M action sequences of the caller's, with no env touched (random shooting, CEM, MPC, MCTS leaf rollouts, beam
  * search).  The multi-step companion of cw_expand: the same pure step function, each state kept in registers for the whole sequence, ONE kernel.
