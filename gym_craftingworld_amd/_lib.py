@@ -141,8 +141,8 @@ class cwh_tuning(C.Structure):
 cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variable's text or None (a pointer: ctypes cannot return a char* a callback made)
 
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
-CWH_SIM_OK, CWH_SIM_NO_FIELD, CWH_SIM_N_STATES, CWH_SIM_N_STEPS, CWH_SIM_PAIR, CWH_SIM_ENV_OF, CWH_SIM_MULTIPLE = range(7)
-CWH_SIM_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
+CWH_REC_OK, CWH_REC_NO_FIELD, CWH_REC_N_STATES, CWH_REC_N_STEPS, CWH_REC_PAIR, CWH_REC_ENV_OF, CWH_REC_OWN_STATES = range(7)
+CWH_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -163,7 +163,10 @@ HOST_HELPERS = {
     'cwh_snapshot_row_in_bank': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_expand_env_in_batch': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_alt_pixel_offset_of': (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
-    'cwh_simulate_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
+    'cwh_reset_grid_of': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'cwh_masked_launch_of': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    'cwh_envs_per_wave_of': (C.c_int, [C.c_int, C.c_int]),
+    'cwh_records_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),

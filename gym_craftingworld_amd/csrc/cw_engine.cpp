@@ -166,13 +166,6 @@ static hipError_t quiesce(cw_engine *e)
     if (all) return hipDeviceSynchronize();
     return e->aux ? hipStreamSynchronize(e->aux) : hipSuccess;
 }
-// The synchronous entry points copy with hipMemcpyAsync on e->aux into / out of vectors and stack buffers of their own: whatever way such a function
-// is left -- an early return on an error included -- nothing may still be in flight against storage that dies with its frame.
-struct AuxDrain {
-    cw_engine *e;
-    explicit AuxDrain(cw_engine *e_) : e(e_) {}
-    ~AuxDrain() { if (e && e->aux) (void)hipStreamSynchronize(e->aux); }
-};
 static inline hipError_t aux_copy(cw_engine *e, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 {
     return bytes ? hipMemcpyAsync(dst, src, bytes, kind, e->aux) : hipSuccess;
@@ -208,7 +201,49 @@ static int resident_park(cw_engine *e)
     __atomic_store_n(&e->res->exited, 0u, __ATOMIC_RELEASE);
     return CW_OK;
 }
-#define PARK(e) do { if ((e)->res_running) { const int _rc = resident_park(e); if (_rc != CW_OK) return _rc; } } while (0)
+
+// ------------------------------------------------------------------------------ what every entry point does on entry and on exit
+// Entry: the engine's device is current until the call returns, and the resident stepper is parked.  `rc` is the call's result if that failed.
+struct Entry {
+    DeviceGuard guard;
+    int rc;
+    explicit Entry(cw_engine *e) : guard(e->device), rc(guard.ok ? resident_park(e) : fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device)) {}
+};
+// An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
+// after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
+//   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_export_onehot_states, cw_render_records,
+//                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
+//   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
+enum Capture { ANY_STREAM, CAPTURE_AWARE };
+enum LastWork { NO_LAST_WORK, LAST_WORK };
+static inline void record_last_work(cw_engine *e, hipStream_t st)
+{
+    if (e->res && hipEventRecord(e->last_work, st) == hipSuccess) e->last_work_set = true;
+}
+struct EnqueueEntry : Entry {
+    cw_engine *const e;
+    const hipStream_t st;
+    const LastWork last;
+    EnqueueEntry(cw_engine *e_, cw_stream_t stream, Capture capture, LastWork last_) : Entry(e_), e(e_), st((hipStream_t)stream), last(last_)
+    {
+        if (rc != CW_OK) return;
+        if (capture == CAPTURE_AWARE && stream_capturing(st)) e->captured = true; else note_work(e, st);
+    }
+    int done() { if (last == LAST_WORK) record_last_work(e, st); return CW_OK; }
+};
+// A SYNCHRONOUS entry point: Entry, then quiesce() -- the engine's own work, not the card's.  It copies with hipMemcpyAsync on e->aux into / out of vectors
+// and stack buffers of its own (declared AHEAD of this object: they must outlive it): whatever way such a function is left -- an early return on an error
+// included -- nothing may still be in flight against storage that dies with its frame, so every exit waits for the private stream; `return in.done()`
+// is the exit that reports what that wait brought.
+struct SyncEntry : Entry {
+    cw_engine *const e;
+    bool drain = false;
+    explicit SyncEntry(cw_engine *e_) : Entry(e_), e(e_) { if (rc == CW_OK) rc = open(); }
+    ~SyncEntry() { if (drain && e->aux) (void)hipStreamSynchronize(e->aux); }
+    int open() { HIP_TRY(quiesce(e)); drain = true; return CW_OK; }
+    int done() { HIP_TRY(hipStreamSynchronize(e->aux)); return CW_OK; }
+};
 
 // (MT19937 state conversion, the DLPack producer, the dense view of a slot record, the checkpoint sections' sizes and the guard's decisions: cw_host.cpp)
 
@@ -609,10 +644,8 @@ int cw_create(const cw_config *cfg, int device, cw_engine **out)
 int cw_destroy(cw_engine *e)
 {
     if (!e) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    (void)resident_park(e);
+    Entry in(e);
+    if (in.rc != CW_OK) return in.rc;
     (void)quiesce(e);
     prof_free(e);
     if (e->aux) (void)hipStreamDestroy(e->aux);
@@ -641,48 +674,37 @@ static hipError_t lookahead_drop(cw_engine *e)
 int cw_seed_mt(cw_engine *e, const uint32_t *keys, const int32_t *pos)
 {
     if (!e || !keys || !pos) return fail(CW_ERR_INVALID, "cw_seed_mt: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const size_t N = (size_t)e->n;
     for (size_t i = 0; i < N; i++)
         if (pos[i] < 0 || pos[i] > CW_MT_N) return fail(CW_ERR_INVALID, "cw_seed_mt: pos[%zu]=%d outside 0..624", i, pos[i]);
-    HIP_TRY(quiesce(e));                              // (the engine's own work, not the card's)
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(aux_copy(e, e->P.mt, keys, N * CW_MT_N * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(aux_copy(e, e->P.mt_idx, pos, N * sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY(cwk_launch_seed(&e->P, nullptr, e->aux));
     HIP_TRY(lookahead_drop(e));
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_seed_int(cw_engine *e, const uint32_t *seeds)
 {
     if (!e || !seeds) return fail(CW_ERR_INVALID, "cw_seed_int: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(aux_copy(e, e->seed_scratch, seeds, (size_t)e->n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(cwk_launch_seed(&e->P, e->seed_scratch, e->aux));
     HIP_TRY(lookahead_drop(e));
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_get_mt(cw_engine *e, uint32_t *keys, int32_t *pos)
 {
     if (!e || !keys || !pos) return fail(CW_ERR_INVALID, "cw_get_mt: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const size_t N = (size_t)e->n;
     std::vector<uint32_t> words(N * CW_MT_N);
     std::vector<uint32_t> misc(e->P.lookahead ? N * 4 * CW_LA_DEPTH : 0);
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(aux_copy(e, words.data(), e->P.mt, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HIP_TRY(aux_copy(e, pos, e->P.mt_idx, N * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (e->P.lookahead) HIP_TRY(aux_copy(e, misc.data(), e->P.nx_misc, N * 16 * CW_LA_DEPTH, hipMemcpyDeviceToHost));
@@ -703,18 +725,29 @@ int cw_get_mt(cw_engine *e, uint32_t *keys, int32_t *pos)
     return CW_OK;
 }
 
+// imagine_obs() / sample_state() draw from the envs' streams at their LOGICAL position.  An engine that keeps look-ahead records has run its streams ahead of
+// that: rewind them and drop the records, as cw_generate_fixed_states does before its pool draws (synchronous; the next refill covers the whole batch).
+static int rewind_streams(cw_engine *e, hipStream_t st, const char *who)
+{
+    if (!e->P.lookahead) return CW_OK;
+    Entry in(e);      // (an entry of its own: cw_imagine_masked / cw_sample_state_masked come here AHEAD of theirs -- the quiesce() below forgets every noted stream)
+    if (in.rc != CW_OK) return in.rc;
+    if (stream_capturing(st)) return fail(CW_ERR_STATE, "%s: an engine that keeps look-ahead records rewinds its streams through the host and cannot be captured", who);
+    std::vector<uint32_t> keys((size_t)e->n * CW_MT_N);
+    std::vector<int32_t> pos((size_t)e->n);
+    int rc = cw_get_mt(e, keys.data(), pos.data());
+    if (rc == CW_OK) rc = cw_seed_mt(e, keys.data(), pos.data());
+    return rc;
+}
+
 int cw_generate_fixed_states(cw_engine *e, cw_stream_t stream)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_generate_fixed_states: null engine");
     if (e->K == 0) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (e->P.lookahead && e->has_reset) {            // records wait, computed from the stream the pool is about to draw from: rewind and drop them
-        std::vector<uint32_t> keys((size_t)e->n * CW_MT_N);
-        std::vector<int32_t> pos((size_t)e->n);
-        int rc = cw_get_mt(e, keys.data(), pos.data());
-        if (rc == CW_OK) rc = cw_seed_mt(e, keys.data(), pos.data());
+    Entry in(e);
+    if (in.rc != CW_OK) return in.rc;
+    if (e->has_reset) {                              // records wait, computed from the stream the pool is about to draw from: rewind and drop them
+        const int rc = rewind_streams(e, (hipStream_t)stream, "cw_generate_fixed_states");      // (never capturing: the call synchronises below)
         if (rc != CW_OK) return rc;
     }
     HIP_TRY(cwk_launch_pool(&e->P, &e->tune, (hipStream_t)stream));
@@ -726,10 +759,8 @@ int cw_generate_fixed_states(cw_engine *e, cw_stream_t stream)
 int cw_reset(cw_engine *e, cw_stream_t stream)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_reset: null engine");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_reset_all(&e->P, &e->tune, e->obs_mode, (hipStream_t)stream));
     if (e->P.lookahead) {                            // every env's NEXT episode, ahead of time (cw_refill_kernel)
         HIP_TRY(cwk_launch_refill(&e->P, &e->tune, 1, (hipStream_t)stream));
@@ -737,8 +768,7 @@ int cw_reset(cw_engine *e, cw_stream_t stream)
         e->la_steps = 0;
     }
     e->has_reset = true;
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 // reset() of the envs the caller selects: ONE kernel (cw_reset_masked_kernel) and nothing else.  No refill of its own -- an env that took a record is QUEUED,
@@ -747,26 +777,10 @@ int cw_reset_masked(cw_engine *e, const uint8_t *mask, cw_stream_t stream)
 {
     if (!e || !mask) return fail(CW_ERR_INVALID, "cw_reset_masked: null %s", !e ? "engine" : "mask");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_reset_masked called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_reset_masked(&e->P, &e->tune, mask, e->obs_mode, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
-}
-
-// imagine_obs() / sample_state() draw from the envs' streams at their LOGICAL position.  An engine that keeps look-ahead records has run its streams ahead of
-// that: rewind them and drop the records, as cw_generate_fixed_states does (synchronous; the next refill covers the whole batch).
-static int rewind_streams(cw_engine *e, hipStream_t st, const char *who)
-{
-    if (!e->P.lookahead) return CW_OK;
-    if (stream_capturing(st)) return fail(CW_ERR_STATE, "%s: an engine that keeps look-ahead records rewinds its streams through the host and cannot be captured", who);
-    std::vector<uint32_t> keys((size_t)e->n * CW_MT_N);
-    std::vector<int32_t> pos((size_t)e->n);
-    int rc = cw_get_mt(e, keys.data(), pos.data());
-    if (rc == CW_OK) rc = cw_seed_mt(e, keys.data(), pos.data());
-    return rc;
+    return in.done();
 }
 
 int cw_imagine_masked(cw_engine *e, const uint8_t *mask, const uint16_t *desired, int32_t commit, uint8_t *out_frames, uint8_t *out_onehot,
@@ -775,15 +789,12 @@ int cw_imagine_masked(cw_engine *e, const uint8_t *mask, const uint16_t *desired
     if (!e) return fail(CW_ERR_INVALID, "cw_imagine_masked: null engine");
     if (!commit && !out_frames && !out_onehot) return fail(CW_ERR_INVALID, "cw_imagine_masked: commit == 0 and no output pointer: nothing to do");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_imagine_masked called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const int rc = rewind_streams(e, (hipStream_t)stream, "cw_imagine_masked");
     if (rc != CW_OK) return rc;
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_imagine_masked(&e->P, &e->tune, mask, desired, commit != 0, e->obs_mode, out_frames, out_onehot, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, uint16_t *out_cells, cw_stream_t stream)
@@ -791,15 +802,12 @@ int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, ui
     if (!e || !out_cells) return fail(CW_ERR_INVALID, "cw_sample_state_masked: null %s", !e ? "engine" : "out_cells");
     if (pooled && e->K == 0) return fail(CW_ERR_INVALID, "cw_sample_state_masked: pooled with fixed_init_state == 0");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_sample_state_masked called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const int rc = rewind_streams(e, (hipStream_t)stream, "cw_sample_state_masked");
     if (rc != CW_OK) return rc;
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_sample_state_masked(&e->P, &e->tune, mask, pooled != 0, out_cells, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 // ------------------------------------------------------------------------------ snapshot bank
@@ -817,10 +825,8 @@ int cw_snapshot_reserve(cw_engine *e, int32_t rows)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: null engine");
     if (rows < 0) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: rows = %d must be >= 0", rows);
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    HIP_TRY(quiesce(e));                              // (the engine's own work: a save or load in flight uses the bank about to go)
+    SyncEntry in(e);                                 // (the engine's own work: a save or load in flight uses the bank about to go)
+    if (in.rc != CW_OK) return in.rc;
     bank_free(e);
     if (rows == 0) return CW_OK;
     size_t bytes[CWH_SNAP_SECTIONS], at[CWH_SNAP_SECTIONS];
@@ -864,13 +870,10 @@ int cw_snapshot_save(cw_engine *e, const int32_t *rows, cw_stream_t stream)
     if (!e || !rows) return fail(CW_ERR_INVALID, "cw_snapshot_save: null %s", !e ? "engine" : "rows");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_snapshot_save called before cw_reset");
     if (!e->bank) return fail(CW_ERR_STATE, "cw_snapshot_save: no bank reserved (cw_snapshot_reserve)");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_snapshot_save(&e->P, &e->tune, &e->B, rows, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_stream_t stream)
@@ -878,110 +881,113 @@ int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_
     if (!e || !rows) return fail(CW_ERR_INVALID, "cw_snapshot_load: null %s", !e ? "engine" : "rows");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_snapshot_load called before cw_reset");
     if (!e->bank) return fail(CW_ERR_STATE, "cw_snapshot_load: no bank reserved (cw_snapshot_reserve)");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_snapshot_load(&e->P, &e->tune, &e->B, rows, with_stream != 0, e->obs_mode, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 // ------------------------------------------------------------------------------ expand: the six successors of every state
-#define CW_EXPAND_MAX_STATES (1 << 27)
-static bool misaligned16(const void *p) { return ((uintptr_t)p & 15u) != 0; }
+// a record array is read and written 16 bytes at a time (null: not given)
+static int aligned16(const void *p, const char *what, const char *who)
+{
+    return ((uintptr_t)p & 15u) == 0 ? CW_OK : fail(CW_ERR_INVALID, "%s: %s is not 16-byte aligned", who, what);
+}
+// [out, out + out_bytes) shares a byte with the header or the slot records a kernel reads (rec_bytes each)
+static bool overlaps_records(const void *out, uint64_t out_bytes, const void *hdr, const void *pos, uint64_t rec_bytes)
+{
+    return cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)hdr, rec_bytes) ||
+           cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)pos, rec_bytes);
+}
+// What cw_expand (max_steps 0: no steps, its own states once) and cw_simulate (its own states broadcast) check alike: the HIP-free rules of cw_host.cpp
+// (cwh_records_args, tested on the CPU) as the caller's error text, then the alignment of the records in and out.
+static int records_args(const char *who, const cw_engine *e, const void *env_of, const void *hdr_in, const void *pos_in, int32_t n_states, int32_t n_steps,
+                        int32_t max_steps, int n_fields, const void *out_hdr, const void *out_pos)
+{
+    switch (cwh_records_args(e->n, env_of != nullptr, hdr_in != nullptr, pos_in != nullptr, n_states, n_steps, n_fields, max_steps, max_steps > 0)) {
+    case CWH_REC_OK: break;
+    case CWH_REC_NO_FIELD: return fail(CW_ERR_INVALID, "%s: every field of out is null", who);
+    case CWH_REC_N_STATES: return fail(CW_ERR_INVALID, "%s: n_states = %d must be 0 .. %d", who, n_states, CWH_MAX_STATES);
+    case CWH_REC_N_STEPS: return fail(CW_ERR_INVALID, "%s: n_steps = %d must be 1 .. %d", who, n_steps, max_steps);
+    case CWH_REC_PAIR: return fail(CW_ERR_INVALID, "%s: %s given without %s", who, hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
+    case CWH_REC_ENV_OF: return fail(CW_ERR_INVALID, "%s: env_of given without hdr_in", who);
+    default:
+        return fail(CW_ERR_INVALID, "%s: n_states = %d must be %snum_envs = %d without hdr_in", who, n_states, max_steps > 0 ? "a positive multiple of " : "", e->n);
+    }
+    int rc = aligned16(hdr_in, "hdr_in", who);
+    if (rc == CW_OK) rc = aligned16(pos_in, "slot_pos_in", who);
+    if (rc == CW_OK) rc = aligned16(out_hdr, "out->hdr", who);
+    if (rc == CW_OK) rc = aligned16(out_pos, "out->slot_pos", who);
+    return rc;
+}
+
+// ... and what cw_export_onehot_states and cw_render_records, which require their records, check alike: the cap and the two arrays' alignment
+static int states_args(const char *who, const void *hdr, const void *pos, int32_t n_states)
+{
+    if (n_states < 0 || n_states > CWH_MAX_STATES) return fail(CW_ERR_INVALID, "%s: n_states = %d must be 0 .. %d", who, n_states, CWH_MAX_STATES);
+    const int rc = aligned16(hdr, "hdr", who);
+    return rc == CW_OK ? aligned16(pos, "slot_pos", who) : rc;
+}
 
 // Only enqueues ONE kernel: no wait, no allocation, the same call whether it runs or is captured.  Writes nothing of the engine but counters[7].
 int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, const cw_expand_out *out,
               cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_expand: null %s", !e ? "engine" : "out");
-    if (!out->reward && !out->done && !out->changed && !out->achieved && !out->hdr && !out->slot_pos)
-        return fail(CW_ERR_INVALID, "cw_expand: every field of out is null");
-    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES) return fail(CW_ERR_INVALID, "cw_expand: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
-    if (!hdr_in != !slot_pos_in) return fail(CW_ERR_INVALID, "cw_expand: %s given without %s", hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
-    if (env_of && !hdr_in) return fail(CW_ERR_INVALID, "cw_expand: env_of given without hdr_in");
-    if (!hdr_in && n_states != e->n) return fail(CW_ERR_INVALID, "cw_expand: n_states = %d must be num_envs = %d without hdr_in", n_states, e->n);
-    if (misaligned16(hdr_in)) return fail(CW_ERR_INVALID, "cw_expand: hdr_in is not 16-byte aligned");
-    if (misaligned16(slot_pos_in)) return fail(CW_ERR_INVALID, "cw_expand: slot_pos_in is not 16-byte aligned");
-    if (misaligned16(out->hdr)) return fail(CW_ERR_INVALID, "cw_expand: out->hdr is not 16-byte aligned");
-    if (misaligned16(out->slot_pos)) return fail(CW_ERR_INVALID, "cw_expand: out->slot_pos is not 16-byte aligned");
+    const int n_fields = !!out->reward + !!out->done + !!out->changed + !!out->achieved + !!out->hdr + !!out->slot_pos;
+    const int bad = records_args("cw_expand", e, env_of, hdr_in, slot_pos_in, n_states, 0, 0, n_fields, out->hdr, out->slot_pos);
+    if (bad != CW_OK) return bad;
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_expand called before cw_reset");
     if (n_states == 0) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     CwExpandOut O;
     O.reward = out->reward; O.done = out->done; O.changed = out->changed; O.achieved = out->achieved;
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos;
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     HIP_TRY(cwk_launch_expand(&e->P, env_of, h, p, n_states, &O, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 // ------------------------------------------------------------------------------ simulate: T steps of M states along the caller's action sequences
-// cw_expand's shape: checks (the HIP-free ones are cw_host.cpp's cwh_simulate_args / cwh_ranges_overlap), then ONE kernel.  Writes nothing of the engine
-// but counters[7].
+// cw_expand's shape: checks (records_args; its outputs may not overlap the records it reads), then ONE kernel.  Writes nothing of the engine but counters[7].
 int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, const uint8_t *actions,
                 int32_t n_steps, int32_t stop_at_done, const cw_simulate_out *out, cw_stream_t stream)
 {
     if (!e || !out || !actions) return fail(CW_ERR_INVALID, "cw_simulate: null %s", !e ? "engine" : !out ? "out" : "actions");
     const int n_fields = !!out->ret + !!out->length + !!out->done + !!out->achieved + !!out->hdr + !!out->slot_pos + !!out->rewards + !!out->dones;
-    switch (cwh_simulate_args(e->n, env_of != nullptr, hdr_in != nullptr, slot_pos_in != nullptr, n_states, n_steps, n_fields)) {
-    case CWH_SIM_OK: break;
-    case CWH_SIM_NO_FIELD: return fail(CW_ERR_INVALID, "cw_simulate: every field of out is null");
-    case CWH_SIM_N_STATES: return fail(CW_ERR_INVALID, "cw_simulate: n_states = %d must be 0 .. %d", n_states, CWH_SIM_MAX_STATES);
-    case CWH_SIM_N_STEPS: return fail(CW_ERR_INVALID, "cw_simulate: n_steps = %d must be 1 .. %d", n_steps, CWH_SIM_MAX_STEPS);
-    case CWH_SIM_PAIR:
-        return fail(CW_ERR_INVALID, "cw_simulate: %s given without %s", hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
-    case CWH_SIM_ENV_OF: return fail(CW_ERR_INVALID, "cw_simulate: env_of given without hdr_in");
-    default: return fail(CW_ERR_INVALID, "cw_simulate: n_states = %d must be a positive multiple of num_envs = %d without hdr_in", n_states, e->n);
-    }
-    if (misaligned16(hdr_in)) return fail(CW_ERR_INVALID, "cw_simulate: hdr_in is not 16-byte aligned");
-    if (misaligned16(slot_pos_in)) return fail(CW_ERR_INVALID, "cw_simulate: slot_pos_in is not 16-byte aligned");
-    if (misaligned16(out->hdr)) return fail(CW_ERR_INVALID, "cw_simulate: out->hdr is not 16-byte aligned");
-    if (misaligned16(out->slot_pos)) return fail(CW_ERR_INVALID, "cw_simulate: out->slot_pos is not 16-byte aligned");
+    const int bad = records_args("cw_simulate", e, env_of, hdr_in, slot_pos_in, n_states, n_steps, CWH_SIM_MAX_STEPS, n_fields, out->hdr, out->slot_pos);
+    if (bad != CW_OK) return bad;
     // the records the kernel reads: the caller's n_states, or the engine's own num_envs
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     const uint64_t in_bytes = 16ull * (uint64_t)(hdr_in ? n_states : e->n), out_bytes = 16ull * (uint64_t)n_states;
     const void *const outs[2] = {out->hdr, out->slot_pos};
     for (int k = 0; k < 2; k++)
-        if (outs[k] && (cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k], out_bytes, (uint64_t)(uintptr_t)h, in_bytes) ||
-                        cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k], out_bytes, (uint64_t)(uintptr_t)p, in_bytes)))
+        if (outs[k] && overlaps_records(outs[k], out_bytes, h, p, in_bytes))
             return fail(CW_ERR_INVALID, "cw_simulate: out->%s overlaps the records read", k ? "slot_pos" : "hdr");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_simulate called before cw_reset");
     if (n_states == 0) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     CwSimulateOut O;
     O.ret = out->ret; O.length = out->length; O.done = out->done; O.achieved = out->achieved;
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.rewards = out->rewards; O.dones = out->dones;
     HIP_TRY(cwk_launch_simulate(&e->P, env_of, h, p, hdr_in ? 0 : 1, n_states, actions, n_steps, stop_at_done ? 1 : 0, &O, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 int cw_export_onehot_states(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, uint8_t *out, cw_stream_t stream)
 {
     if (!e || !hdr || !slot_pos || !out)
         return fail(CW_ERR_INVALID, "cw_export_onehot_states: null %s", !e ? "engine" : !hdr ? "hdr" : !slot_pos ? "slot_pos" : "out");
-    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES)
-        return fail(CW_ERR_INVALID, "cw_export_onehot_states: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
-    if (misaligned16(hdr)) return fail(CW_ERR_INVALID, "cw_export_onehot_states: hdr is not 16-byte aligned");
-    if (misaligned16(slot_pos)) return fail(CW_ERR_INVALID, "cw_export_onehot_states: slot_pos is not 16-byte aligned");
+    const int bad = states_args("cw_export_onehot_states", hdr, slot_pos, n_states);
+    if (bad != CW_OK) return bad;
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_export_onehot_states called before cw_reset");
     if (n_states == 0) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_export_onehot_states(&e->P, &e->tune, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 // ------------------------------------------------------------------------------ render_records: the frames of packed records, straight from the records
@@ -991,26 +997,21 @@ int cw_render_records(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos
 {
     if (!e || !hdr || !slot_pos || !out_frames)
         return fail(CW_ERR_INVALID, "cw_render_records: null %s", !e ? "engine" : !hdr ? "hdr" : !slot_pos ? "slot_pos" : "out_frames");
-    if (n_states < 0 || n_states > CW_EXPAND_MAX_STATES)
-        return fail(CW_ERR_INVALID, "cw_render_records: n_states = %d must be 0 .. %d", n_states, CW_EXPAND_MAX_STATES);
-    if (misaligned16(hdr)) return fail(CW_ERR_INVALID, "cw_render_records: hdr is not 16-byte aligned");
-    if (misaligned16(slot_pos)) return fail(CW_ERR_INVALID, "cw_render_records: slot_pos is not 16-byte aligned");
+    const int bad = states_args("cw_render_records", hdr, slot_pos, n_states);
+    if (bad != CW_OK) return bad;
     if (e->P.raster != CW_RASTER_ALT && ((uintptr_t)out_frames & 3u) != 0)      // (the Ray painter's 12-byte stores; AltObs frames start at every alignment anyway)
         return fail(CW_ERR_INVALID, "cw_render_records: out_frames is not 4-byte aligned");
-    const uint64_t o = (uint64_t)(uintptr_t)out_frames, o_bytes = (uint64_t)n_states * e->P.frame_bytes, rec_bytes = 16ull * (uint64_t)n_states;
-    if (cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)hdr, rec_bytes) || cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)slot_pos, rec_bytes))
+    const uint64_t o_bytes = (uint64_t)n_states * e->P.frame_bytes;
+    if (overlaps_records(out_frames, o_bytes, hdr, slot_pos, 16ull * (uint64_t)n_states))
         return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the records read");
-    if (mask && cwh_ranges_overlap(o, o_bytes, (uint64_t)(uintptr_t)mask, (uint64_t)n_states))
+    if (mask && cwh_ranges_overlap((uint64_t)(uintptr_t)out_frames, o_bytes, (uint64_t)(uintptr_t)mask, (uint64_t)n_states))
         return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the mask");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_render_records called before cw_reset");
     if (n_states == 0) return CW_OK;
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_render_records(&e->P, &e->tune, (const uint4 *)hdr, (const uint4 *)slot_pos, mask, n_states, out_frames, (hipStream_t)stream));
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
-    return CW_OK;
+    return in.done();
 }
 
 int cw_step(cw_engine *e, const void *actions, int action_dtype, cw_stream_t stream)
@@ -1018,9 +1019,8 @@ int cw_step(cw_engine *e, const void *actions, int action_dtype, cw_stream_t str
     if (!e || !actions) return fail(CW_ERR_INVALID, "cw_step: null argument");
     if (action_dtype < CW_ACT_I32 || action_dtype > CW_ACT_U8) return fail(CW_ERR_INVALID, "cw_step: bad action dtype %d", action_dtype);
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_step called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
+    Entry in(e);      // (not EnqueueEntry: cw_step_many asked once for all of its steps whether the stream captures, and the usual stream is found without note_work)
+    if (in.rc != CW_OK) return in.rc;
     const bool capturing = e->in_step_many ? e->capturing_now : stream_capturing((hipStream_t)stream);
     if (capturing) e->captured = true;
     else if (e->n_work != 1 || e->work[0] != (hipStream_t)stream) note_work(e, (hipStream_t)stream);
@@ -1037,7 +1037,7 @@ int cw_step(cw_engine *e, const void *actions, int action_dtype, cw_stream_t str
     }
     HIP_TRY(cwk_launch_step(&e->P, &e->tune, actions, action_dtype, e->obs_mode, e->auto_reset, (hipStream_t)stream, ev));
     if (profiled) e->prof_n++;
-    if (e->res && hipEventRecord(e->last_work, (hipStream_t)stream) == hipSuccess) e->last_work_set = true;
+    record_last_work(e, (hipStream_t)stream);
     return CW_OK;
 }
 
@@ -1122,9 +1122,7 @@ int cw_step_resident(cw_engine *e, int32_t action, int32_t want_onehot)
 int cw_resident_stop(cw_engine *e)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_resident_stop: null engine");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    return resident_park(e);
+    return Entry(e).rc;
 }
 
 int cw_rollout(cw_engine *e, const uint8_t *actions, int32_t n_steps, int32_t *rewards, uint8_t *dones, cw_stream_t stream)
@@ -1134,10 +1132,8 @@ int cw_rollout(cw_engine *e, const uint8_t *actions, int32_t n_steps, int32_t *r
     if (e->obs_mode != CW_OBS_STATE || !e->auto_reset)
         return fail(CW_ERR_INVALID, "cw_rollout needs obs_mode CW_OBS_STATE and auto_reset (frames are not painted by the persistent kernel)");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_rollout called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    if (stream_capturing((hipStream_t)stream)) e->captured = true; else note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     // Engines with look-ahead records: the n_steps go out in SEGMENTS of max_steps steps (64 at least), a refill kernel ahead of each -- a persistent launch
     // cannot refill, and an env that finishes a second time inside it finds no record and is reset the slow way by its whole wave (~12 us per env: the second
     // all-env time-out of a 600-step launch cost 64 envs x 12 us per wave, as much as the 600 steps themselves).  An episode lasts max_steps steps at most, so
@@ -1156,53 +1152,45 @@ int cw_rollout(cw_engine *e, const uint8_t *actions, int32_t n_steps, int32_t *r
         HIP_TRY(cwk_launch_rollout(&e->P, actions + (size_t)t0 * N, n, rewards ? rewards + (size_t)t0 * N : nullptr, dones ? dones + (size_t)t0 * N : nullptr,
                                    (hipStream_t)stream));
     }
-    return CW_OK;
+    return in.done();
 }
 
 int cw_render(cw_engine *e, uint8_t *out_frames, cw_stream_t stream)
 {
     if (!e || !out_frames) return fail(CW_ERR_INVALID, "cw_render: null argument");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_render called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_render_ext(&e->P, &e->tune, out_frames, (hipStream_t)stream));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_render_onehot(cw_engine *e, const uint8_t *onehot, int32_t n_states, uint16_t *out_frames, cw_stream_t stream)
 {
     if (!e || !onehot || !out_frames) return fail(CW_ERR_INVALID, "cw_render_onehot: null argument");
     if (n_states < 1) return fail(CW_ERR_INVALID, "cw_render_onehot: n_states must be >= 1");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_render_onehot(&e->P, onehot, n_states, out_frames, (hipStream_t)stream));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_export_grid(cw_engine *e, uint8_t *out, cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_export_grid: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_export(&e->P, &e->tune, out, 0, 0, (hipStream_t)stream));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_export_onehot(cw_engine *e, uint8_t *out, cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_export_onehot: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_export(&e->P, &e->tune, out, 1, 0, (hipStream_t)stream));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_export_onehot_of(cw_engine *e, int which, uint8_t *out, cw_stream_t stream)
@@ -1210,20 +1198,17 @@ int cw_export_onehot_of(cw_engine *e, int which, uint8_t *out, cw_stream_t strea
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_export_onehot_of: null argument");
     if (which < CW_STATE_CURRENT || which > CW_STATE_INIT) return fail(CW_ERR_INVALID, "cw_export_onehot_of: which must be CW_STATE_*");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_export_onehot_of called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    note_work(e, (hipStream_t)stream);
+    EnqueueEntry in(e, stream, ANY_STREAM, NO_LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_export(&e->P, &e->tune, out, 1, which, (hipStream_t)stream));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_profile_begin(cw_engine *e, int max_steps)
 {
     if (!e || max_steps < 1 || max_steps > 100000) return fail(CW_ERR_INVALID, "cw_profile_begin: bad argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
+    Entry in(e);
+    if (in.rc != CW_OK) return in.rc;
     prof_free(e);
     e->prof_ev.resize((size_t)max_steps * 6);
     for (auto &ev : e->prof_ev) HIP_TRY(hipEventCreate(&ev));
@@ -1234,9 +1219,8 @@ int cw_profile_begin(cw_engine *e, int max_steps)
 int cw_profile_end(cw_engine *e, cw_profile *out)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_profile_end: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
+    Entry in(e);
+    if (in.rc != CW_OK) return in.rc;
     memset(out, 0, sizeof(*out));
     const int n = e->prof_n;
     if (n > 0) {
@@ -1314,9 +1298,8 @@ int cw_buffers(cw_engine *e, cw_buffer_table *out)
 int cw_synchronize(cw_engine *e, cw_stream_t stream)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_synchronize: null engine");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
+    Entry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     for (int i = 0; i < e->n_work; i++)               // (that stream's share of the engine's work is done: the caller may destroy it now)
         if (e->work[i] == (hipStream_t)stream) { e->work[i] = e->work[--e->n_work]; break; }
@@ -1329,30 +1312,23 @@ int cw_get_fixed_states(cw_engine *e, uint16_t *out)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_get_fixed_states: null argument");
     if (e->K == 0) return fail(CW_ERR_INVALID, "cw_get_fixed_states: the engine was created with fixed_init_state = 0");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(aux_copy(e, out, e->P.pool, (size_t)e->n * e->K * 9 * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 // ------------------------------------------------------------------------------ state get/set
 int cw_get_state(cw_engine *e, cw_state_view *v)
 {
     if (!e || !v) return fail(CW_ERR_INVALID, "cw_get_state: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const size_t N = (size_t)e->n;
     const int S = e->S, nc = e->ncell;
     std::vector<uint32_t> hdr(N * 4), goal_codes(N);
     std::vector<uint16_t> pos(N * 8), ipos(N * 8), gpos(N * 8), iagent(N), gagent(N);
     std::vector<int32_t> epno(N);
-    HIP_TRY(quiesce(e));                              // (the engine's own work; copies on its private stream)
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     HIP_TRY(aux_copy(e, hdr.data(), e->P.hdr, N * 16, hipMemcpyDeviceToHost));
     HIP_TRY(aux_copy(e, pos.data(), e->P.pos, N * 16, hipMemcpyDeviceToHost));
     HIP_TRY(aux_copy(e, ipos.data(), e->P.init_pos, N * 16, hipMemcpyDeviceToHost));
@@ -1383,9 +1359,6 @@ int cw_set_state(cw_engine *e, const cw_state_view *v)
 {
     if (!e || !v) return fail(CW_ERR_INVALID, "cw_set_state: null argument");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_set_state called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const size_t N = (size_t)e->n;
     const int S = e->S, nc = e->ncell;
     std::vector<uint32_t> hdr(N * 4);
@@ -1393,8 +1366,8 @@ int cw_set_state(cw_engine *e, const cw_state_view *v)
     std::vector<uint32_t> gcodes;
     std::vector<int32_t> epno(N);
     const bool restore_episode = v->goal_grid || v->goal_agent_rc || v->init_agent_rc;
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     if (restore_episode) {                           // the episode records: goal state (imagine_obs' result) and the agent's start cell
         gpos.resize(N * 8); gagent.resize(N); iagent.resize(N); gcodes.resize(N);
         HIP_TRY(aux_copy(e, gpos.data(), e->P.goal_pos, N * 16, hipMemcpyDeviceToHost));
@@ -1498,8 +1471,7 @@ int cw_set_state(cw_engine *e, const cw_state_view *v)
         if (restore_episode) HIP_TRY(cwk_launch_render_restore(&e->P, &e->tune, e->aux));
         else HIP_TRY(cwk_launch_render_ext(&e->P, &e->tune, e->P.obs, e->aux));
     }
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 }  // extern "C"
@@ -1564,13 +1536,10 @@ int cw_checkpoint_save(cw_engine *e, void *buf, size_t capacity)
 {
     if (!e || !buf) return fail(CW_ERR_INVALID, "cw_checkpoint_save: null argument");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_checkpoint_save called before cw_reset");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     const CwCkptHeader h = ckpt_header(e);
     if (capacity < h.total_bytes) return fail(CW_ERR_INVALID, "cw_checkpoint_save: buffer of %zu bytes, %llu needed", capacity, (unsigned long long)h.total_bytes);
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     unsigned char *p = (unsigned char *)buf;
     memcpy(p, &h, sizeof(h));
     p += sizeof(h);
@@ -1578,16 +1547,12 @@ int cw_checkpoint_save(cw_engine *e, void *buf, size_t capacity)
         if (sec.bytes) HIP_TRY(aux_copy(e, p, sec.dev, sec.bytes, hipMemcpyDefault));
         p += sec.bytes;
     }
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 int cw_checkpoint_load(cw_engine *e, const void *buf, size_t length)
 {
     if (!e || !buf) return fail(CW_ERR_INVALID, "cw_checkpoint_load: null argument");
-    DeviceGuard guard(e->device);
-    if (!guard.ok) return fail(CW_ERR_HIP, "hipSetDevice(%d) failed", e->device);
-    PARK(e);
     CwCkptHeader h;
     if (length < sizeof(h)) return fail(CW_ERR_INVALID, "cw_checkpoint_load: %zu bytes is not a checkpoint", length);
     memcpy(&h, buf, sizeof(h));
@@ -1607,13 +1572,13 @@ int cw_checkpoint_load(cw_engine *e, const void *buf, size_t length)
     // other way round: the records are not state, only work done ahead -- where one waits, the env's stream is rewound by the draws it took
     // (cwh_mt_rewind) and the record dropped; an engine that keeps records recomputes them at its next refill.
     const size_t N = (size_t)e->n;
-    std::vector<uint32_t> key(CW_MT_N), words(CW_MT_N);      // (scratch of the rewind below; declared ahead of the drain guard: it outlives every copy)
+    std::vector<uint32_t> key(CW_MT_N), words(CW_MT_N);      // (scratch of the rewind below; declared ahead of the entry: it outlives every copy)
     const size_t la_bytes = N * 16 * 3 * CW_LA_DEPTH + N * 4;
     const unsigned long long expect = mine.total_bytes + (h.lookahead && !mine.lookahead ? la_bytes : 0) - (!h.lookahead && mine.lookahead ? la_bytes : 0);
     if (h.total_bytes != expect || length < h.total_bytes)
         return fail(CW_ERR_INVALID, "cw_checkpoint_load: truncated checkpoint (%zu of %llu bytes)", length, (unsigned long long)h.total_bytes);
-    HIP_TRY(quiesce(e));
-    AuxDrain drain(e);                               // (every exit waits for the private stream: the copies below target this frame's buffers)
+    SyncEntry in(e);
+    if (in.rc != CW_OK) return in.rc;
     const unsigned char *p = (const unsigned char *)buf + sizeof(h);
     const unsigned char *blob_mt = nullptr, *blob_idx = nullptr;
     for (const CkptSection &sec : ckpt_sections(e)) {
@@ -1651,8 +1616,7 @@ int cw_checkpoint_load(cw_engine *e, const void *buf, size_t length)
     e->has_reset = true;
     e->la_refill_all = e->P.lookahead != 0;          // (harmless: envs that hold a record are skipped)
     if (e->obs_mode != CW_OBS_STATE) HIP_TRY(cwk_launch_render_restore(&e->P, &e->tune, e->aux));   // frames follow the records
-    HIP_TRY(hipStreamSynchronize(e->aux));
-    return CW_OK;
+    return in.done();
 }
 
 }  // extern "C"

@@ -176,17 +176,21 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
 int cwh_snapshot_row_in_bank(int32_t row, int32_t capacity) { return cwh_snapshot_row_ok(row, capacity); }
 int cwh_expand_env_in_batch(int32_t env, int32_t num_envs) { return cwh_expand_env_ok(env, num_envs); }
 uint32_t cwh_alt_pixel_offset_of(uint32_t size, uint32_t pos, uint32_t item) { return cwh_alt_pixel_offset(size, pos, item); }
+int cwh_reset_grid_of(int jobs, int n_cu, int reset_blocks_per_cu) { return cwh_reset_grid(jobs, n_cu, reset_blocks_per_cu); }
+int cwh_masked_launch_of(int n_envs, int n_cu, int reset_blocks_per_cu, int *blocks) { return cwh_masked_launch(n_envs, n_cu, reset_blocks_per_cu, blocks); }
+int cwh_envs_per_wave_of(int n, int most) { return cwh_envs_per_wave(n, most); }
 
-// ------------------------------------------------------------------------------ cw_simulate's argument rules
-int cwh_simulate_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields)
+// ------------------------------------------------------------------------------ the argument rules of a call that reads packed records
+int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields,
+                     int32_t max_steps, int broadcast)
 {
-    if (n_out_fields <= 0) return CWH_SIM_NO_FIELD;
-    if (n_states < 0 || n_states > CWH_SIM_MAX_STATES) return CWH_SIM_N_STATES;
-    if (n_steps < 1 || n_steps > CWH_SIM_MAX_STEPS) return CWH_SIM_N_STEPS;
-    if (!has_hdr_in != !has_slot_pos_in) return CWH_SIM_PAIR;
-    if (has_env_of && !has_hdr_in) return CWH_SIM_ENV_OF;
-    if (!has_hdr_in && (num_envs <= 0 || n_states <= 0 || n_states % num_envs != 0)) return CWH_SIM_MULTIPLE;
-    return CWH_SIM_OK;
+    if (n_out_fields <= 0) return CWH_REC_NO_FIELD;
+    if (n_states < 0 || n_states > CWH_MAX_STATES) return CWH_REC_N_STATES;
+    if (max_steps > 0 && (n_steps < 1 || n_steps > max_steps)) return CWH_REC_N_STEPS;
+    if (!has_hdr_in != !has_slot_pos_in) return CWH_REC_PAIR;
+    if (has_env_of && !has_hdr_in) return CWH_REC_ENV_OF;
+    if (!has_hdr_in && (broadcast ? num_envs <= 0 || n_states <= 0 || n_states % num_envs != 0 : n_states != num_envs)) return CWH_REC_OWN_STATES;
+    return CWH_REC_OK;
 }
 
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)

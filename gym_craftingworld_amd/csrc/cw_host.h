@@ -64,13 +64,50 @@ static inline CWH_HOST_DEVICE uint32_t cwh_alt_pixel_offset(uint32_t size, uint3
 }
 uint32_t cwh_alt_pixel_offset_of(uint32_t size, uint32_t pos, uint32_t item);     // (the same, exported for the CPU tests)
 
-// ---- cw_simulate's argument rules that need no HIP (cw_engine.cpp: cw_simulate turns the code into its error text), in the order they are tested:
-// some output field, 0 <= n_states <= 2^27, 1 <= n_steps <= 32 767, hdr_in and slot_pos_in together, env_of only with them, and without them (the
-// engine's own states, broadcast) n_states a positive multiple of num_envs.  has_*: the pointer is not null; n_out_fields: how many fields of out are not.
-#define CWH_SIM_MAX_STATES (1 << 27)
+// ---- launch shapes shared by the launchers (cw_kernels.hip) and the CPU tests: the code the launchers run, no copy of it
+#define CW_WAVE 64          // lanes of a wavefront
+#define CW_RESET_WAVES 4    // waves (= envs in flight) per workgroup of the kernels that reset
+// workgroups of CW_RESET_WAVES waves for `jobs` waves' worth of work -- persistent: one wave per env in flight, n_cu * reset_blocks_per_cu workgroups at most
+static inline int cwh_reset_grid(int jobs, int n_cu, int reset_blocks_per_cu)
+{
+    int blocks = (jobs + CW_RESET_WAVES - 1) / CW_RESET_WAVES;
+    if (blocks > n_cu * reset_blocks_per_cu) blocks = n_cu * reset_blocks_per_cu;
+    return blocks < 1 ? 1 : blocks;
+}
+int cwh_reset_grid_of(int jobs, int n_cu, int reset_blocks_per_cu);        // (the same, exported for the CPU tests)
+// THE shape of the masked kernels (reset, imagine, sample) and the snapshot kernels: a workgroup scans `epb` mask bytes (row numbers) per round and deals the
+// selected envs out to its four waves: 64, halved down to 4 (one env per wave, cw_reset_kernel's shape) while the ceil(N / epb) chunks would not fill
+// most = n_cu * reset_blocks_per_cu workgroups; min(chunks, most) workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...  With
+// CW_TUNE_RESET_BLOCKS=4 on 256 CUs: 4 below 8 185 envs, 64 from 65 473 (tests/test_masked_shapes.py runs every width with the value 1).  -> epb; *blocks
+static inline int cwh_masked_launch(int n_envs, int n_cu, int reset_blocks_per_cu, int *blocks)
+{
+    const int most = n_cu * reset_blocks_per_cu;
+    int epb = CW_WAVE;
+    while (epb > CW_RESET_WAVES && (n_envs + epb - 1) / epb < most) epb >>= 1;
+    *blocks = cwh_reset_grid(((n_envs + epb - 1) / epb) * CW_RESET_WAVES, n_cu, reset_blocks_per_cu);
+    return epb;
+}
+int cwh_masked_launch_of(int n_envs, int n_cu, int reset_blocks_per_cu, int *blocks);      // (the same, exported for the CPU tests)
+// envs per wavefront of the kernels that reset inline (an inline reset occupies the whole wave, one finished env at a time -- rare now that
+// finished envs take their look-ahead records): aim for ~1024 waves (one per SIMD) -- `most` (64) envs per wave for large batches, down to 8 for small ones
+static inline int cwh_envs_per_wave(int n, int most)
+{
+    int epw = most;
+    while (epw > 8 && (n + epw - 1) / epw < 1024) epw >>= 1;
+    return epw;
+}
+int cwh_envs_per_wave_of(int n, int most);         // (the same, exported for the CPU tests)
+
+// ---- the argument rules of an entry point that reads PACKED RECORDS and needs no HIP to check them (cw_engine.cpp: cw_expand and cw_simulate turn the code
+// into their error texts), in the order they are tested: some output field, 0 <= n_states <= CWH_MAX_STATES (cw_export_onehot_states and cw_render_records,
+// which require their records, share only this cap), 1 <= n_steps <= max_steps (max_steps 0: a call without steps, cw_expand), hdr_in and slot_pos_in
+// together, env_of only with them, and without them (the engine's own states) n_states = num_envs -- or, broadcast (cw_simulate), a positive multiple of it.
+// has_*: the pointer is not null; n_out_fields: how many fields of out are not.
+#define CWH_MAX_STATES (1 << 27)
 #define CWH_SIM_MAX_STEPS 32767     // with max_steps <= 65 535 the int32 sum of n_steps rewards cannot overflow
-enum { CWH_SIM_OK = 0, CWH_SIM_NO_FIELD = 1, CWH_SIM_N_STATES = 2, CWH_SIM_N_STEPS = 3, CWH_SIM_PAIR = 4, CWH_SIM_ENV_OF = 5, CWH_SIM_MULTIPLE = 6 };
-int cwh_simulate_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields);
+enum { CWH_REC_OK = 0, CWH_REC_NO_FIELD = 1, CWH_REC_N_STATES = 2, CWH_REC_N_STEPS = 3, CWH_REC_PAIR = 4, CWH_REC_ENV_OF = 5, CWH_REC_OWN_STATES = 6 };
+int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields,
+                     int32_t max_steps, int broadcast);
 // the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
 

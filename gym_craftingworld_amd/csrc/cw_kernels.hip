@@ -34,7 +34,6 @@
 #include "cw_layout.h"
 #include "cw_mt.h"
 
-#define CW_WAVE 64
 #define CW_BALLOT(p) __builtin_amdgcn_ballot_w64(p)   // the compare's own SGPR pair (__ballot goes through a select + compare)
 #define CW_ALT_FRAME_PACE 2    // render_frame_alt: s_sleep(1) after each 1-KiB store of a single frame's zero fill (back to back 3.0 TB/s, with 64-192 idle clocks 5.2-5.4)
 
@@ -877,7 +876,6 @@ __device__ __forceinline__ int nth_with_code(uint32_t v_fp, uint32_t v_fc, uint3
 }
 #define CW_SET_LANE(v, idx, val) v = ((int)lane == (idx)) ? (val) : v
 
-#define CW_RESET_WAVES 4    // waves (= envs in flight) per workgroup
 // One env's reset() (ray.py:156-218) by one wavefront; every value in the result is wave-uniform.
 struct CwResetOut {
     uint4 init_pos;          // sample_state placement of objects 0..7
@@ -2471,22 +2469,15 @@ static void cw_launch_sweep(const CwParams &P, const CwTuning &tn, uint8_t *fram
 
 // workgroups of CW_RESET_WAVES waves that hold `waves` waves
 static inline int cw_wave_blocks(int waves) { return (waves + CW_RESET_WAVES - 1) / CW_RESET_WAVES; }
-static inline int cw_reset_grid(const CwTuning &tn, int jobs)
+// the shapes the CPU tests can call are cw_host.h's: the reset-shaped grid, the masked / snapshot kernels' (epb, workgroups), the envs per wave
+static inline int cw_reset_grid(const CwTuning &tn, int jobs) { return cwh_reset_grid(jobs, tn.n_cu, tn.reset_blocks_per_cu); }
+static inline int cw_masked_launch(const CwParams *P, const CwTuning *T, int *blocks) { return cwh_masked_launch(P->n_envs, T->n_cu, T->reset_blocks_per_cu, blocks); }
+// workgroups of 256 threads of the export kernels, one thread per cell of `total`, grid-stride above 32 workgroups per CU
+static inline int cw_export_grid(const CwTuning &tn, size_t total)
 {
-    // persistent: one wave per env in flight, reset_blocks_per_cu workgroups (x 4 waves) per CU at most
-    int blocks = cw_wave_blocks(jobs);
-    if (blocks > tn.n_cu * tn.reset_blocks_per_cu) blocks = tn.n_cu * tn.reset_blocks_per_cu;
-    if (blocks < 1) blocks = 1;
-    return blocks;
-}
-
-// envs per wavefront of the kernels that reset inline (an inline reset occupies the whole wave, one finished env at a time -- rare now that
-// finished envs take their look-ahead records): aim for ~1024 waves (one per SIMD) -- 64 envs per wave for large batches, down to 8 for small ones
-static int cw_envs_per_wave(int n, int most = 64)
-{
-    int epw = most;
-    while (epw > 8 && (n + epw - 1) / epw < 1024) epw >>= 1;
-    return epw;
+    const size_t cap = (size_t)tn.n_cu * 32;
+    const int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
+    return blocks < 1 ? 1 : blocks;
 }
 
 extern "C" {
@@ -2501,7 +2492,7 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
     const bool ev_all = ev && obs_mode != 1;                   // (full-frame mode: only the dominant kernel is bracketed -- every event record costs a pipeline bubble)
     if (ev_all) (void)hipEventRecord(ev[0], st);
     if (auto_reset) {
-        const int epw = cw_envs_per_wave(n, tn.step_envs_per_wave);
+        const int epw = cwh_envs_per_wave(n, tn.step_envs_per_wave);
         const int waves = (n + epw - 1) / epw;
         const int paint = obs_mode == 2 ? 1 : obs_mode == 1 ? 2 : 0;
         hipLaunchKernelGGL(cw_step_fused_variant(paint, paint != 0 && P->terminal_img != nullptr), dim3(cw_wave_blocks(waves)), dim3(CW_RESET_WAVES * CW_WAVE),
@@ -2534,7 +2525,7 @@ hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const u
 
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st)
 {
-    const int epw = cw_envs_per_wave(P->n_envs);
+    const int epw = cwh_envs_per_wave(P->n_envs, CW_WAVE);
     const int waves = (P->n_envs + epw - 1) / epw;
     hipLaunchKernelGGL(cw_rollout_kernel, dim3(cw_wave_blocks(waves)), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, actions, T, rewards, dones, epw);
     return hipGetLastError();
@@ -2557,34 +2548,22 @@ hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mo
     return hipGetLastError();
 }
 
-// reset() of the envs with mask[i] != 0 (cw_reset_masked_kernel): one launch, nothing else.  A workgroup scans `epb` mask bytes per round and deals the
-// selected envs out to its four waves: 64, halved down to 4 (one env per wave, cw_reset_kernel's shape) while the ceil(N / epb) chunks would not fill
-// most = n_cu * reset_blocks_per_cu workgroups; min(chunks, most) workgroups, each taking chunks blockIdx.x, blockIdx.x + gridDim.x, ...  With
-// CW_TUNE_RESET_BLOCKS=4 on 256 CUs: 4 below 8 185 envs, 64 from 65 473 (tests/test_masked_shapes.py runs every width with the value 1)
+// reset() of the envs with mask[i] != 0 (cw_reset_masked_kernel): one launch, nothing else, in the masked shape (cw_host.h: cwh_masked_launch)
 hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st)
 {
-    const int most = T->n_cu * T->reset_blocks_per_cu;
-    int epb = CW_WAVE;
-    while (epb > CW_RESET_WAVES && (P->n_envs + epb - 1) / epb < most) epb >>= 1;
-    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    int blocks;
+    const int epb = cw_masked_launch(P, T, &blocks);
     if (obs_mode != 0) hipLaunchKernelGGL(cw_reset_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
     else hipLaunchKernelGGL(cw_reset_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
     return hipGetLastError();
 }
 
 // imagine_obs() / sample_state() of the envs with mask[i] != 0 (NULL: all): one launch each, in cwk_launch_reset_masked's shape
-static int cw_masked_epb(const CwParams *P, const CwTuning *T)
-{
-    const int most = T->n_cu * T->reset_blocks_per_cu;
-    int epb = CW_WAVE;
-    while (epb > CW_RESET_WAVES && (P->n_envs + epb - 1) / epb < most) epb >>= 1;
-    return epb;
-}
 hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, const uint16_t *desired, int commit, int obs_mode,
                                      uint8_t *out_frames, uint8_t *out_onehot, hipStream_t st)
 {
-    const int epb = cw_masked_epb(P, T);
-    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    int blocks;
+    const int epb = cw_masked_launch(P, T, &blocks);
     const int paint_goal = obs_mode != 0;
     if (out_frames || (commit && paint_goal))
         hipLaunchKernelGGL(cw_imagine_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, desired, commit, paint_goal,
@@ -2596,24 +2575,24 @@ hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const
 }
 hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st)
 {
-    const int epb = cw_masked_epb(P, T);
-    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    int blocks;
+    const int epb = cw_masked_launch(P, T, &blocks);
     hipLaunchKernelGGL(cw_sample_state_masked_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, pooled, out_cells, epb);
     return hipGetLastError();
 }
 
-// snapshot save / load of the envs with rows[i] >= 0: one launch each, in the masked kernels' shape (cw_masked_epb, cw_reset_grid)
+// snapshot save / load of the envs with rows[i] >= 0: one launch each, in the masked kernels' shape
 hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st)
 {
-    const int epb = cw_masked_epb(P, T);
-    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    int blocks;
+    const int epb = cw_masked_launch(P, T, &blocks);
     hipLaunchKernelGGL(cw_snapshot_save_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, epb);
     return hipGetLastError();
 }
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st)
 {
-    const int epb = cw_masked_epb(P, T);
-    const int blocks = cw_reset_grid(*T, ((P->n_envs + epb - 1) / epb) * CW_RESET_WAVES);
+    int blocks;
+    const int epb = cw_masked_launch(P, T, &blocks);
     if (obs_mode != 0) hipLaunchKernelGGL(cw_snapshot_load_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
     else hipLaunchKernelGGL(cw_snapshot_load_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
     return hipGetLastError();
@@ -2627,11 +2606,7 @@ hipError_t cwk_launch_expand(const CwParams *P, const int32_t *env_of, const uin
 }
 hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, int n_states, uint8_t *out, hipStream_t st)
 {
-    const size_t total = (size_t)n_states * P->ncell;
-    const size_t cap = (size_t)T->n_cu * 32;
-    int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(cw_export_onehot_states_kernel, dim3(blocks), dim3(256), 0, st, *P, hdr, pos, n_states, out);
+    hipLaunchKernelGGL(cw_export_onehot_states_kernel, dim3(cw_export_grid(*T, (size_t)n_states * P->ncell)), dim3(256), 0, st, *P, hdr, pos, n_states, out);
     return hipGetLastError();
 }
 
@@ -2712,10 +2687,7 @@ hipError_t cwk_launch_render_ext(const CwParams *P, const CwTuning *T, uint8_t *
 
 hipError_t cwk_launch_export(const CwParams *P, const CwTuning *T, uint8_t *out, int onehot, int which, hipStream_t st)
 {
-    const size_t total = (size_t)P->n_envs * P->ncell;
-    const size_t cap = (size_t)T->n_cu * 32;
-    int blocks = (int)((total + 255) / 256 < cap ? (total + 255) / 256 : cap);
-    if (blocks < 1) blocks = 1;
+    const int blocks = cw_export_grid(*T, (size_t)P->n_envs * P->ncell);
     if (onehot) hipLaunchKernelGGL(cw_export_onehot_kernel, dim3(blocks), dim3(256), 0, st, *P, out, which);
     else hipLaunchKernelGGL(cw_export_grid_kernel, dim3(blocks), dim3(256), 0, st, *P, out);
     return hipGetLastError();

@@ -16,7 +16,7 @@ CW_WAVE, CW_RESET_WAVES = 64, 4
 
 # ------------------------------------------------------------------------------------------------------------------------------ the launch rule
 def masked_launch(n_envs, n_cu, reset_blocks=4):
-    """the shape cwk_launch_reset_masked / cw_masked_epb give the three masked kernels (CW_TUNE_RESET_BLOCKS) -> (epb, chunks, workgroups):
+    """the shape cwh_masked_launch (csrc/cw_host.h) gives the masked and snapshot kernels (CW_TUNE_RESET_BLOCKS) -> (epb, chunks, workgroups):
     a workgroup deals `epb` mask bytes a round -- 64, halved down to 4 while the chunks would not fill n_cu * reset_blocks workgroups"""
     most = n_cu * reset_blocks
     epb = CW_WAVE

@@ -2,10 +2,13 @@
 "before" side from the CPU oracle, the "after" side by this file's own use of the model: a faithful after-snapshot passes, and every way a masked
 kernel can be wrong that the GPU tests are there to catch -- one element of any compared quantity in a selected row, one element of an unselected
 row, a kernel that stops before the last partial chunk, two envs' results swapped within a chunk -- fails, naming the quantity and the env."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import imagine_model as M
+from hostlib import host_lib
 from masked_check import check_masked_call, masked_launch, untouched
 from oracle_replay import oracle_arrays
 
@@ -208,9 +211,37 @@ def test_desired_bits_above_the_task_list_and_odd_mask_bytes(case):
 
 
 def test_the_launch_rule():
-    """cw_masked_epb / cwk_launch_reset_masked as DESIGN.md 5.1 states it, at the figures tests/test_masked_shapes.py asserts on 256 CUs"""
+    """cwh_masked_launch (cw_host.h: what the masked and snapshot launchers call) as DESIGN.md 5.1 states it, at the figures tests/test_masked_shapes.py asserts
+    on 256 CUs -- and the C++ rule equal to masked_check.masked_launch, the copy the GPU tests compute their expectations with"""
     assert [masked_launch(n, 256, 1) for n in (509, 2053, 4099, 8209, 16411, 20011)] == \
         [(4, 128, 128), (8, 257, 256), (16, 257, 256), (32, 257, 256), (64, 257, 256), (64, 313, 256)]
     assert masked_launch(65536, 256)[:2] == (64, 1024) and masked_launch(16384, 256)[0] == 16 and masked_launch(700, 256)[0] == 4
     assert [masked_launch(n, 256)[0] for n in (1, 2, 3, 5, 63, 64, 65)] == [4] * 7
     assert masked_launch(1, 256) == (4, 1, 1) and masked_launch(37, 1, 1) == (64, 1, 1)
+    lib = host_lib()[1]
+    blocks = C.c_int(0)
+    sizes = sorted(set(range(1, 70001, 97)) | {p + d for k in range(18) for p in [2 ** k] for d in (-1, 0, 1) if p + d >= 1})
+    assert sizes[0] == 1 and 131073 in sizes and len(sizes) > 750
+    for n_cu in (1, 8, 256, 304):
+        for reset_blocks in (1, 4, 16):
+            for n in sizes:
+                epb = lib.cwh_masked_launch_of(n, n_cu, reset_blocks, C.byref(blocks))
+                want = masked_launch(n, n_cu, reset_blocks)
+                assert (epb, blocks.value) == (want[0], want[2]), (n, n_cu, reset_blocks, epb, blocks.value, want)
+                assert lib.cwh_reset_grid_of(want[1] * 4, n_cu, reset_blocks) == want[2]       # (the grid of that many chunks, four waves each)
+    # the reset-shaped grid on its own (cw_reset_kernel, cw_refill_kernel, cw_pool_kernel: one wave per env): ceil(jobs / 4), n_cu * reset_blocks at most, 1 at least
+    assert [lib.cwh_reset_grid_of(j, 256, 4) for j in (0, 1, 4, 5, 4096, 4097, 65536)] == [1, 1, 1, 2, 1024, 1024, 1024]
+    assert lib.cwh_reset_grid_of(4093, 256, 4) == 1024 and lib.cwh_reset_grid_of(4092, 256, 4) == 1023 and lib.cwh_reset_grid_of(2 ** 27, 304, 16) == 4864
+
+
+def test_the_envs_per_wave_rule():
+    """cwh_envs_per_wave (cw_host.h: what the step and rollout launchers call): `most` envs per wave, halved down to 8 while the waves would number under
+    1 024 -- the widths 64 / 32 / 16 / 8 tests/test_launch_shapes.py runs, at the N where each begins"""
+    f = host_lib()[1].cwh_envs_per_wave_of
+    for width in (64, 32, 16):                                                     # ceil(N / width) reaches 1 024 at N = 1 023 * width + 1
+        assert f(1023 * width + 1, 64) == width and f(1023 * width, 64) == width // 2, width
+    assert (f(65473, 64), f(32737, 64), f(16369, 64), f(16368, 64)) == (64, 32, 16, 8)
+    assert [f(n, 64) for n in (1, 7, 8, 8192)] == [8] * 4 and f(65536, 64) == 64 and f(2 ** 27, 64) == 64
+    for most in (32, 16):                                                          # CW_TUNE_STEP_ENVS_PER_WAVE caps the width, the thresholds below it stay
+        assert f(2 ** 20, most) == most and f(1023 * most + 1, most) == most and f(1023 * most, most) == most // 2
+    assert [f(n, 8) for n in (1, 8193, 2 ** 20)] == [8] * 3

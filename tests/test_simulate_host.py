@@ -1,5 +1,5 @@
 """CPU tier: the host side of simulate -- vec_env.simulate_args (what cw_simulate is handed, validated without a GPU), the ctypes mirror of cw_simulate_out
-against the C compiler's layout of the header's struct, the ABI entry, and the HIP-free argument rules of cw_simulate (cw_host.h: cwh_simulate_args,
+against the C compiler's layout of the header's struct, the ABI entry, and the HIP-free argument rules of cw_simulate and cw_expand (cw_host.h: cwh_records_args,
 cwh_ranges_overlap)."""
 import ctypes as C
 import os
@@ -109,22 +109,50 @@ def test_the_abi_entry():
 
 
 def test_the_argument_rules(lib):
-    """cwh_simulate_args: (num_envs, has env_of, has hdr_in, has slot_pos_in, n_states, n_steps, output fields) -> which rule refuses the call"""
+    """cwh_records_args, the one rule set of a call that reads packed records: (num_envs, has env_of, has hdr_in, has slot_pos_in, n_states, n_steps, output
+    fields, max_steps, broadcast) -> which rule refuses the call.  cw_simulate calls it with (32 767, 1), cw_expand -- no steps, its own states once -- with (0, 0)"""
     L, lib = lib
-    f = lib.cwh_simulate_args
-    assert (L.CWH_SIM_MAX_STATES, L.CWH_SIM_MAX_STEPS) == (2 ** 27, 32767)
+    assert (L.CWH_MAX_STATES, L.CWH_SIM_MAX_STEPS) == (2 ** 27, 32767)
+
+    def f(*args):
+        return lib.cwh_records_args(*args, L.CWH_SIM_MAX_STEPS, 1)
     for args in [(N, 0, 0, 0, N, 1, 1), (N, 0, 0, 0, 16 * N, 32767, 8), (N, 0, 1, 1, 0, 5, 1), (N, 0, 1, 1, 3, 5, 2), (N, 1, 1, 1, 1000, 5, 2),
                  (N, 0, 1, 1, 2 ** 27, 1, 1), (1, 0, 0, 0, 2 ** 27, 1, 1), (N, 1, 1, 1, 0, 1, 1)]:
-        assert f(*args) == L.CWH_SIM_OK, args
-    for args, code in [((N, 0, 0, 0, N, 1, 0), L.CWH_SIM_NO_FIELD), ((N, 0, 1, 1, 0, 1, 0), L.CWH_SIM_NO_FIELD),
-                       ((N, 0, 1, 1, -1, 1, 1), L.CWH_SIM_N_STATES), ((N, 0, 1, 1, 2 ** 27 + 1, 1, 1), L.CWH_SIM_N_STATES),
-                       ((N, 0, 1, 1, INT32_MAX, 1, 1), L.CWH_SIM_N_STATES), ((N, 0, 0, 0, -N, 1, 1), L.CWH_SIM_N_STATES),
-                       ((N, 0, 0, 0, N, 0, 1), L.CWH_SIM_N_STEPS), ((N, 0, 0, 0, N, -1, 1), L.CWH_SIM_N_STEPS), ((N, 0, 0, 0, N, 32768, 1), L.CWH_SIM_N_STEPS),
-                       ((N, 0, 1, 1, 4, INT32_MAX, 1), L.CWH_SIM_N_STEPS), ((N, 0, 1, 1, 4, -2 ** 31, 1), L.CWH_SIM_N_STEPS),
-                       ((N, 0, 1, 0, 4, 1, 1), L.CWH_SIM_PAIR), ((N, 0, 0, 1, 4, 1, 1), L.CWH_SIM_PAIR), ((N, 1, 0, 1, 4, 1, 1), L.CWH_SIM_PAIR),
-                       ((N, 1, 0, 0, N, 1, 1), L.CWH_SIM_ENV_OF),
-                       ((N, 0, 0, 0, 0, 1, 1), L.CWH_SIM_MULTIPLE), ((N, 0, 0, 0, N - 1, 1, 1), L.CWH_SIM_MULTIPLE), ((N, 0, 0, 0, N + 1, 1, 1), L.CWH_SIM_MULTIPLE),
-                       ((N, 0, 0, 0, 2 ** 27, 1, 1), L.CWH_SIM_MULTIPLE), ((0, 0, 0, 0, 4, 1, 1), L.CWH_SIM_MULTIPLE)]:
+        assert f(*args) == L.CWH_REC_OK, args
+    for args, code in [((N, 0, 0, 0, N, 1, 0), L.CWH_REC_NO_FIELD), ((N, 0, 1, 1, 0, 1, 0), L.CWH_REC_NO_FIELD),
+                       ((N, 0, 1, 1, -1, 1, 1), L.CWH_REC_N_STATES), ((N, 0, 1, 1, 2 ** 27 + 1, 1, 1), L.CWH_REC_N_STATES),
+                       ((N, 0, 1, 1, INT32_MAX, 1, 1), L.CWH_REC_N_STATES), ((N, 0, 0, 0, -N, 1, 1), L.CWH_REC_N_STATES),
+                       ((N, 0, 0, 0, N, 0, 1), L.CWH_REC_N_STEPS), ((N, 0, 0, 0, N, -1, 1), L.CWH_REC_N_STEPS), ((N, 0, 0, 0, N, 32768, 1), L.CWH_REC_N_STEPS),
+                       ((N, 0, 1, 1, 4, INT32_MAX, 1), L.CWH_REC_N_STEPS), ((N, 0, 1, 1, 4, -2 ** 31, 1), L.CWH_REC_N_STEPS),
+                       ((N, 0, 1, 0, 4, 1, 1), L.CWH_REC_PAIR), ((N, 0, 0, 1, 4, 1, 1), L.CWH_REC_PAIR), ((N, 1, 0, 1, 4, 1, 1), L.CWH_REC_PAIR),
+                       ((N, 1, 0, 0, N, 1, 1), L.CWH_REC_ENV_OF),
+                       ((N, 0, 0, 0, 0, 1, 1), L.CWH_REC_OWN_STATES), ((N, 0, 0, 0, N - 1, 1, 1), L.CWH_REC_OWN_STATES),
+                       ((N, 0, 0, 0, N + 1, 1, 1), L.CWH_REC_OWN_STATES), ((N, 0, 0, 0, 2 ** 27, 1, 1), L.CWH_REC_OWN_STATES),
+                       ((0, 0, 0, 0, 4, 1, 1), L.CWH_REC_OWN_STATES)]:
+        assert f(*args) == code, (args, code)
+
+
+def test_the_argument_rules_of_expand(lib):
+    """the same function as cw_expand calls it: no steps (whatever n_steps holds), and without records n_states is num_envs itself.  Each code is the one
+    cw_expand turns into its text (tests/test_expand.py pins the texts on the GPU)"""
+    L, lib = lib
+
+    def f(num_envs, env_of, hdr, pos, n_states, fields, n_steps=0):
+        return lib.cwh_records_args(num_envs, env_of, hdr, pos, n_states, n_steps, fields, 0, 0)
+    for args in [(N, 0, 0, 0, N, 1), (N, 0, 0, 0, N, 6), (1, 0, 0, 0, 1, 1), (2 ** 27, 0, 0, 0, 2 ** 27, 1),          # its own states
+                 (N, 0, 1, 1, 0, 1), (N, 0, 1, 1, 3, 2), (N, 0, 1, 1, N - 1, 1), (N, 0, 1, 1, N + 1, 1), (N, 0, 1, 1, 2 ** 27, 1),      # records: any count
+                 (N, 1, 1, 1, 1000, 2), (N, 1, 1, 1, 0, 1)]:
+        assert f(*args) == L.CWH_REC_OK, args
+    for n_steps in (0, -1, 1, 32768, INT32_MAX, -2 ** 31):                           # a call without steps: the value is not looked at
+        assert f(N, 0, 0, 0, N, 1, n_steps) == L.CWH_REC_OK, n_steps
+    for args, code in [((N, 0, 0, 0, N, 0), L.CWH_REC_NO_FIELD), ((N, 0, 1, 1, 0, 0), L.CWH_REC_NO_FIELD), ((N, 1, 0, 1, -1, 0), L.CWH_REC_NO_FIELD),
+                       ((N, 0, 0, 0, -1, 1), L.CWH_REC_N_STATES), ((N, 0, 1, 1, -1, 1), L.CWH_REC_N_STATES), ((N, 0, 0, 0, 2 ** 27 + 1, 1), L.CWH_REC_N_STATES),
+                       ((N, 0, 1, 1, 2 ** 27 + 1, 1), L.CWH_REC_N_STATES), ((N, 0, 1, 0, INT32_MAX, 1), L.CWH_REC_N_STATES),
+                       ((2 ** 27 + 1, 0, 0, 0, 2 ** 27 + 1, 1), L.CWH_REC_N_STATES),
+                       ((N, 0, 1, 0, 4, 1), L.CWH_REC_PAIR), ((N, 0, 0, 1, 4, 1), L.CWH_REC_PAIR), ((N, 1, 0, 1, 4, 1), L.CWH_REC_PAIR), ((N, 1, 1, 0, N, 1), L.CWH_REC_PAIR),
+                       ((N, 1, 0, 0, N, 1), L.CWH_REC_ENV_OF), ((N, 1, 0, 0, N + 1, 1), L.CWH_REC_ENV_OF),
+                       ((N, 0, 0, 0, 0, 1), L.CWH_REC_OWN_STATES), ((N, 0, 0, 0, N - 1, 1), L.CWH_REC_OWN_STATES), ((N, 0, 0, 0, N + 1, 1), L.CWH_REC_OWN_STATES),
+                       ((N, 0, 0, 0, 2 * N, 1), L.CWH_REC_OWN_STATES), ((N, 0, 0, 0, 2 ** 27, 1), L.CWH_REC_OWN_STATES)]:
         assert f(*args) == code, (args, code)
 
 
