@@ -12,7 +12,7 @@
 import torch
 
 from .sharding import shard_range
-from .vec_env import CraftingWorldVecEnv, reset_mask
+from .vec_env import CraftingWorldVecEnv, as_numpy, desired_bits, reset_mask
 
 
 class GymnasiumVecAdapter:
@@ -83,29 +83,25 @@ class MultiDeviceVecEnv:
     def reset_envs(self, mask):
         """reset() of the envs with mask[i] set (CraftingWorldVecEnv.reset_envs): the [num_envs] mask is split along self.ranges, each shard's part
         goes to that shard on its own stream; per-shard observation dicts as a list, like reset()."""
-        m = mask.cpu().numpy() if torch.is_tensor(mask) else mask
-        m = reset_mask(self.num_envs, mask=m)
         out = []
-        for (lo, hi), sh, st in zip(self.ranges, self.shards, self.streams):
+        for sh, st, m in zip(self.shards, self.streams, self._split_mask(mask, None)):      # (no mask: the first shard's reset_envs raises, as it does alone)
             with torch.cuda.stream(st):
-                out.append(sh.reset_envs(mask=m[lo:hi]))
+                out.append(sh.reset_envs(mask=m))
         return out
 
     def _split_mask(self, mask, indices):
         if mask is None and indices is None:
             return [None] * len(self.shards)
-        m = mask.cpu().numpy() if torch.is_tensor(mask) else mask
-        m = reset_mask(self.num_envs, mask=m, indices=indices)
+        m = reset_mask(self.num_envs, mask=as_numpy(mask), indices=indices)
         return [m[lo:hi] for lo, hi in self.ranges]
 
     def imagine_obs(self, mask=None, *, indices=None, desired=None, commit=False, one_hot=False):
         """CraftingWorldVecEnv.imagine_obs over the shards: the [num_envs] mask / indices and `desired` ([num_envs] masks or [num_envs, T] rows) are split
         along self.ranges, each part goes to its shard on that shard's stream; -> the shards' result tensors as a list."""
-        from .vec_env import desired_bits
         parts = self._split_mask(mask, indices)
         d = None
         if desired is not None:
-            d = desired_bits(self.num_envs, desired.cpu().numpy() if torch.is_tensor(desired) else desired, len(self.shards[0].task_list))
+            d = desired_bits(self.num_envs, as_numpy(desired), len(self.shards[0].task_list))
         out = []
         for (lo, hi), sh, st, m in zip(self.ranges, self.shards, self.streams, parts):
             with torch.cuda.stream(st):

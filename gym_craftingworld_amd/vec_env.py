@@ -56,7 +56,29 @@ def _menu_struct(task_list, selected_tasks, number_of_tasks, stacking, reward_st
     return m
 
 
-_NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64}
+_NP_OF = {torch.uint8: np.uint8, torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.bool: np.bool_}
+
+
+def as_numpy(a):
+    """a tensor (wherever it lives), an array or a list as a numpy array on the host; None stays None"""
+    if a is None:
+        return None
+    return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def _shape_dtype(a):
+    """(shape, numpy dtype) of a tensor or an array: what the validators below take in place of the data"""
+    return tuple(a.shape), _NP_OF.get(a.dtype, np.float64) if torch.is_tensor(a) else a.dtype
+
+
+def _vp(t):
+    """a tensor's address as the library takes it; None -> NULL"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _out_struct(cls, out):
+    """cw_expand_out / cw_simulate_out over the tensors of an out dict ('achieved_mask' is the structs' `achieved`); a field not asked for stays NULL"""
+    return cls(**{'achieved' if f == 'achieved_mask' else f: t.data_ptr() for f, t in out.items()})
 
 
 def _host_view(ptr, shape, dtype):
@@ -280,6 +302,20 @@ def render_records_args(frame_shape, hdr, slot_pos, mask=None, out=None):
     return m, lead
 
 
+def _field_names(fields, known, default):
+    names = default if fields is None else tuple(fields)
+    if not names or any(f not in known for f in names) or len(set(names)) != len(names):
+        raise ValueError('fields must be a non-empty subset of %s' % (known,))
+    return names
+
+
+# What _in_place does with a tensor that is NOT on the env's device.  Every call keeps the rule it came with:
+#   records, env_of, simulate's actions, render_records' mask   _RAISES: ValueError for another CUDA device, whatever else the tensor is; a CPU tensor is copied
+#   reset_envs / imagine_obs / sample_states: the mask          _RAISES_CPU_TOO: the same, and a CPU tensor raises as well -- unless host_outputs, then it is copied
+#   snapshot_save / snapshot_load: rows                         _RAISES_IF_ELIGIBLE: ValueError only if it would otherwise go over in place, else copied (CPU: copied)
+#   imagine_obs: desired                                        _COPIED: never an error -- copied through the host
+_RAISES, _RAISES_CPU_TOO, _RAISES_IF_ELIGIBLE, _COPIED = range(4)
+
 _LIVE = weakref.WeakSet()
 
 
@@ -424,19 +460,69 @@ class CraftingWorldVecEnv:
             init_observation=Box(0, 1, (self.size, self.size, 12), np.uint8)))
         self._pending = False
         self._actions_keepalive = None
-        self._mask_keepalive = None
+        self._keepalive = {}                                         # entry point -> the tensors its last call handed over (_call)
         self._cw_step, self._di = self._lib.cw_step, self.device.index
         self._raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (lambda di: torch.cuda.current_stream(di).cuda_stream)
         self.seed(seed)                                              # ray.py:70 (OS entropy when None)
         if self.fixed_init_state:                                    # ray.py:116-118
-            L.check(self._lib.cw_generate_fixed_states(self._h, self._stream()), 'cw_generate_fixed_states', self._lib)
+            self._call('cw_generate_fixed_states', sync=False)
 
     # ------------------------------------------------------------------ plumbing
     def _stream(self):
-        try:        # the raw handle without building a torch.cuda.Stream object (this sits on the per-step path)
-            return C.c_void_p(torch._C._cuda_getCurrentRawStream(self.device.index))
-        except AttributeError:
-            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(self._raw_stream(self._di))       # (the raw handle without building a torch.cuda.Stream object)
+
+    def _call(self, name, *args, sync=True, keep=None):
+        """The tail of a call that enqueues work: library entry point `name` with the engine, `args` and torch's current stream.  A tensor among `args`
+        goes over as its address and is kept alive under `name` until the next call of the same entry point (the kernel may not have run yet, and a
+        captured graph replays it), as is `keep`: tensors that go over inside a struct; what the caller alone owns goes in as a pointer (_vp) and is
+        not kept.  sync: a host_outputs engine waits for the work, its results being read by host code next."""
+        self._keepalive[name] = (args, keep)
+        rc = getattr(self._lib, name)(self._h, *[C.c_void_p(a.data_ptr()) if type(a) is torch.Tensor else a for a in args], self._stream())
+        if rc:
+            L.check(rc, name, self._lib)
+        if sync and self.host_outputs:
+            self._sync()
+
+    def _in_place(self, t, dtypes, shape=None, elsewhere=_RAISES, what='tensor'):
+        """Does `t` go to the kernel as it is -- no copy, no synchronisation?  Yes for a contiguous CUDA tensor on the env's device of one of `dtypes` (and
+        of `shape`, where one is given); everything else the caller validates and packs on the host and copies over.  elsewhere: the call's rule for a
+        tensor on another device (the table above _RAISES)."""
+        if type(t) is not torch.Tensor:
+            return False
+        here = t.device == self.device
+        if not here and (t.is_cuda and (elsewhere == _RAISES or elsewhere == _RAISES_CPU_TOO) or elsewhere == _RAISES_CPU_TOO and not self.host_outputs):
+            raise ValueError('the %s is on %s, the envs are on %s' % (what, t.device, self.device))
+        if not (t.is_cuda and t.dtype in dtypes and (shape is None or tuple(t.shape) == shape) and t.is_contiguous()):
+            return False
+        if not here and elsewhere == _RAISES_IF_ELIGIBLE:
+            raise ValueError('the %s is on %s, the envs are on %s' % (what, t.device, self.device))
+        return here
+
+    def _out(self, out, shape, full=True):
+        """The uint8 tensor a call writes: a fresh one, or the caller's once it is found to be a contiguous uint8 tensor of `shape` on the env's device
+        (ValueError otherwise; full=False: shape and dtype are left to the caller's own check)."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if (type(out) is not torch.Tensor or out.device != self.device or not out.is_contiguous()
+                or full and (out.dtype != torch.uint8 or tuple(out.shape) != shape)):
+            raise ValueError('out must be a contiguous uint8 tensor %s on %s' % (shape, self.device))
+        return out
+
+    def _out_dict(self, out, names, spec):
+        """The named tensors a call writes, spec[name] = (shape, dtype): fresh ones for `names` (a bool field is allocated as bytes and viewed: the kernels
+        write 0 / 1), or the caller's dict once it holds exactly `names`, each a contiguous tensor of its shape and dtype on the env's device (ValueError
+        otherwise)."""
+        if out is None:
+            out = {f: torch.empty(spec[f][0], dtype=torch.uint8 if spec[f][1] is torch.bool else spec[f][1], device=self.device) for f in names}
+            return {f: t.view(torch.bool) if spec[f][1] is torch.bool else t for f, t in out.items()}
+        if set(out) != set(names):
+            raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names)))
+        for f in names:
+            t = out[f]
+            if (type(t) is not torch.Tensor or tuple(t.shape) != spec[f][0] or t.dtype != spec[f][1] or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError('out[%r] must be a contiguous %s tensor %s on %s' % (f, spec[f][1], spec[f][0], self.device))
+        return out
 
     def close_extras(self, **kwargs):
         """gym.vector hook: nothing besides the engine to release."""
@@ -529,7 +615,7 @@ class CraftingWorldVecEnv:
         self._sync()
 
     def reset_async(self):
-        L.check(self._lib.cw_reset(self._h, self._stream()), 'cw_reset', self._lib)     # enqueues; nothing waits
+        self._call('cw_reset', sync=False)                  # enqueues; nothing waits
         self._has_reset = True
         self._reset_pending = True
 
@@ -552,33 +638,19 @@ class CraftingWorldVecEnv:
         manual-reset loop of an auto_reset=False engine (and can be captured into a graph with the steps).  Anything else (numpy, lists, `indices`)
         is validated and packed on the host (reset_mask) and copied over.  A selected row afterwards holds what reset() leaves there; reward, done,
         the episode statistics and the counters are not touched: a forced reset is not a finished episode."""
-        if type(mask) is torch.Tensor and (mask.is_cuda or not self.host_outputs) and mask.device != self.device:
-            raise ValueError('the mask tensor is on %s, the envs are on %s' % (mask.device, self.device))
-        if (type(mask) is torch.Tensor and indices is None and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
-                and tuple(mask.shape) == (self.num_envs,) and mask.is_contiguous()):
-            m = mask
-        else:
-            if torch.is_tensor(mask):
-                mask = mask.cpu().numpy()
-            m = torch.as_tensor(reset_mask(self.num_envs, mask, indices)).to(self.device)
-        self._mask_keepalive = m
-        L.check(self._lib.cw_reset_masked(self._h, C.c_void_p(m.data_ptr()), self._stream()), 'cw_reset_masked', self._lib)
-        if self.host_outputs:
-            self._sync()
+        m = self._select(mask, indices)
+        if m is None:
+            reset_mask(self.num_envs)           # (nothing given: its "exactly one of" ValueError)
+        self._call('cw_reset_masked', m)
         return self._observation()
 
     def _select(self, mask, indices):
         """mask / indices as reset_envs takes them -> the byte tensor the masked kernels read; None (every env) when neither is given."""
         if mask is None and indices is None:
             return None
-        if type(mask) is torch.Tensor and (mask.is_cuda or not self.host_outputs) and mask.device != self.device:
-            raise ValueError('the mask tensor is on %s, the envs are on %s' % (mask.device, self.device))
-        if (type(mask) is torch.Tensor and indices is None and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
-                and tuple(mask.shape) == (self.num_envs,) and mask.is_contiguous()):
+        if self._in_place(mask, (torch.bool, torch.uint8), (self.num_envs,), _RAISES_CPU_TOO, 'mask tensor') and indices is None:
             return mask
-        if torch.is_tensor(mask):
-            mask = mask.cpu().numpy()
-        return torch.as_tensor(reset_mask(self.num_envs, mask, indices)).to(self.device)
+        return torch.as_tensor(reset_mask(self.num_envs, as_numpy(mask), indices)).to(self.device)
 
     def imagine_obs(self, mask=None, *, indices=None, desired=None, commit=False, out=None, one_hot=False):
         """imagine_obs() (ray.py:220-299) of the selected envs against their RUNNING episode (cw_imagine_masked): a goal state drawn from each env's
@@ -593,15 +665,9 @@ class CraftingWorldVecEnv:
         On an engine that keeps look-ahead records (auto_reset=True on the device) the call rewinds every stream through the host first: correct, but off
         the hot path and not capturable; relabel on an auto_reset=False engine with reset_envs(env.done)."""
         m = self._select(mask, indices)
-        d = None
-        if desired is not None:
-            if (type(desired) is torch.Tensor and desired.is_cuda and desired.device == self.device and desired.dtype in (torch.uint16, torch.int16)
-                    and tuple(desired.shape) == (self.num_envs,) and desired.is_contiguous()):
-                d = desired
-            else:
-                if torch.is_tensor(desired):
-                    desired = desired.cpu().numpy()
-                d = torch.as_tensor(desired_bits(self.num_envs, desired, len(self.task_list)).view(np.int16)).to(self.device)
+        d = desired
+        if d is not None and not self._in_place(d, (torch.uint16, torch.int16), (self.num_envs,), _COPIED):
+            d = torch.as_tensor(desired_bits(self.num_envs, as_numpy(d), len(self.task_list)).view(np.int16)).to(self.device)
         shape = (self.num_envs, self.size, self.size, 12) if one_hot else (self.num_envs,) + self.frame_shape
         if out is None:
             key = '_imagine_oh' if one_hot else '_imagine_frames'
@@ -609,15 +675,9 @@ class CraftingWorldVecEnv:
             if out is None:
                 out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
                 setattr(self, key, out)
-        elif not (type(out) is torch.Tensor and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()
-                  and out.device == self.device):
-            raise ValueError('out must be a contiguous uint8 tensor of shape %s on %s' % (shape, self.device))
-        self._imagine_keepalive = (m, d)
-        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        L.check(self._lib.cw_imagine_masked(self._h, vp(m), vp(d), 1 if commit else 0, None if one_hot else vp(out), vp(out) if one_hot else None,
-                                            self._stream()), 'cw_imagine_masked', self._lib)
-        if self.host_outputs:
-            self._sync()
+        else:
+            self._out(out, shape)
+        self._call('cw_imagine_masked', m, d, 1 if commit else 0, None if one_hot else _vp(out), _vp(out) if one_hot else None)
         return out
 
     def sample_states(self, mask=None, *, indices=None, pooled=False):
@@ -631,11 +691,7 @@ class CraftingWorldVecEnv:
         out = getattr(self, '_sample_cells', None)
         if out is None:
             out = self._sample_cells = torch.zeros((self.num_envs, 9), dtype=torch.int16, device=self.device).view(torch.uint16)
-        self._imagine_keepalive = (m, None)
-        L.check(self._lib.cw_sample_state_masked(self._h, C.c_void_p(m.data_ptr()) if m is not None else None, 1 if pooled else 0,
-                                                 C.c_void_p(out.data_ptr()), self._stream()), 'cw_sample_state_masked', self._lib)
-        if self.host_outputs:
-            self._sync()
+        self._call('cw_sample_state_masked', m, 1 if pooled else 0, _vp(out))
         return out
 
     # ------------------------------------------------------------------ device-resident snapshots
@@ -657,30 +713,18 @@ class CraftingWorldVecEnv:
         return int(self._counters_raw[6].item())
 
     def _snapshot_rows(self, rows, envs, fork):
-        if (type(rows) is torch.Tensor and envs is None and rows.is_cuda and rows.dtype == torch.int32 and tuple(rows.shape) == (self.num_envs,)
-                and rows.is_contiguous()):
-            if rows.device != self.device:
-                raise ValueError('the rows tensor is on %s, the envs are on %s' % (rows.device, self.device))
-            r = rows
-        else:
-            if torch.is_tensor(rows):
-                rows = rows.cpu().numpy()
-            if torch.is_tensor(envs):
-                envs = envs.cpu().numpy()
-            cap = getattr(self, '_snapshot_capacity', 0) if self.snapshot_row_bytes else 2 ** 31 - 1      # (no bank: the library reports the call order)
-            r = torch.as_tensor(snapshot_rows(self.num_envs, cap, rows, envs, fork)).to(self.device)
-        self._rows_keepalive = r
-        return C.c_void_p(r.data_ptr())
+        """rows / envs as snapshot_save and snapshot_load take them -> the int32 tensor [num_envs] the kernels read"""
+        if envs is None and self._in_place(rows, (torch.int32,), (self.num_envs,), _RAISES_IF_ELIGIBLE, 'rows tensor'):
+            return rows
+        cap = getattr(self, '_snapshot_capacity', 0) if self.snapshot_row_bytes else 2 ** 31 - 1      # (no bank: the library reports the call order)
+        return torch.as_tensor(snapshot_rows(self.num_envs, cap, as_numpy(rows), as_numpy(envs), fork)).to(self.device)
 
     def snapshot_save(self, rows=None, *, envs=None):
         """Save envs into rows of the bank (cw_snapshot_save: one kernel, no host round trip, capturable): env i into row rows[i].  A contiguous
         torch.int32 tensor [num_envs] on the env's device is handed over in place -- no copy, no synchronisation; a negative entry = env i takes no
         part, an entry at or above the capacity is skipped and counted (snapshot_skipped).  Anything else is validated and packed on the host
         (snapshot_rows): `rows` alone holds one entry per env, `envs=[3, 5], rows=[0, 1]` pairs envs with rows.  Nothing of the envs changes."""
-        p = self._snapshot_rows(rows, envs, False)
-        L.check(self._lib.cw_snapshot_save(self._h, p, self._stream()), 'cw_snapshot_save', self._lib)
-        if self.host_outputs:
-            self._sync()
+        self._call('cw_snapshot_save', self._snapshot_rows(rows, envs, False))
 
     def snapshot_load(self, rows=None, *, envs=None, with_stream=True):
         """Load rows of the bank into envs (cw_snapshot_load): env i from row rows[i], `rows` / `envs` as in snapshot_save; any number of envs may name
@@ -689,10 +733,7 @@ class CraftingWorldVecEnv:
         on with episodes of its own.  A row never saved since snapshot_reserve is skipped and counted like a row outside the bank.  reward, done, the
         episode statistics and counters[0..5] are not touched; achieved_mask / desired_mask and, in the pixel modes, the three frames show the
         restored state at once.  -> the observation dict (live views, as reset_envs returns)."""
-        p = self._snapshot_rows(rows, envs, True)
-        L.check(self._lib.cw_snapshot_load(self._h, p, 1 if with_stream else 0, self._stream()), 'cw_snapshot_load', self._lib)
-        if self.host_outputs:
-            self._sync()
+        self._call('cw_snapshot_load', self._snapshot_rows(rows, envs, True), 1 if with_stream else 0)
         return self._observation()
 
     # ------------------------------------------------------------------ looking one step ahead
@@ -701,41 +742,28 @@ class CraftingWorldVecEnv:
         """how many states expand() and simulate() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
         return int(self._counters_raw[7].item())
 
-    _NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.int8: np.int8}
-
-    def _in_place(self, t, dtypes):
-        """a contiguous tensor on the env's device of one of `dtypes` goes to the kernel as it is"""
-        if type(t) is not torch.Tensor or not t.is_cuda:
-            return False
-        if t.device != self.device:
-            raise ValueError('the tensor is on %s, the envs are on %s' % (t.device, self.device))
-        return t.dtype in dtypes and t.is_contiguous()
-
     def _records(self, hdr, slot_pos, env_of):
         """hdr / slot_pos / env_of as expand() and one_hot_states() take them -> (M, leading shape, device tensors or None)"""
         if hdr is None or slot_pos is None:
             return _expand_m(self.num_envs, None if hdr is None else ((16,), np.uint8), None if slot_pos is None else ((8,), np.int16),
                              None if env_of is None else ((0,), np.int32)), (self.num_envs,), None, None, None
         h_dev, p_dev = self._in_place(hdr, (torch.uint8,)), self._in_place(slot_pos, (torch.int16,))
-        e_dev = env_of is not None and self._in_place(env_of, (torch.int32,))
-        as_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+        e_dev = env_of is None or self._in_place(env_of, (torch.int32,))
         if not h_dev:
-            hdr = as_np(hdr)
+            hdr = as_numpy(hdr)
         if not p_dev:
-            slot_pos = as_np(slot_pos)
-        if env_of is not None and not e_dev:
-            env_of = as_np(env_of)
-        def sd(a, empty=None):          # (shape, numpy dtype) of a device tensor or a numpy array; an empty env_of list is an empty list of ints
-            if torch.is_tensor(a):
-                return tuple(a.shape), self._NP_OF.get(a.dtype, np.float64)
-            return tuple(a.shape), a.dtype if a.size or empty is None else empty
-        m = _expand_m(self.num_envs, sd(hdr), sd(slot_pos), None if env_of is None else sd(env_of, np.dtype(np.int32)))
+            slot_pos = as_numpy(slot_pos)
+        if not e_dev:
+            env_of = as_numpy(env_of)
+            if not env_of.size:
+                env_of = env_of.astype(np.int32)        # (an empty list is an empty list of ints)
+        m = _expand_m(self.num_envs, _shape_dtype(hdr), _shape_dtype(slot_pos), None if env_of is None else _shape_dtype(env_of))
         lead = tuple(hdr.shape[:-1])
         if not h_dev:
             hdr = torch.as_tensor(np.ascontiguousarray(hdr)).to(self.device)
         if not p_dev:
             slot_pos = torch.as_tensor(np.ascontiguousarray(slot_pos).view(np.int16)).to(self.device)
-        if env_of is not None and not e_dev:
+        if not e_dev:
             if env_of.size and int(env_of.max()) >= self.num_envs:
                 raise IndexError('env index %d outside a batch of %d envs' % (int(env_of.max()), self.num_envs))
             env_of = torch.as_tensor(np.ascontiguousarray(np.maximum(env_of.astype(np.int64), -1), dtype=np.int32)).to(self.device)
@@ -754,33 +782,13 @@ class CraftingWorldVecEnv:
         Contiguous tensors on the env's device go over in place -- no copy, no synchronisation; an env_of entry >= num_envs is then skipped by the kernel
         and counted (expand_skipped).  Anything else is validated on the host (expand_args: ValueError, IndexError).
         fields: a subset of EXPAND_FIELDS to compute (default all).  out: a dict returned by an earlier call with the same M and fields, written again."""
-        names = EXPAND_FIELDS if fields is None else tuple(fields)
-        if not names or any(f not in EXPAND_FIELDS for f in names) or len(set(names)) != len(names):
-            raise ValueError('fields must be a non-empty subset of %s' % (EXPAND_FIELDS,))
+        names = _field_names(fields, EXPAND_FIELDS, EXPAND_FIELDS)
         m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
         spec = {'reward': ((6, m), torch.int32), 'done': ((6, m), torch.bool), 'changed': ((6, m), torch.bool),
                 'achieved_mask': ((6, m), self.achieved_mask.dtype), 'hdr': ((6, m, 16), torch.uint8), 'slot_pos': ((6, m, 8), self.slot_pos.dtype)}
-        if out is None:
-            out = {f: torch.empty(spec[f][0], dtype=torch.uint8 if spec[f][1] is torch.bool else spec[f][1], device=self.device) for f in names}
-            out = {f: t.view(torch.bool) if spec[f][1] is torch.bool else t for f, t in out.items()}
-        else:
-            if set(out) != set(names):
-                raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names)))
-            for f in names:
-                t = out[f]
-                if (type(t) is not torch.Tensor or tuple(t.shape) != spec[f][0] or t.dtype != spec[f][1] or t.device != self.device
-                        or not t.is_contiguous()):
-                    raise ValueError('out[%r] must be a contiguous %s tensor %s on %s' % (f, spec[f][1], spec[f][0], self.device))
-        if m == 0:
-            return out
-        ptr = lambda f: C.c_void_p(out[f].data_ptr()) if f in out else None  # noqa: E731
-        o = L.cw_expand_out(reward=ptr('reward'), done=ptr('done'), changed=ptr('changed'), achieved=ptr('achieved_mask'), hdr=ptr('hdr'),
-                            slot_pos=ptr('slot_pos'))
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        self._expand_keepalive = (hdr, slot_pos, env_of, out)
-        L.check(self._lib.cw_expand(self._h, vp(env_of), vp(hdr), vp(slot_pos), m, C.byref(o), self._stream()), 'cw_expand', self._lib)
-        if self.host_outputs:
-            self._sync()
+        out = self._out_dict(out, names, spec)
+        if m:
+            self._call('cw_expand', env_of, hdr, slot_pos, m, C.byref(_out_struct(L.cw_expand_out, out)), keep=out)
         return out
 
     # ------------------------------------------------------------------ trying plans
@@ -798,41 +806,20 @@ class CraftingWorldVecEnv:
         record after the last step taken, byte for byte what step() leaves on an auto_reset=False engine) and, only when named in `fields`, the traces
         'rewards' int32 [T, M] / 'dones' bool [T, M] (rows after a stopped state's end: 0 / False).  fields: a subset of SIMULATE_FIELDS (default: the
         six per-state ones).  out: a dict returned by an earlier call with the same T, M and fields, written again."""
-        names = SIMULATE_FIELDS[:6] if fields is None else tuple(fields)
-        if not names or any(f not in SIMULATE_FIELDS for f in names) or len(set(names)) != len(names):
-            raise ValueError('fields must be a non-empty subset of %s' % (SIMULATE_FIELDS,))
+        names = _field_names(fields, SIMULATE_FIELDS, SIMULATE_FIELDS[:6])
         own = hdr is None and slot_pos is None
         m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
         if self._in_place(actions, (torch.uint8,)):
             T, m = _simulate_tm(self.num_envs, actions.shape, np.uint8, None if own else m)
         else:
-            a = actions.cpu().numpy() if torch.is_tensor(actions) else np.asarray(actions)
+            a = as_numpy(actions)
             T, m = _simulate_tm(self.num_envs, a.shape, a.dtype, None if own else m)
             actions = torch.as_tensor(simulate_actions(a)).to(self.device)
         spec = {'ret': ((m,), torch.int32), 'length': ((m,), torch.int32), 'done': ((m,), torch.bool), 'achieved_mask': ((m,), self.achieved_mask.dtype),
                 'hdr': ((m, 16), torch.uint8), 'slot_pos': ((m, 8), self.slot_pos.dtype), 'rewards': ((T, m), torch.int32), 'dones': ((T, m), torch.bool)}
-        if out is None:
-            out = {f: torch.empty(spec[f][0], dtype=torch.uint8 if spec[f][1] is torch.bool else spec[f][1], device=self.device) for f in names}
-            out = {f: t.view(torch.bool) if spec[f][1] is torch.bool else t for f, t in out.items()}
-        else:
-            if set(out) != set(names):
-                raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names)))
-            for f in names:
-                t = out[f]
-                if (type(t) is not torch.Tensor or tuple(t.shape) != spec[f][0] or t.dtype != spec[f][1] or t.device != self.device
-                        or not t.is_contiguous()):
-                    raise ValueError('out[%r] must be a contiguous %s tensor %s on %s' % (f, spec[f][1], spec[f][0], self.device))
-        if m == 0:
-            return out
-        ptr = lambda f: C.c_void_p(out[f].data_ptr()) if f in out else None  # noqa: E731
-        o = L.cw_simulate_out(ret=ptr('ret'), length=ptr('length'), done=ptr('done'), achieved=ptr('achieved_mask'), hdr=ptr('hdr'),
-                              slot_pos=ptr('slot_pos'), rewards=ptr('rewards'), dones=ptr('dones'))
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        self._simulate_keepalive = (actions, hdr, slot_pos, env_of, out)
-        L.check(self._lib.cw_simulate(self._h, vp(env_of), vp(hdr), vp(slot_pos), m, vp(actions), T, 1 if stop_at_done else 0, C.byref(o),
-                                      self._stream()), 'cw_simulate', self._lib)
-        if self.host_outputs:
-            self._sync()
+        out = self._out_dict(out, names, spec)
+        if m:
+            self._call('cw_simulate', env_of, hdr, slot_pos, m, actions, T, 1 if stop_at_done else 0, C.byref(_out_struct(L.cw_simulate_out, out)), keep=out)
         return out
 
     def one_hot_states(self, hdr, slot_pos, out=None):
@@ -842,19 +829,9 @@ class CraftingWorldVecEnv:
         if hdr is None or slot_pos is None:
             raise ValueError('one_hot_states needs hdr and slot_pos')
         m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
-        shape = lead + (self.size, self.size, 12)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        elif (type(out) is not torch.Tensor or tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != self.device
-              or not out.is_contiguous()):
-            raise ValueError('out must be a contiguous uint8 tensor %s on %s' % (shape, self.device))
-        if m == 0:
-            return out
-        self._onehot_states_keepalive = (hdr, slot_pos, out)
-        L.check(self._lib.cw_export_onehot_states(self._h, C.c_void_p(hdr.data_ptr()), C.c_void_p(slot_pos.data_ptr()), m, C.c_void_p(out.data_ptr()),
-                                                  self._stream()), 'cw_export_onehot_states', self._lib)
-        if self.host_outputs:
-            self._sync()
+        out = self._out(out, lead + (self.size, self.size, 12))
+        if m:
+            self._call('cw_export_onehot_states', hdr, slot_pos, m, out)
         return out
 
     def render_records(self, hdr, slot_pos, *, mask=None, out=None):
@@ -870,25 +847,17 @@ class CraftingWorldVecEnv:
             raise ValueError('render_records needs hdr and slot_pos')
         m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
         m_dev = mask is not None and self._in_place(mask, (torch.bool, torch.uint8))
-        if mask is not None and not m_dev:
-            mask = mask.cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
-        if out is not None and (type(out) is not torch.Tensor or out.device != self.device or not out.is_contiguous()):
-            raise ValueError('out must be a contiguous uint8 tensor %s on %s' % (lead + tuple(self.frame_shape), self.device))
-        np_of = lambda t: np.bool_ if t.dtype is torch.bool else self._NP_OF.get(t.dtype, np.float64)  # noqa: E731
-        _render_records_m(self.frame_shape, lead, None if mask is None else (tuple(mask.shape), np_of(mask) if m_dev else mask.dtype),
-                          None if out is None else (tuple(out.shape), np_of(out)))
+        if not m_dev:
+            mask = as_numpy(mask)
+        if out is not None:
+            self._out(out, lead + tuple(self.frame_shape), full=False)
+        _render_records_m(self.frame_shape, lead, None if mask is None else _shape_dtype(mask), None if out is None else _shape_dtype(out))
         if mask is not None and not m_dev:
             mask = torch.as_tensor(np.ascontiguousarray(mask).view(np.uint8)).to(self.device)
         if out is None:
-            out = torch.empty(lead + tuple(self.frame_shape), dtype=torch.uint8, device=self.device)
-        if m == 0:
-            return out
-        self._render_records_keepalive = (hdr, slot_pos, mask, out)
-        L.check(self._lib.cw_render_records(self._h, C.c_void_p(hdr.data_ptr()), C.c_void_p(slot_pos.data_ptr()),
-                                            None if mask is None else C.c_void_p(mask.data_ptr()), m, C.c_void_p(out.data_ptr()), self._stream()),
-                'cw_render_records', self._lib)
-        if self.host_outputs:
-            self._sync()
+            out = self._out(None, lead + tuple(self.frame_shape))
+        if m:
+            self._call('cw_render_records', hdr, slot_pos, mask, m, out)
         return out
 
     def step_async(self, actions):
@@ -956,9 +925,7 @@ class CraftingWorldVecEnv:
         if not (type(actions) is torch.Tensor and actions.dtype in _ACT_DTYPES and actions.device == self.device and actions.is_contiguous()
                 and actions.dim() == 2 and actions.shape[1] == self.num_envs):
             raise ValueError('actions must be a contiguous [K, num_envs] tensor of dtype uint8 / int32 / int64 on %s' % (self.device,))
-        self._actions_keepalive = actions
-        L.check(self._lib.cw_step_many(self._h, C.c_void_p(actions.data_ptr()), _ACT_DTYPES[actions.dtype], int(actions.shape[0]), self._stream()),
-                'cw_step_many', self._lib)
+        self._call('cw_step_many', actions, _ACT_DTYPES[actions.dtype], int(actions.shape[0]), sync=False)
 
     def capture_steps(self, actions):
         """-> a torch.cuda.CUDAGraph that takes K = actions.shape[0] steps per replay(), reading row t of the device tensor `actions` [K, N] on
@@ -992,10 +959,7 @@ class CraftingWorldVecEnv:
         T = actions.shape[0]
         rew = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device) if record else None
         don = torch.empty((T, self.num_envs), dtype=torch.uint8, device=self.device) if record else None
-        L.check(self._lib.cw_rollout(self._h, C.c_void_p(actions.data_ptr()), T,
-                                     C.c_void_p(rew.data_ptr()) if record else None,
-                                     C.c_void_p(don.data_ptr()) if record else None, self._stream()), 'cw_rollout', self._lib)
-        self._actions_keepalive = actions
+        self._call('cw_rollout', actions, T, _vp(rew), _vp(don), sync=False)      # (the results are the caller's alone)
         return (rew, don.view(torch.bool)) if record else None
 
     # ------------------------------------------------------------------ views / checkpoints
@@ -1003,7 +967,7 @@ class CraftingWorldVecEnv:
         """render() of ray.py:442-520 for every env -> uint8 [N,4S,4S,3] (works in every obs_mode)."""
         if out is None:
             out = torch.empty((self.num_envs,) + self.frame_shape, dtype=torch.uint8, device=self.device)
-        L.check(self._lib.cw_render(self._h, C.c_void_p(out.data_ptr()), self._stream()), 'cw_render', self._lib)
+        self._call('cw_render', _vp(out), sync=False)
         return out
 
     def render_exact(self):
@@ -1023,16 +987,14 @@ class CraftingWorldVecEnv:
         if oh.dim() != 4 or tuple(oh.shape[1:]) != (self.size, self.size, 12):
             raise ValueError('states must have shape [M, %d, %d, 12]' % (self.size, self.size))
         out = torch.empty((oh.shape[0],) + self.frame_shape, dtype=torch.int16, device=self.device)
-        L.check(self._lib.cw_render_onehot(self._h, C.c_void_p(oh.data_ptr()), oh.shape[0], C.c_void_p(out.data_ptr()), self._stream()),
-                'cw_render_onehot', self._lib)
-        self._states_keepalive = oh
+        self._call('cw_render_onehot', oh, oh.shape[0], _vp(out), sync=False)
         return out
 
     def grid(self, out=None):
         """Dense cell codes uint8 [N,S,S] (0 empty, k+1 = OBJECTS[k])."""
         if out is None:
             out = torch.empty((self.num_envs, self.size, self.size), dtype=torch.uint8, device=self.device)
-        L.check(self._lib.cw_export_grid(self._h, C.c_void_p(out.data_ptr()), self._stream()), 'cw_export_grid', self._lib)
+        self._call('cw_export_grid', _vp(out), sync=False)
         return out
 
     def one_hot(self, out=None, which='current'):
@@ -1041,7 +1003,7 @@ class CraftingWorldVecEnv:
         if out is None:
             out = torch.empty((self.num_envs, self.size, self.size, 12), dtype=torch.uint8, device=self.device)
         w = {'current': 0, 'goal': 1, 'init': 2}[which]
-        L.check(self._lib.cw_export_onehot_of(self._h, w, C.c_void_p(out.data_ptr()), self._stream()), 'cw_export_onehot_of', self._lib)
+        self._call('cw_export_onehot_of', w, _vp(out), sync=False)
         return out
 
     def mask_to_vector(self, mask):
