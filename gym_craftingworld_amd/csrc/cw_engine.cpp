@@ -37,6 +37,8 @@ hipError_t cwk_launch_resident(const CwParams *P, CwResident *R, uint32_t seq0, 
                                unsigned long long life_ticks, hipStream_t st);
 hipError_t cwk_launch_render_onehot(const CwParams *P, const uint8_t *onehot, int n_states, uint16_t *out, hipStream_t st);
 hipError_t cwk_launch_render_restore(const CwParams *P, const CwTuning *T, hipStream_t st);
+hipError_t cwk_launch_plan(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, int depth, const CwPlanOut *O,
+                           hipStream_t st);
 hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
                                int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
@@ -212,7 +214,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -899,12 +901,12 @@ static bool overlaps_records(const void *out, uint64_t out_bytes, const void *hd
     return cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)hdr, rec_bytes) ||
            cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)pos, rec_bytes);
 }
-// What cw_expand (max_steps 0: no steps, its own states once) and cw_simulate (its own states broadcast) check alike: the HIP-free rules of cw_host.cpp
+// What cw_expand (max_steps 0: no steps, its own states once), cw_plan (the same, depth already checked) and cw_simulate (its own states broadcast) check alike: the HIP-free rules of cw_host.cpp
 // (cwh_records_args, tested on the CPU) as the caller's error text, then the alignment of the records in and out.
 static int records_args(const char *who, const cw_engine *e, const void *env_of, const void *hdr_in, const void *pos_in, int32_t n_states, int32_t n_steps,
-                        int32_t max_steps, int n_fields, const void *out_hdr, const void *out_pos)
+                        int32_t max_steps, bool broadcast, int n_fields, const void *out_hdr, const void *out_pos)
 {
-    switch (cwh_records_args(e->n, env_of != nullptr, hdr_in != nullptr, pos_in != nullptr, n_states, n_steps, n_fields, max_steps, max_steps > 0)) {
+    switch (cwh_records_args(e->n, env_of != nullptr, hdr_in != nullptr, pos_in != nullptr, n_states, n_steps, n_fields, max_steps, broadcast)) {
     case CWH_REC_OK: break;
     case CWH_REC_NO_FIELD: return fail(CW_ERR_INVALID, "%s: every field of out is null", who);
     case CWH_REC_N_STATES: return fail(CW_ERR_INVALID, "%s: n_states = %d must be 0 .. %d", who, n_states, CWH_MAX_STATES);
@@ -912,7 +914,7 @@ static int records_args(const char *who, const cw_engine *e, const void *env_of,
     case CWH_REC_PAIR: return fail(CW_ERR_INVALID, "%s: %s given without %s", who, hdr_in ? "hdr_in" : "slot_pos_in", hdr_in ? "slot_pos_in" : "hdr_in");
     case CWH_REC_ENV_OF: return fail(CW_ERR_INVALID, "%s: env_of given without hdr_in", who);
     default:
-        return fail(CW_ERR_INVALID, "%s: n_states = %d must be %snum_envs = %d without hdr_in", who, n_states, max_steps > 0 ? "a positive multiple of " : "", e->n);
+        return fail(CW_ERR_INVALID, "%s: n_states = %d must be %snum_envs = %d without hdr_in", who, n_states, broadcast ? "a positive multiple of " : "", e->n);
     }
     int rc = aligned16(hdr_in, "hdr_in", who);
     if (rc == CW_OK) rc = aligned16(pos_in, "slot_pos_in", who);
@@ -935,7 +937,7 @@ int cw_expand(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const 
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_expand: null %s", !e ? "engine" : "out");
     const int n_fields = !!out->reward + !!out->done + !!out->changed + !!out->achieved + !!out->hdr + !!out->slot_pos;
-    const int bad = records_args("cw_expand", e, env_of, hdr_in, slot_pos_in, n_states, 0, 0, n_fields, out->hdr, out->slot_pos);
+    const int bad = records_args("cw_expand", e, env_of, hdr_in, slot_pos_in, n_states, 0, 0, false, n_fields, out->hdr, out->slot_pos);
     if (bad != CW_OK) return bad;
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_expand called before cw_reset");
     if (n_states == 0) return CW_OK;
@@ -956,7 +958,7 @@ int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, cons
 {
     if (!e || !out || !actions) return fail(CW_ERR_INVALID, "cw_simulate: null %s", !e ? "engine" : !out ? "out" : "actions");
     const int n_fields = !!out->ret + !!out->length + !!out->done + !!out->achieved + !!out->hdr + !!out->slot_pos + !!out->rewards + !!out->dones;
-    const int bad = records_args("cw_simulate", e, env_of, hdr_in, slot_pos_in, n_states, n_steps, CWH_SIM_MAX_STEPS, n_fields, out->hdr, out->slot_pos);
+    const int bad = records_args("cw_simulate", e, env_of, hdr_in, slot_pos_in, n_states, n_steps, CWH_SIM_MAX_STEPS, true, n_fields, out->hdr, out->slot_pos);
     if (bad != CW_OK) return bad;
     // the records the kernel reads: the caller's n_states, or the engine's own num_envs
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
@@ -973,6 +975,33 @@ int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, cons
     O.ret = out->ret; O.length = out->length; O.done = out->done; O.achieved = out->achieved;
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.rewards = out->rewards; O.dones = out->dones;
     HIP_TRY(cwk_launch_simulate(&e->P, env_of, h, p, hdr_in ? 0 : 1, n_states, actions, n_steps, stop_at_done ? 1 : 0, &O, (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ plan: the best return within `depth` steps after each first action
+// cw_expand's shape: checks (cwh_plan_args: cw_expand's rules, the depth and the cap on one launch's work), then ONE kernel.  Writes nothing of the engine
+// but counters[7].
+int cw_plan(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t depth, const cw_plan_out *out,
+            cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_plan: null %s", !e ? "engine" : "out");
+    const int n_fields = !!out->q + !!out->length + !!out->done + !!out->achieved + !!out->hdr + !!out->slot_pos + !!out->plan;
+    switch (cwh_plan_args(e->n, env_of != nullptr, hdr_in != nullptr, slot_pos_in != nullptr, n_states, depth, n_fields)) {
+    case CWH_REC_N_STEPS: return fail(CW_ERR_INVALID, "cw_plan: depth = %d must be 1 .. %d", depth, CWH_PLAN_MAX_DEPTH);
+    case CWH_REC_PLAN_WORK: return fail(CW_ERR_INVALID, "cw_plan: n_states = %d times 6^depth = 6^%d is above 2^32 plans in one call", n_states, depth);
+    default: break;
+    }
+    const int bad = records_args("cw_plan", e, env_of, hdr_in, slot_pos_in, n_states, depth, CWH_PLAN_MAX_DEPTH, false, n_fields, out->hdr, out->slot_pos);
+    if (bad != CW_OK) return bad;
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_plan called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    CwPlanOut O;
+    O.q = out->q; O.length = out->length; O.done = out->done; O.achieved = out->achieved;
+    O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.plan = out->plan;
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    HIP_TRY(cwk_launch_plan(&e->P, env_of, h, p, n_states, depth, &O, (hipStream_t)stream));
     return in.done();
 }
 

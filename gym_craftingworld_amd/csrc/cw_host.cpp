@@ -193,6 +193,16 @@ int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_s
     return CWH_REC_OK;
 }
 
+int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t depth, int n_out_fields)
+{
+    const int rc = cwh_records_args(num_envs, has_env_of, has_hdr_in, has_slot_pos_in, n_states, depth, n_out_fields, CWH_PLAN_MAX_DEPTH, 0);
+    if (rc == CWH_REC_NO_FIELD || rc == CWH_REC_N_STATES || rc == CWH_REC_N_STEPS) return rc;
+    uint64_t leaves = (uint64_t)n_states;                             // (<= 2^27, times 6^8 < 2^21: no overflow)
+    for (int32_t d = 0; d < depth; d++) leaves *= 6u;
+    if (leaves > CWH_PLAN_MAX_LEAVES) return CWH_REC_PLAN_WORK;
+    return rc;
+}
+
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)
 {
     if (!a_bytes || !b_bytes) return 0;

@@ -108,6 +108,13 @@ int cwh_envs_per_wave_of(int n, int most);         // (the same, exported for th
 enum { CWH_REC_OK = 0, CWH_REC_NO_FIELD = 1, CWH_REC_N_STATES = 2, CWH_REC_N_STEPS = 3, CWH_REC_PAIR = 4, CWH_REC_ENV_OF = 5, CWH_REC_OWN_STATES = 6 };
 int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields,
                      int32_t max_steps, int broadcast);
+// ... and of cw_plan: cwh_records_args as cw_expand calls it (its own states once, no broadcast) with 1 <= depth <= CWH_PLAN_MAX_DEPTH in the place of n_steps
+// (CWH_REC_N_STEPS), and behind that check and before the pointer rules the cap on the work of ONE launch: n_states * 6^depth <= CWH_PLAN_MAX_LEAVES
+// (CWH_REC_PLAN_WORK) -- 65 536 states at depth 6, 2 048 at depth 8.
+#define CWH_PLAN_MAX_DEPTH 8
+#define CWH_PLAN_MAX_LEAVES (1ull << 32)
+enum { CWH_REC_PLAN_WORK = 7 };
+int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t depth, int n_out_fields);
 // the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
 

@@ -18,6 +18,8 @@
 //   cw_render_records_kernel  the frames of such records in the engine's raster, one wave per state (paint_state_frame); writes nothing of the engine.
 //   cw_simulate_kernel  T steps of M such states along M action sequences of the caller's, one lane per state, the state in registers throughout, the
 //                     action bytes fetched a block of steps ahead; writes nothing of the engine.
+//   cw_plan_kernel    the best return within D steps after each first action of M such states and the plan that reaches it: one lane per (first action,
+//                     state) pair, a depth-first search with its stack in registers and a wave-uniform action at every level; writes nothing of the engine.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -751,8 +753,98 @@ __global__ __launch_bounds__(256) void cw_simulate_kernel(CwParams P, const int3
     if (O.pos) O.pos[j] = pack_pos(sp);
 }
 
+// ------------------------------------------------------------------------------------ plan
+// cw_plan: the best return within D steps after each first action, by exhaustive depth-first search -- cw_expand_kernel's launch shape and input handling
+// (one lane per (first action, state) pair, blockIdx.y the first action, the same env_of rules and counters[7] by the action-0 waves), cw_simulate_kernel's
+// semantics for every plan (stop_at_done).  The three 16-byte loads happen once, up front; the search touches no memory and no LDS.
+// THE STACK IS IN NAMED REGISTERS: plan_level<L> is inlined into plan_level<L - 1>, each level's saved record (header, packed slots, return so far) being
+// its own by-value parameters -- no array is indexed by a run-time value, so nothing goes to scratch.  CW_PLAN_MAX_DEPTH levels are built; `depth` is
+// a uniform run-time test at each.  That is one copy of step_env per level (the action loop is NOT unrolled), eight in all.
+// THE ORDER IS THE SAME IN EVERY LANE, so the action at every level is the loop's counter: wave-uniform, step_env's `a == ...` are scalar branches (what
+// cw_expand_kernel gets from a literal), and the digits of the path so far are a scalar too.  A lane whose prefix is done, or which cannot improve (below),
+// does not descend: the `if` around the next level is the exec mask, and the wave descends while any lane does.
+// THE BEST of a lane (return, length, done, the path's digits at 3 bits a level, the leaf record) is replaced only on a STRICTLY greater return: the walk
+// visits the leaves -- a done step, or level depth - 1 -- in lexicographic order of their taken prefixes, so what stays is the smallest maximiser, and its
+// digits behind its end are 0 because nothing was ever or-ed in there.
+// PRUNING, exact: a step pays max_steps and ends the plan, or -1.  Below a node with return r no leaf returns more than r + max_steps, so a lane whose best
+// is already that much does not descend; nothing strictly greater is lost, and ties never replace.
+#define CW_PLAN_MAX_DEPTH 8
+struct CwPlanBest {
+    int32_t ret;
+    uint32_t meta;           // length | done << 8
+    uint32_t digits;         // action of step t in bits 3t .. 3t + 2
+    uint4 h, pos;
+};
+
+template <int L>
+__device__ __forceinline__ void plan_level(const CwParams &P, const uint4 &ip, const uint4 h, const uint4 pos, const int32_t ret, const uint32_t digits,
+                                           const int a_lo, const int a_hi, const int depth, CwPlanBest &b)
+{
+#pragma unroll 1
+    for (int a = a_lo; a < a_hi; a++) {                                   // (uniform: a scalar counter)
+        uint4 h2 = h;
+        uint32_t sp[8];
+        unpack_pos(pos, sp);
+        const CwStepOut o = step_env(P, h2, sp, a, [&]() { return ip; });
+        const int32_t r2 = ret + o.reward;
+        const uint32_t d2 = digits | ((uint32_t)a << (3 * L));
+        const uint4 p2 = pack_pos(sp);
+        if (o.done || L + 1 >= depth) {                                   // a leaf
+            if (r2 > b.ret) {
+                b.ret = r2;
+                b.meta = (uint32_t)(L + 1) | (o.done ? 0x100u : 0u);
+                b.digits = d2;
+                b.h = h2;
+                b.pos = p2;
+            }
+        } else if constexpr (L + 1 < CW_PLAN_MAX_DEPTH) {
+            if (r2 + P.max_steps > b.ret) plan_level<L + 1>(P, ip, h2, p2, r2, d2, 0, 6, depth, b);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cw_plan_kernel(CwParams P, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                      const uint4 *__restrict__ pos_in, int n_states, int depth, CwPlanOut O)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
+    const int a0 = (int)blockIdx.y;
+    int env = -1;
+    bool skipped = false;
+    if (j < n_states) {
+        if (env_of) {
+            const int32_t v = env_of[j];
+            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
+            else skipped = v >= 0;
+        } else {
+            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
+        }
+    }
+    if (a0 == 0) {
+        const unsigned long long m_skip = CW_BALLOT(skipped);
+        if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
+    }
+    if (env < 0) return;
+    const uint4 h = hdr_in[j], pos = pos_in[j], ip = P.init_pos[env];
+    CwPlanBest b;
+    b.ret = INT32_MIN; b.meta = 0; b.digits = 0; b.h = h; b.pos = pos;
+    plan_level<0>(P, ip, h, pos, 0, 0u, a0, a0 + 1, depth, b);
+
+    const size_t M = (size_t)n_states;
+    const size_t row = (size_t)a0 * M + (size_t)j;
+    if (O.q) O.q[row] = b.ret;
+    if (O.length) O.length[row] = (int32_t)(b.meta & 0xFFu);
+    if (O.done) O.done[row] = (uint8_t)(b.meta >> 8);
+    if (O.achieved) O.achieved[row] = (uint16_t)(b.h.y & 0xFFFFu);
+    if (O.hdr) O.hdr[row] = b.h;
+    if (O.pos) O.pos[row] = b.pos;
+    if (O.plan) {
+        uint8_t *const pl = O.plan + (size_t)a0 * (size_t)depth * M + (size_t)j;
+        for (int t = 0; t < depth; t++) pl[(size_t)t * M] = (uint8_t)((b.digits >> (3 * t)) & 7u);
+    }
+}
+
 // ------------------------------------------------------------------------------------ reset
-// One WAVEFRONT per finished env.  reset() is an inherently serial walk down the env's MT19937
+// One WAVEFRONT per finished env. reset() is an inherently serial walk down the env's MT19937
 // stream (a rejection-sampled Fisher-Yates of S*S cells, then imagine_obs), so a lane-per-env
 // kernel leaves every global-memory latency of that stream on the critical path -- measured 127 us
 // per reset alone and 350 us beside the render kernel's HBM traffic.  Here the wave stages the
@@ -2595,6 +2687,14 @@ hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const 
     const int epb = cw_masked_launch(P, T, &blocks);
     if (obs_mode != 0) hipLaunchKernelGGL(cw_snapshot_load_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
     else hipLaunchKernelGGL(cw_snapshot_load_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
+    return hipGetLastError();
+}
+
+// cw_plan: one launch, grid = (ceil(n_states / 256), 6 first actions)
+hipError_t cwk_launch_plan(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, int depth, const CwPlanOut *O,
+                           hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_plan_kernel, dim3((unsigned)((n_states + 255) / 256), 6u), dim3(256), 0, st, *P, env_of, hdr_in, pos_in, n_states, depth, *O);
     return hipGetLastError();
 }
 

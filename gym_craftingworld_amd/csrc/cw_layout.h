@@ -114,6 +114,18 @@ struct CwSimulateOut {
     uint8_t *dones;          // [T][M]
 };
 
+// Where cw_plan_kernel leaves the best plan of each (first action, state) pair (the public cw_plan_out with the records typed): ACTION-MAJOR like CwExpandOut,
+// row a * M + j.  A null field is not written.
+struct CwPlanOut {
+    int32_t *q;              // [6][M] the best return within the horizon after first action a
+    int32_t *length;         // [6][M] steps the best plan takes
+    uint8_t *done;           // [6][M] it ends inside the horizon
+    uint16_t *achieved;      // [6][M]
+    uint4 *hdr;              // [6][M] record after its last step
+    uint4 *pos;              // [6][M]
+    uint8_t *plan;           // [6][D][M] its actions, step-major; 0 behind its end
+};
+
 // Everything the kernels need, passed by value.
 struct CwParams {
     // per-env state (SoA of 16-byte records unless noted)
@@ -159,8 +171,8 @@ struct CwParams {
     unsigned long long *counters; // [4] public: steps, finished, successes, invalid actions; [4] PRIVATE: the finished count the last sweep of the
                                   // observation array saw (cw_render_pieces_kernel: what kind of step does it follow?), [5] PRIVATE: resets of
                                   // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot save / load
-                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); [7] public: states cw_expand_kernel
-                                  // or cw_simulate_kernel skipped for an env index at or above n_envs; 8 words allocated
+                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); [7] public: states cw_expand_kernel,
+                                  // cw_simulate_kernel or cw_plan_kernel skipped for an env index at or above n_envs; 8 words allocated
     const CwMenuDev *menus;
     // constants
     int32_t n_envs;

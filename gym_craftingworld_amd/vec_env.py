@@ -272,6 +272,30 @@ def simulate_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of):
     return _simulate_tm(num_envs, shape, dtype, None if hdr is None else m)
 
 
+PLAN_FIELDS = ('q', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'best_action', 'best_q')
+PLAN_MAX_DEPTH, PLAN_MAX_LEAVES = 8, 2 ** 32
+
+
+def _plan_depth(depth, m):
+    """plan_args on the depth and the number of states: -> D"""
+    if isinstance(depth, (bool, np.bool_)) or not isinstance(depth, (int, np.integer)):
+        raise ValueError('depth must be an integer 1 .. %d, got %r' % (PLAN_MAX_DEPTH, depth))
+    depth = int(depth)
+    if not 1 <= depth <= PLAN_MAX_DEPTH:
+        raise ValueError('depth = %d: 1 .. %d in one call' % (depth, PLAN_MAX_DEPTH))
+    if m * 6 ** depth > PLAN_MAX_LEAVES:
+        raise ValueError('%d states at depth %d are %d plans: at most 2**32 in one call' % (m, depth, m * 6 ** depth))
+    return depth
+
+
+def plan_args(num_envs, depth, hdr, slot_pos, env_of):
+    """What cw_plan is handed, validated on the host: -> (D, M).  depth: an integer 1 .. 8 with M * 6**depth <= 2**32 (65 536 states at depth 6, 2 048 at
+    depth 8); hdr / slot_pos / env_of: numpy inputs under expand_args' rules (both records or neither, env_of only with them, IndexError for an entry
+    >= num_envs).  ValueError for everything else."""
+    m = expand_args(num_envs, hdr, slot_pos, env_of)
+    return _plan_depth(depth, m), m
+
+
 def _render_records_m(frame_shape, lead, mask, out):
     """render_records_args on the records' leading shape and the (shape, numpy dtype) of mask and out (None: not given)"""
     lead, frame_shape = tuple(int(x) for x in lead), tuple(int(x) for x in frame_shape)
@@ -821,6 +845,49 @@ class CraftingWorldVecEnv:
         if m:
             self._call('cw_simulate', env_of, hdr, slot_pos, m, actions, T, 1 if stop_at_done else 0, C.byref(_out_struct(L.cw_simulate_out, out)), keep=out)
         return out
+
+    # ------------------------------------------------------------------ searching every plan
+    def plan(self, depth, hdr=None, slot_pos=None, env_of=None, *, fields=None, out=None):
+        """What is the best that can be done from here within `depth` steps, and which action starts it?  (cw_plan: ONE kernel that walks all 6**depth
+        action strings of every state depth-first with its stack in registers -- shared prefixes are stepped once, a plan stops at its first done step;
+        no host round trip, capturable; no env is touched.)  depth: 1 .. 8, with M * 6**depth <= 2**32.  The states are expand()'s: without records the
+        envs' current ones (M = num_envs), else hdr [..., 16] / slot_pos [..., 8] / env_of under expand()'s rules (env j % num_envs or env_of[j], a
+        negative entry takes no part and none of its rows is written, an entry >= num_envs handed over on the device is skipped and counted in
+        expand_skipped).  -> a dict of device tensors, ACTION-MAJOR: entry [a, j] belongs to the plans of state j that begin with action a.
+        'q' int32 [6, M]: the largest return simulate(stop_at_done=True) gives any of them; the BEST PLAN is the lexicographically smallest one that
+        reaches it, zeros behind its end.  'length' int32 [6, M], 'done' bool [6, M], 'achieved_mask' [6, M], 'hdr' uint8 [6, M, 16] and 'slot_pos'
+        int16 [6, M, 8]: what simulate() returns for the best plan; 'plan' uint8 [6, depth, M]: the plan itself, plan[a] step-major as simulate() takes
+        its actions, plan[a, 0] == a.  'best_q' int32 [M]: the maximum of q over a, and 'best_action' uint8 [M]: the SMALLEST a that reaches it -- both
+        derived from q on the device, on the env's stream, without synchronisation (of a state that takes no part they are computed from unwritten rows).
+        fields: a subset of PLAN_FIELDS (default: all but 'hdr' and 'slot_pos').  out: a dict returned by an earlier call with the same depth, M and
+        fields, written again."""
+        names = _field_names(fields, PLAN_FIELDS, tuple(f for f in PLAN_FIELDS if f not in ('hdr', 'slot_pos')))
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        depth = _plan_depth(depth, m)
+        spec = {'q': ((6, m), torch.int32), 'length': ((6, m), torch.int32), 'done': ((6, m), torch.bool), 'achieved_mask': ((6, m), self.achieved_mask.dtype),
+                'hdr': ((6, m, 16), torch.uint8), 'slot_pos': ((6, m, 8), self.slot_pos.dtype), 'plan': ((6, depth, m), torch.uint8),
+                'best_action': ((m,), torch.uint8), 'best_q': ((m,), torch.int32)}
+        out = self._out_dict(out, names, spec)
+        derived = [f for f in ('best_action', 'best_q') if f in out]
+        kernel = {f: t for f, t in out.items() if f not in derived}
+        if derived and 'q' not in kernel:
+            kernel['q'] = torch.empty((6, m), dtype=torch.int32, device=self.device)        # (scratch: the caller did not ask for q itself)
+        if m:
+            self._call('cw_plan', env_of, hdr, slot_pos, m, depth, C.byref(_out_struct(L.cw_plan_out, kernel)), keep=kernel)
+        if derived:
+            q = kernel['q']
+            best = out['best_q'] if 'best_q' in out else torch.empty((m,), dtype=torch.int32, device=self.device)
+            torch.amax(q, dim=0, out=best)
+            if 'best_action' in out:                                                        # the smallest a with q[a] == best: no argmax, whose ties are not pinned
+                first = torch.where(q == best, self._plan_action_ids(), 6)
+                torch.amin(first, dim=0, out=out['best_action'])
+        return out
+
+    def _plan_action_ids(self):
+        ids = getattr(self, '_plan_ids', None)
+        if ids is None:
+            ids = self._plan_ids = torch.arange(6, dtype=torch.uint8, device=self.device).reshape(6, 1)
+        return ids
 
     def one_hot_states(self, hdr, slot_pos, out=None):
         """obs_one_hot (ray.py:119) of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() takes and returns them):

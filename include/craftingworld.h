@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -127,7 +127,7 @@ typedef struct cw_buffer_table {
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
                               *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
-                              *      for a bad row number, [7] counts the states skipped by cw_expand or cw_simulate for an env index at or above num_envs.
+                              *      for a bad row number, [7] counts the states skipped by cw_expand, cw_simulate or cw_plan for an env index at or above num_envs.
                               *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
@@ -358,6 +358,38 @@ typedef struct cw_simulate_out {  /* DEVICE pointers (host_outputs engines: or G
 int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states,
                 const uint8_t *actions /* DEVICE uint8 [n_steps][n_states] */, int32_t n_steps, int32_t stop_at_done,
                 const cw_simulate_out *out, cw_stream_t stream);
+
+/* --- searching every plan: the best that can be done from a state within D steps, and which action starts it (the exhaustive receding-horizon controller:
+ * an expert for imitation, an optimal-within-horizon baseline, an exact ranking of the six actions, the "goal reachable within D steps" label).
+ * M = n_states, D = depth.  For input state j and first action a in 0..5 take every action string p in {0..5}^D with p[0] = a, and let R(p) be cw_simulate's
+ * `ret` for that state with n_steps = D and stop_at_done = 1.  q[a][j] = max R(p).  The BEST PLAN p* is the lexicographically smallest maximiser in canonical
+ * form: its entries at t >= length are 0 (those steps are never taken: all strings that share the taken prefix tie, and the smallest of them ends in zeros) --
+ * the first strict maximum of a depth-first pre-order walk that does not descend below a done step.  length, done, achieved, hdr and slot_pos are what
+ * cw_simulate returns for p*, hdr and slot_pos byte for byte. */
+typedef struct cw_plan_out {   /* DEVICE pointers (host_outputs engines: or GPU-mapped host memory); NULL = not written; all NULL: CW_ERR_INVALID; ACTION-MAJOR like cw_expand_out */
+    int32_t  *q;         /* [6][M]      the best return within D steps after first action a                            */
+    int32_t  *length;    /* [6][M]      steps p* takes: 1 + its done step, D if it has none                            */
+    uint8_t  *done;      /* [6][M]      p* ends inside the horizon                                                     */
+    uint16_t *achieved;  /* [6][M]      achieved mask after p*'s last step                                             */
+    uint8_t  *hdr;       /* [6][M][16]  record after p*'s last step; 16-byte aligned                                   */
+    uint16_t *slot_pos;  /* [6][M][8]   16-byte aligned                                                                */
+    uint8_t  *plan;      /* [6][D][M]   p*; plan[a] is step-major: it feeds cw_simulate's `actions` as it is; plan[a][0][j] == a */
+} cw_plan_out;
+/* The inputs follow cw_expand's rules.  hdr_in == NULL: the engine's CURRENT states, n_states == num_envs, slot_pos_in and env_of NULL.  Otherwise n_states
+ *   records of the caller's (hdr_in [M][16], slot_pos_in [M][8], both required, 16-byte aligned, only read); the env of state j is j % num_envs, or
+ *   env_of[j] (DEVICE int32 [M]): a negative entry takes no part and NO row of it is written; an entry >= num_envs is SKIPPED: no row is written either and
+ *   counters[7] is incremented once.  No entry becomes an address without that check.
+ * 1 <= depth <= 8, and n_states * 6^depth <= 2^32: one launch on a shared card must stay short (65 536 states at depth 6, 2 048 at depth 8).
+ * PURE: nothing of the engine is written except counters[7]; nothing is drawn from any RNG stream.
+ * Enqueues ONE kernel (cw_plan_kernel: one lane per (first action, state) pair, a depth-first search whose stack is in registers and whose action is uniform
+ *   across a wave at every level; no memory access inside the search) on `stream` -- no host synchronisation, no allocation -- and can be captured into a HIP
+ *   graph with cw_step / cw_expand / cw_simulate.  Every obs_mode, with and without auto_reset, host_outputs engines included.  n_states == 0 (with hdr_in):
+ *   CW_OK, nothing enqueued.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID: a null engine or out, all seven fields NULL,
+ *   n_states < 0 or above 2^27, depth < 1 or above 8, n_states * 6^depth above 2^32, hdr_in without slot_pos_in or the reverse, env_of without hdr_in,
+ *   n_states != num_envs without hdr_in, a misaligned hdr_in / slot_pos_in / out->hdr / out->slot_pos.
+ *   (21x21, launch included: 65 536 envs 23 us at depth 1, 1.08 ms at 4, 5.9 ms at 5, 33.5 ms at 6 with no goal in reach -- the whole tree; the enumeration through cw_simulate: 311 us / 2.47 ms at depths 1 / 4, over its cap from 5 on: tools/measure_plan.py, profiles/r10_plan.txt.) */
+int cw_plan(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t depth,
+            const cw_plan_out *out, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
