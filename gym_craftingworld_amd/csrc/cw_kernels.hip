@@ -68,6 +68,13 @@ __device__ __forceinline__ uint4 pack_pos(const uint32_t sp[8])
 {
     return make_uint4(sp[0] | (sp[1] << 16), sp[2] | (sp[3] << 16), sp[4] | (sp[5] << 16), sp[6] | (sp[7] << 16));
 }
+// a 16-byte record that every lane of the wave has loaded from the same address, as wave-uniform words (SGPRs) / as its eight uniform slots
+__device__ __forceinline__ uint4 uniform4(const uint4 &v)
+{
+    return make_uint4(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y), __builtin_amdgcn_readfirstlane(v.z),
+                      __builtin_amdgcn_readfirstlane(v.w));
+}
+__device__ __forceinline__ void unpack_uniform(const uint4 &v, uint32_t sp[8]) { unpack_pos(uniform4(v), sp); }
 // slot index whose object sits in `cell`, or -1 (at most one object per cell, ray.py:334)
 __device__ __forceinline__ int slot_at(const uint32_t sp[8], uint32_t cell)
 {
@@ -112,6 +119,15 @@ __device__ __forceinline__ u32x3 overlay_dwords(u32x3 d, uint32_t o)
     d.y = (o >> 8) | (o << 16);
     d.z = (d.z & 0xFFFFFF00u) | (o >> 16);
     return d;
+}
+// the channel bits of one cell of the one-hot view: 0-7 the object `code` (0: none), at the agent's cell 8 and, while it holds something, 8 + hold.
+// kRecords: `hold` is a byte of a CALLER's record and can be anything: the shift is taken modulo 32 (an engine's own hold is 0..3)
+template <bool kRecords = false>
+__device__ __forceinline__ uint32_t onehot_bits(uint32_t code, bool at_agent, uint32_t hold)
+{
+    uint32_t bits = code ? (1u << (code - 1)) : 0u;
+    if (at_agent) bits |= (1u << 8) | (hold ? (1u << (kRecords ? (8 + hold) & 31u : 8 + hold)) : 0u);
+    return bits;
 }
 // one cell of the one-hot view (ray.py:94-98): channel bits 0..11 as 12 bytes of 0/1
 __device__ __forceinline__ u32x3 onehot_dwords(uint32_t bits)
@@ -335,8 +351,7 @@ __device__ __forceinline__ void load_state_uniform(const CwParams &P, int env, i
         v_c = P.goal_codes[env];
         v_a = P.goal_agent[env];
     }
-    unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(v_p.x), __builtin_amdgcn_readfirstlane(v_p.y), __builtin_amdgcn_readfirstlane(v_p.z),
-                          __builtin_amdgcn_readfirstlane(v_p.w)), sp);
+    unpack_uniform(v_p, sp);
     codes = __builtin_amdgcn_readfirstlane(v_c);
     agent_cell = __builtin_amdgcn_readfirstlane(v_a);
     hold = __builtin_amdgcn_readfirstlane(v_h);
@@ -605,16 +620,39 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwParams P, const void *ac
     }
 }
 
+// ------------------------------------------------------------------------------------ the caller's states
+// The prologue of the pure kernels (cw_expand_kernel, cw_simulate_kernel, cw_plan_kernel), one lane per state j of n_states: the env the state belongs to
+// (it supplies init_pos), or a negative value when the state takes no part -- such a lane returns at once and writes no row.  env_of == null: env j % n_envs;
+// else env_of[j] -- negative: no part; an index only behind cwh_expand_env_ok, else the state is SKIPPED and, where `count` is set, counted in counters[7],
+// once a wave by ballot (`count` is wave-uniform, and every lane of the wave calls this: kernels whose grid visits a state several times, one wave per first
+// action, set it in the action-0 waves only).  The records themselves are only ever compared, never used as addresses.
+__device__ __forceinline__ int state_env(const CwParams &P, const int32_t *__restrict__ env_of, int j, int n_states, bool count)
+{
+    int env = -1;
+    bool skipped = false;
+    if (j < n_states) {
+        if (env_of) {
+            const int32_t v = env_of[j];
+            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
+            else skipped = v >= 0;
+        } else {
+            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
+        }
+    }
+    if (count) {
+        const unsigned long long m_skip = CW_BALLOT(skipped);
+        if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
+    }
+    return env;
+}
+
 // ------------------------------------------------------------------------------------ expand
 // cw_expand: step_env as the pure function it is -- the successors of ALL SIX actions of n_states states, with no env touched.  One lane per (action, state)
 // pair: blockIdx.y is the action, the lanes of a wave are 64 consecutive states.  The action is therefore uniform across a wave, and handed to step_env as a
 // LITERAL (expand_one<A> behind a uniform switch): every `a == ...` of step_env is folded away, where the step kernels -- each lane with an action of its
 // own -- run both sides.  Loads: hdr, pos and (while something is held) init_pos[env], 16 bytes a lane each; with env_of == null and n_states <= n_envs all
 // three are one contiguous KiB per wave, and the six action waves of a state re-read the same lines from L2.  Stores: the outputs are action-major, row
-// a * n_states + j, so every store of a wave is one contiguous run.  No LDS.
-// Which env a record belongs to (it supplies init_pos): env_of == null: j % n_envs; else env_of[j] -- negative: the state takes no part; an index only behind
-// cwh_expand_env_ok, else the state is skipped and counted in counters[7], once a wave by ballot and by the action-0 waves only.  Rows of states that take
-// no part or are skipped are not written.  The records themselves are only ever compared, never used as addresses.
+// a * n_states + j, so every store of a wave is one contiguous run.  No LDS.  The env of a state: state_env, counted by the action-0 waves.
 template <int A>
 __device__ __forceinline__ void expand_one(const CwParams &P, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int j, int env, size_t row,
                                            const CwExpandOut &O)
@@ -636,21 +674,7 @@ __global__ __launch_bounds__(256) void cw_expand_kernel(CwParams P, const int32_
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
     const int a = (int)blockIdx.y;
-    int env = -1;
-    bool skipped = false;
-    if (j < n_states) {
-        if (env_of) {
-            const int32_t v = env_of[j];
-            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
-            else skipped = v >= 0;
-        } else {
-            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
-        }
-    }
-    if (a == 0) {
-        const unsigned long long m_skip = CW_BALLOT(skipped);
-        if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
-    }
+    const int env = state_env(P, env_of, j, n_states, a == 0);
     if (env < 0) return;
     const size_t row = (size_t)a * (size_t)n_states + (size_t)j;
     switch (a) {
@@ -669,8 +693,7 @@ __global__ __launch_bounds__(256) void cw_expand_kernel(CwParams P, const int32_
 // cw_rollout_kernel's register-resident loop.  One lane per state: its header, eight slots and its env's init_pos (one 16-byte load up front, not lazily
 // inside the loop) stay in registers for the whole call.  No LDS.  The actions differ per lane, so step_env runs both sides of its branches predicated, as
 // in the step kernels.  own != 0: the records are the engine's own, BROADCAST -- state j reads record j % n_envs; else the caller's record j of env
-// j % n_envs or env_of[j], an entry an index only behind cwh_expand_env_ok (cw_expand_kernel's rules: negative = no part, too large = skipped and counted
-// in counters[7] once a wave by ballot).  A state that takes no part writes no row, trace rows included.
+// j % n_envs or env_of[j] (state_env, every wave counting).  A state that takes no part writes no row, trace rows included.
 // The ACTION BYTES are the only loads inside the loop, and they do not depend on the state: they are fetched CW_SIM_BLOCK steps at a time, one block AHEAD
 // of the steps that use them -- the eight loads of block b + 1 (each one coalesced 64-byte run per wave in the step-major layout; the last block's clamped
 // to row T - 1) are issued after block b's bytes have been packed into two registers and before block b's first step, so only the very first block's
@@ -686,19 +709,7 @@ __global__ __launch_bounds__(256) void cw_simulate_kernel(CwParams P, const int3
                                                           int T, int stop_at_done, CwSimulateOut O)
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
-    int env = -1;
-    bool skipped = false;
-    if (j < n_states) {
-        if (env_of) {
-            const int32_t v = env_of[j];
-            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
-            else skipped = v >= 0;
-        } else {
-            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
-        }
-    }
-    const unsigned long long m_skip = CW_BALLOT(skipped);
-    if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
+    const int env = state_env(P, env_of, j, n_states, true);
     if (env < 0) return;
     const size_t M = (size_t)n_states;
     const int src = own ? env : j;
@@ -755,7 +766,7 @@ __global__ __launch_bounds__(256) void cw_simulate_kernel(CwParams P, const int3
 
 // ------------------------------------------------------------------------------------ plan
 // cw_plan: the best return within D steps after each first action, by exhaustive depth-first search -- cw_expand_kernel's launch shape and input handling
-// (one lane per (first action, state) pair, blockIdx.y the first action, the same env_of rules and counters[7] by the action-0 waves), cw_simulate_kernel's
+// (one lane per (first action, state) pair, blockIdx.y the first action, state_env counted by the action-0 waves), cw_simulate_kernel's
 // semantics for every plan (stop_at_done).  The three 16-byte loads happen once, up front; the search touches no memory and no LDS.
 // THE STACK IS IN NAMED REGISTERS: plan_level<L> is inlined into plan_level<L - 1>, each level's saved record (header, packed slots, return so far) being
 // its own by-value parameters -- no array is indexed by a run-time value, so nothing goes to scratch.  CW_PLAN_MAX_DEPTH levels are built; `depth` is
@@ -808,21 +819,7 @@ __global__ __launch_bounds__(256) void cw_plan_kernel(CwParams P, const int32_t 
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // (n_states <= 2^27)
     const int a0 = (int)blockIdx.y;
-    int env = -1;
-    bool skipped = false;
-    if (j < n_states) {
-        if (env_of) {
-            const int32_t v = env_of[j];
-            if (cwh_expand_env_ok(v, P.n_envs)) env = v;                  // (the ONLY way an entry becomes an index)
-            else skipped = v >= 0;
-        } else {
-            env = j < P.n_envs ? j : (int)((uint32_t)j % (uint32_t)P.n_envs);
-        }
-    }
-    if (a0 == 0) {
-        const unsigned long long m_skip = CW_BALLOT(skipped);
-        if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
-    }
+    const int env = state_env(P, env_of, j, n_states, a0 == 0);
     if (env < 0) return;
     const uint4 h = hdr_in[j], pos = pos_in[j], ip = P.init_pos[env];
     CwPlanBest b;
@@ -1151,6 +1148,17 @@ __device__ __forceinline__ void store_next_record(const CwParams &P, int env, in
     P.nx_goal_pos[at] = r.goal_pos;
     P.nx_misc[at] = make_uint4(r.init_agent | (r.goal_agent << 16), r.goal_codes, r.desired | (r.subset << 16) | 0x80000000u, r.draws);      // (VALID)
 }
+// The four stores that make a header and slots an env's state as callers see it: the records, and the mask outputs that describe them (a new episode has
+// achieved nothing: its h.y is desired << 16; an auto-reset leaves the outputs at the finished step's values instead).  One lane.  cw_reset_kernel and
+// cw_snapshot_load_kernel; cw_reset_masked_kernel writes the same four out itself (with this function its code moved, see deal_envs).
+__device__ __forceinline__ void store_env_state(const CwParams &P, int env, const uint4 &h, const uint4 &pos)
+{
+    P.pos[env] = pos;
+    P.hdr[env] = h;
+    P.achieved_out[env] = (uint16_t)(h.y & 0xFFFFu);
+    P.desired_out[env] = (uint16_t)(h.y >> 16);
+}
+
 // reset() of EVERY env (cw_reset, ray.py:156-218), one wavefront per env: a waiting look-ahead record is taken over, any other env is
 // reset here from its stream.  (cw_reset then sweeps the three frame arrays and refills the records.)
 __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_kernel(CwParams P)
@@ -1169,20 +1177,14 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_kernel(CwPar
                 uint4 h = v_h;
                 uint32_t sp[8];
                 pop_next_episode(P, env, ctl, h, sp, count_episode);      // (not listed: cw_reset tops every env's ring up right after this kernel)
-                P.pos[env] = pack_pos(sp);
-                P.hdr[env] = h;
-                P.achieved_out[env] = 0;                              // the mask outputs describe the new episode
-                P.desired_out[env] = (uint16_t)(h.y >> 16);           // (an auto-reset leaves them at the finished step's values)
+                store_env_state(P, env, h, pack_pos(sp));
             }
             continue;
         }
         const CwResetOut r = reset_env_wave(P, env, [&]() { return menu_id; }, s_mt[wave_in_block], lane);
         if (lane == 0) {
             store_episode_records(P, env, r, count_episode);
-            P.pos[env] = r.init_pos;
-            P.hdr[env] = reset_header(P, r, menu_id);
-            P.achieved_out[env] = 0;
-            P.desired_out[env] = (uint16_t)r.desired;
+            store_env_state(P, env, reset_header(P, r, menu_id), r.init_pos);
         }
     }
 }
@@ -1234,10 +1236,8 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_reset_masked_kerne
                 }
                 if constexpr (PAINT) {                                    // lane 0's record for the whole wave
                     const uint4 p0 = pack_pos(sp);
-                    ipos = make_uint4(__builtin_amdgcn_readfirstlane(p0.x), __builtin_amdgcn_readfirstlane(p0.y), __builtin_amdgcn_readfirstlane(p0.z),
-                                      __builtin_amdgcn_readfirstlane(p0.w));
-                    gpos = make_uint4(__builtin_amdgcn_readfirstlane(goal.pos.x), __builtin_amdgcn_readfirstlane(goal.pos.y),
-                                      __builtin_amdgcn_readfirstlane(goal.pos.z), __builtin_amdgcn_readfirstlane(goal.pos.w));
+                    ipos = uniform4(p0);
+                    gpos = uniform4(goal.pos);
                     iagent = agent_cell_of(P, __builtin_amdgcn_readfirstlane(h.x));
                     gagent = __builtin_amdgcn_readfirstlane(goal.agent);
                     gcodes = __builtin_amdgcn_readfirstlane(goal.codes);
@@ -1306,8 +1306,7 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_imagine_masked_ker
             const uint32_t des = __builtin_amdgcn_readfirstlane(v_des) & P.task_mask;
             const uint32_t cur_agent = agent_cell_of(P, __builtin_amdgcn_readfirstlane(v_h.x));
             uint32_t ip[8];
-            unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(v_ip.x), __builtin_amdgcn_readfirstlane(v_ip.y), __builtin_amdgcn_readfirstlane(v_ip.z),
-                                  __builtin_amdgcn_readfirstlane(v_ip.w)), ip);
+            unpack_uniform(v_ip, ip);
             uint32_t v_fp = (uint32_t)CW_POS_GONE;                        // the start state: one of each object, lane = slot
 #pragma unroll
             for (int k = 0; k < 8; k++) v_fp = (lane == k) ? ip[k] : v_fp;
@@ -1340,7 +1339,7 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_imagine_masked_ker
                 for (uint32_t cell = (uint32_t)lane; cell < (uint32_t)P.ncell; cell += CW_WAVE) {
                     const uint32_t code = code_of(gcodes, slot_at(jp, cell));
                     uint32_t bits = code ? (1u << (code - 1)) : 0u;
-                    if (cell == gagent) bits |= 1u << 8;                  // a goal state never holds an item
+                    if (cell == gagent) bits |= 1u << 8;                  // a goal state never holds an item (onehot_bits moved this kernel's code)
                     *(u32x3_a4 *)(oh + (size_t)cell * 12u) = onehot_dwords(bits);
                 }
             }
@@ -1348,40 +1347,58 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_imagine_masked_ker
     }
 }
 
-// sample_state() (ray.py:599-628; pooled: generate_fixed_initial_state(), :630-644) of the envs the caller selects, from each env's stream: the nine
-// cells (objects 0..7, agent) to out_cells[env][9], the format of cw_get_fixed_states.  Nothing else of the env is touched.  Envs are dealt out as in
-// cw_reset_masked_kernel; mask == NULL selects every env.
-__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_sample_state_masked_kernel(CwParams P, const uint8_t *__restrict__ mask, int pooled,
-                                                                                           uint16_t *__restrict__ out_cells, int epb)
+// ------------------------------------------------------------------------------------ the dealer
+// THE DEALER of cw_reset_masked_kernel (above), written once for cw_sample_state_masked_kernel and the two snapshot kernels: a workgroup scans `epb`
+// consecutive envs per round, grid-stride over the chunks; all four waves evaluate the same selection, one env per lane, and hold the same ballot: the
+// selected env of rank k goes to wave k mod 4.
+// cw_reset_masked_kernel and cw_imagine_masked_kernel KEEP THEIR OWN COPY of this loop: as bodies of deal_envs their code moved, and the calls that paint
+// 65 536 envs' frames then left the band of the parent build's own run-to-run spread in two of two timing sessions (profiles/r11_kernel_frames.txt); as they
+// stand their instruction streams are the parent's.
+//   pick(mine, in_chunk, wave_in_block, lane) -> the lane's TICKET for env `mine`, negative: not selected.  Called by every lane of every wave; in_chunk says
+//       that `mine` is an env of this round -- nothing may be read at `mine` without it.  Whatever is counted once a chunk is counted by wave 0.
+//   body(env, ticket, wave_in_block, lane)    the work on one selected env, by the whole wave it was dealt to; `ticket` is that env's, wave-uniform.
+// lane and wave_in_block reach both BY VALUE, as arguments: how `lane` reaches the inline functions they share with the step kernels (CwMtWave,
+// copy_stream_group) decides how those are optimised in EVERY kernel, and a reference captured by a lambda changed the step and rollout kernels' code.
+template <typename PickFn, typename BodyFn>
+__device__ __forceinline__ void deal_envs(const CwParams &P, int epb, PickFn pick, BodyFn body)
 {
-    __shared__ uint32_t s_mt[CW_RESET_WAVES][CW_MT_WORDS];
     const int lane = threadIdx.x & (CW_WAVE - 1);
     const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
     for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
         const int mine = base + lane;
         const bool in_chunk = lane < epb && mine < P.n_envs;
-        const uint32_t v_sel = in_chunk ? (mask ? (uint32_t)mask[mine] : 1u) : 0u;
-        unsigned long long m = CW_BALLOT(v_sel != 0u);
+        const int32_t v_ticket = pick(mine, in_chunk, wave_in_block, lane);
+        unsigned long long m = CW_BALLOT(v_ticket >= 0);
         for (int rank = 0; m; rank++) {
             const int l = __builtin_ctzll(m);
             m &= m - 1;
             if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
-            const int env = base + l;
-            CwMtWave mt;
-            mt.load(s_mt[wave_in_block], P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
-            const uint32_t v_tok = place_env_wave(P, env, mt, pooled != 0, lane);
-            mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
-            if (lane < 9) out_cells[(size_t)env * 9 + lane] = (uint16_t)v_tok;
+            body(base + l, (int32_t)__builtin_amdgcn_readlane(v_ticket, l), wave_in_block, lane);
         }
     }
 }
 
+// sample_state() (ray.py:599-628; pooled: generate_fixed_initial_state(), :630-644) of the envs the caller selects, from each env's stream: the nine
+// cells (objects 0..7, agent) to out_cells[env][9], the format of cw_get_fixed_states.  Nothing else of the env is touched.  Dealt out by deal_envs;
+// mask == NULL selects every env.
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_sample_state_masked_kernel(CwParams P, const uint8_t *__restrict__ mask, int pooled,
+                                                                                           uint16_t *__restrict__ out_cells, int epb)
+{
+    __shared__ uint32_t s_mt[CW_RESET_WAVES][CW_MT_WORDS];
+    deal_envs(P, epb, [&](int mine, bool in_chunk, int, int) { return (in_chunk && (!mask || mask[mine] != 0)) ? 0 : -1; },
+              [&](int env, int32_t, int wave_in_block, int lane) {
+        CwMtWave mt;
+        mt.load(s_mt[wave_in_block], P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+        const uint32_t v_tok = place_env_wave(P, env, mt, pooled != 0, lane);
+        mt.store(P.mt + (size_t)env * CW_MT_WORDS, P.mt_idx + env, lane);
+        if (lane < 9) out_cells[(size_t)env * 9 + lane] = (uint16_t)v_tok;
+    });
+}
+
 // ------------------------------------------------------------------------------------ snapshot bank
 // cw_snapshot_save / cw_snapshot_load: envs into rows of the engine's bank (CwBank, cw_layout.h) and rows back into envs, driven by a device array
-// rows[N] -- bank row rows[i] for env i, negative: env i takes no part.  Dealt out like the masked kernels: a workgroup ballots `epb` entries for "takes part
-// and passes the row check" (cwh_snapshot_row_ok: the ONLY way a row number becomes an index; on load also the row's valid byte, read behind that check),
-// rank k goes to wave k mod 4, a wave copies one env at a time, grid-stride over the chunks.  An env whose row number is >= 0 but fails the check is left
-// exactly as it is and counted in counters[6], once (by wave 0 of the workgroup that balloted it).  No LDS.
+// rows[N] -- bank row rows[i] for env i, negative: env i takes no part.  Dealt out by deal_envs, an env's ticket being its row number if it passes the row
+// check (snapshot_ticket), and a wave copies one env at a time.  No LDS.
 // An env is two groups.  The EPISODE: hdr, pos, init_pos, init_agent, goal_pos, goal_codes, goal_agent, ep_no -- uniform loads, lane 0 stores.  Its SOURCE OF
 // FUTURE EPISODES: the MT19937 words (156 uint4 per env: 2 496 B is a multiple of 16 on both sides) and index, on engines that keep look-ahead records the
 // whole ring verbatim (the stream in HBM stands ahead of the env's logical position by the waiting records: copied together they stay consistent, and
@@ -1424,40 +1441,44 @@ __device__ __forceinline__ void copy_stream_group(const CwParams &P, const CwBan
     for (int j = lane; j < pool_words; j += CW_WAVE) d.pool[di * pool_words + j] = s.pool[si * pool_words + j];
 }
 
+// deal_envs' pick of both bank kernels: env `mine`'s row number as its ticket if it takes part and passes cwh_snapshot_row_ok -- the ONLY way a row number
+// becomes an index -- and, where need_valid is set (load), the row has been saved since the last reserve: its valid byte, read behind that check.  An env
+// whose row number is >= 0 but fails is left exactly as it is and counted in counters[6], once: by wave 0 of the workgroup that balloted it.
+__device__ __forceinline__ int32_t snapshot_ticket(const CwParams &P, const CwBank &B, const int32_t *__restrict__ rows, bool need_valid, int mine,
+                                                   bool in_chunk, int wave_in_block, int lane)
+{
+    const int32_t v_row = in_chunk ? rows[mine] : -1;
+    bool v_ok = cwh_snapshot_row_ok(v_row, B.rows) != 0;
+    if (need_valid) {
+        uint32_t v_valid = 0u;
+        if (v_ok) v_valid = B.valid[v_row];                                       // (an address only behind the check)
+        v_ok = v_valid != 0u;
+    }
+    const unsigned long long skipped = CW_BALLOT(v_row >= 0 && !v_ok);
+    if (skipped && wave_in_block == 0 && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
+    return v_ok ? v_row : -1;
+}
+
 // bank row rows[i] <- env i.  Writes nothing of the engine (but counters[6] for a row number at or above the capacity).  Two envs that name the same row leave
 // an unspecified mix of the two there.  The row's valid byte is written after its data, by the same wave.
 __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_snapshot_save_kernel(CwParams P, CwBank B, const int32_t *__restrict__ rows, int epb)
 {
-    const int lane = threadIdx.x & (CW_WAVE - 1);
-    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
     const CwBank E = engine_as_bank(P);
-    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
-        const int mine = base + lane;
-        const bool in_chunk = lane < epb && mine < P.n_envs;
-        const int32_t v_row = in_chunk ? rows[mine] : -1;
-        const bool v_ok = cwh_snapshot_row_ok(v_row, B.rows) != 0;
-        unsigned long long m = CW_BALLOT(v_ok);
-        const unsigned long long skipped = CW_BALLOT(v_row >= 0 && !v_ok);
-        if (skipped && wave_in_block == 0 && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
-        for (int rank = 0; m; rank++) {
-            const int l = __builtin_ctzll(m);
-            m &= m - 1;
-            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
-            const int env = base + l;
-            const size_t row = (size_t)__builtin_amdgcn_readlane(v_row, l);       // (passed the check in lane l)
-            const uint4 h = P.hdr[env], ps = P.pos[env], ip = P.init_pos[env], gp = P.goal_pos[env];
-            const uint32_t gc = P.goal_codes[env];
-            const int32_t ep = P.ep_no[env];
-            const uint16_t ia = P.init_agent[env], ga = P.goal_agent[env];
-            copy_stream_group(P, B, row, E, (size_t)env, lane);
-            if (lane == 0) {
-                B.hdr[row] = h; B.pos[row] = ps; B.init_pos[row] = ip; B.goal_pos[row] = gp;
-                B.goal_codes[row] = gc; B.ep_no[row] = ep; B.init_agent[row] = ia; B.goal_agent[row] = ga;
-            }
-            __threadfence();                                                      // the row's data, then its valid byte
-            if (lane == 0) B.valid[row] = 1;
+    deal_envs(P, epb, [&](int mine, bool in_chunk, int wave_in_block, int lane) { return snapshot_ticket(P, B, rows, false, mine, in_chunk, wave_in_block, lane); },
+              [&](int env, int32_t ticket, int, int lane) {
+        const size_t row = (size_t)ticket;
+        const uint4 h = P.hdr[env], ps = P.pos[env], ip = P.init_pos[env], gp = P.goal_pos[env];
+        const uint32_t gc = P.goal_codes[env];
+        const int32_t ep = P.ep_no[env];
+        const uint16_t ia = P.init_agent[env], ga = P.goal_agent[env];
+        copy_stream_group(P, B, row, E, (size_t)env, lane);
+        if (lane == 0) {
+            B.hdr[row] = h; B.pos[row] = ps; B.init_pos[row] = ip; B.goal_pos[row] = gp;
+            B.goal_codes[row] = gc; B.ep_no[row] = ep; B.init_agent[row] = ia; B.goal_agent[row] = ga;
         }
-    }
+        __threadfence();                                                      // the row's data, then its valid byte
+        if (lane == 0) B.valid[row] = 1;
+    });
 }
 
 // env i <- bank row rows[i]; any number of envs may name the same row (the fork).  A row at or above the capacity, or one never saved since the last reserve,
@@ -1470,55 +1491,34 @@ template <bool PAINT>
 __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_snapshot_load_kernel(CwParams P, CwBank B, const int32_t *__restrict__ rows, int with_stream,
                                                                                      int epb)
 {
-    const int lane = threadIdx.x & (CW_WAVE - 1);
-    const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / CW_WAVE);
     const CwBank E = engine_as_bank(P);
-    for (int base = (int)blockIdx.x * epb; base < P.n_envs; base += (int)gridDim.x * epb) {
-        const int mine = base + lane;
-        const bool in_chunk = lane < epb && mine < P.n_envs;
-        const int32_t v_row = in_chunk ? rows[mine] : -1;
-        const bool v_in = cwh_snapshot_row_ok(v_row, B.rows) != 0;
-        uint32_t v_valid = 0u;
-        if (v_in) v_valid = B.valid[v_row];                                       // (an address only behind the check)
-        const bool v_ok = v_valid != 0u;
-        unsigned long long m = CW_BALLOT(v_ok);
-        const unsigned long long skipped = CW_BALLOT(v_row >= 0 && !v_ok);
-        if (skipped && wave_in_block == 0 && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
-        for (int rank = 0; m; rank++) {
-            const int l = __builtin_ctzll(m);
-            m &= m - 1;
-            if ((rank & (CW_RESET_WAVES - 1)) != wave_in_block) continue;
-            const int env = base + l;
-            const size_t row = (size_t)__builtin_amdgcn_readlane(v_row, l);       // (passed the check in lane l)
-            uint4 h = B.hdr[row];
-            const uint4 ps = B.pos[row], ip = B.init_pos[row], gp = B.goal_pos[row];
-            const uint32_t gc = B.goal_codes[row];
-            const int32_t ep = B.ep_no[row];
-            const uint32_t ia = B.init_agent[row], ga = B.goal_agent[row];
-            if (with_stream) copy_stream_group(P, E, (size_t)env, B, row, lane);
-            else h.x = (h.x & 0x00FFFFFFu) | (P.hdr[env].x & 0xFF000000u);        // (the env's own menu id)
-            if (lane == 0) {
-                P.hdr[env] = h; P.pos[env] = ps; P.init_pos[env] = ip; P.goal_pos[env] = gp;
-                P.goal_codes[env] = gc; P.ep_no[env] = ep; P.init_agent[env] = (uint16_t)ia; P.goal_agent[env] = (uint16_t)ga;
-                P.achieved_out[env] = (uint16_t)(h.y & 0xFFFFu);
-                P.desired_out[env] = (uint16_t)(h.y >> 16);
-            }
-            if constexpr (PAINT) {
-                const size_t off = (size_t)env * P.frame_bytes;
-                const uint32_t hx = __builtin_amdgcn_readfirstlane(h.x);
-                uint32_t jp[8];
-                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(ps.x), __builtin_amdgcn_readfirstlane(ps.y), __builtin_amdgcn_readfirstlane(ps.z),
-                                      __builtin_amdgcn_readfirstlane(ps.w)), jp);
-                paint_state_frame(P, P.obs + off, jp, __builtin_amdgcn_readfirstlane(h.w), agent_cell_of(P, hx), hold_of(hx), lane);
-                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(ip.x), __builtin_amdgcn_readfirstlane(ip.y), __builtin_amdgcn_readfirstlane(ip.z),
-                                      __builtin_amdgcn_readfirstlane(ip.w)), jp);
-                paint_state_frame(P, P.init_img + off, jp, CW_CODES_INITIAL, __builtin_amdgcn_readfirstlane(ia), 0u, lane);
-                unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(gp.x), __builtin_amdgcn_readfirstlane(gp.y), __builtin_amdgcn_readfirstlane(gp.z),
-                                      __builtin_amdgcn_readfirstlane(gp.w)), jp);
-                paint_state_frame(P, P.desired_img + off, jp, __builtin_amdgcn_readfirstlane(gc), __builtin_amdgcn_readfirstlane(ga), 0u, lane);
-            }
+    deal_envs(P, epb, [&](int mine, bool in_chunk, int wave_in_block, int lane) { return snapshot_ticket(P, B, rows, true, mine, in_chunk, wave_in_block, lane); },
+              [&](int env, int32_t ticket, int, int lane) {
+        const size_t row = (size_t)ticket;
+        uint4 h = B.hdr[row];
+        const uint4 ps = B.pos[row], ip = B.init_pos[row], gp = B.goal_pos[row];
+        const uint32_t gc = B.goal_codes[row];
+        const int32_t ep = B.ep_no[row];
+        const uint32_t ia = B.init_agent[row], ga = B.goal_agent[row];
+        if (with_stream) copy_stream_group(P, E, (size_t)env, B, row, lane);
+        else h.x = (h.x & 0x00FFFFFFu) | (P.hdr[env].x & 0xFF000000u);        // (the env's own menu id)
+        if (lane == 0) {
+            store_env_state(P, env, h, ps);
+            P.init_pos[env] = ip; P.goal_pos[env] = gp;
+            P.goal_codes[env] = gc; P.ep_no[env] = ep; P.init_agent[env] = (uint16_t)ia; P.goal_agent[env] = (uint16_t)ga;
         }
-    }
+        if constexpr (PAINT) {
+            const size_t off = (size_t)env * P.frame_bytes;
+            const uint32_t hx = __builtin_amdgcn_readfirstlane(h.x);
+            uint32_t jp[8];
+            unpack_uniform(ps, jp);
+            paint_state_frame(P, P.obs + off, jp, __builtin_amdgcn_readfirstlane(h.w), agent_cell_of(P, hx), hold_of(hx), lane);
+            unpack_uniform(ip, jp);
+            paint_state_frame(P, P.init_img + off, jp, CW_CODES_INITIAL, __builtin_amdgcn_readfirstlane(ia), 0u, lane);
+            unpack_uniform(gp, jp);
+            paint_state_frame(P, P.desired_img + off, jp, __builtin_amdgcn_readfirstlane(gc), __builtin_amdgcn_readfirstlane(ga), 0u, lane);
+        }
+    });
 }
 
 // LOOK-AHEAD refill: the next reset()s of every QUEUED env (all_envs: of every env with a free slot in its ring), run ahead of time from
@@ -1691,9 +1691,7 @@ __global__ __launch_bounds__(CW_WAVE) void cw_resident_kernel(CwParams P, CwResi
                 const uint32_t agent_cell = agent_cell_of(P, hx), hold = hold_of(hx);
                 for (int cell = lane; cell < P.ncell; cell += CW_WAVE) {
                     const uint32_t code = code_of(codes, slot_at(bp, (uint32_t)cell));
-                    uint32_t bits = code ? (1u << (code - 1)) : 0u;
-                    if ((uint32_t)cell == agent_cell) bits |= (1u << 8) | (hold ? (1u << (8 + hold)) : 0u);
-                    *(u32x3_a4 *)(P.res_onehot + 12 * cell) = onehot_dwords(bits);
+                    *(u32x3_a4 *)(P.res_onehot + 12 * cell) = onehot_dwords(onehot_bits(code, (uint32_t)cell == agent_cell, hold));
                 }
             }
             __threadfence_system();                                              // every lane's stores, then (lane 0) the answer
@@ -1845,8 +1843,7 @@ __device__ __forceinline__ void fused_step(const CwParams &P, const void *action
     for (int jq = wave_in_block; jq < n_jobs; jq += CW_RESET_WAVES) {
         const CwPaintJob &j = s_jobs[jq];
         uint32_t jp[8];
-        unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(j.pos.x), __builtin_amdgcn_readfirstlane(j.pos.y), __builtin_amdgcn_readfirstlane(j.pos.z),
-                              __builtin_amdgcn_readfirstlane(j.pos.w)), jp);
+        unpack_uniform(j.pos, jp);
         const uint32_t codes = __builtin_amdgcn_readfirstlane(j.codes), ahk = __builtin_amdgcn_readfirstlane(j.agent_hold_kind);
         const size_t off = (size_t)__builtin_amdgcn_readfirstlane(j.env) * P.frame_bytes;
         const uint32_t kind = ahk >> 24;
@@ -1923,8 +1920,7 @@ __global__ __launch_bounds__(256) void cw_render_records_kernel(CwParams P, cons
         if (mask && __builtin_amdgcn_readfirstlane((uint32_t)mask[j]) == 0u) continue;
         const uint4 v_h = hdr[j], v_p = pos[j];
         uint32_t sp[8];
-        unpack_pos(make_uint4(__builtin_amdgcn_readfirstlane(v_p.x), __builtin_amdgcn_readfirstlane(v_p.y), __builtin_amdgcn_readfirstlane(v_p.z),
-                              __builtin_amdgcn_readfirstlane(v_p.w)), sp);
+        unpack_uniform(v_p, sp);
         const uint32_t hx = __builtin_amdgcn_readfirstlane(v_h.x), codes = __builtin_amdgcn_readfirstlane(v_h.w);
         paint_state_frame<true>(P, out + (size_t)j * P.frame_bytes, sp, codes, agent_cell_of(P, hx), hold_of(hx), lane);
     }
@@ -2328,9 +2324,7 @@ __global__ __launch_bounds__(256) void cw_export_onehot_kernel(CwParams P, uint8
         const uint32_t code = code_of(codes, slot_at(sp, cell));
         const uint32_t agent_cell = which == 1 ? (uint32_t)P.goal_agent[env] : which == 2 ? (uint32_t)P.init_agent[env] : agent_cell_of(P, h.x);
         const uint32_t hold = which ? 0u : hold_of(h.x);
-        uint32_t bits = code ? (1u << (code - 1)) : 0u;
-        if (cell == agent_cell) bits |= (1u << 8) | (hold ? (1u << (8 + hold)) : 0u);
-        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(bits);
+        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(onehot_bits(code, cell == agent_cell, hold));
     }
 }
 
@@ -2348,10 +2342,7 @@ __global__ __launch_bounds__(256) void cw_export_onehot_states_kernel(CwParams P
         uint32_t sp[8];
         unpack_pos(pos[st], sp);
         const uint32_t code = code_of(h.w, slot_at(sp, cell));
-        const uint32_t hold = hold_of(h.x);
-        uint32_t bits = code ? (1u << (code - 1)) : 0u;
-        if (cell == agent_cell_of(P, h.x)) bits |= (1u << 8) | (hold ? (1u << ((8 + hold) & 31u)) : 0u);
-        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(bits);
+        *(u32x3_a4 *)(out + g * 12) = onehot_dwords(onehot_bits<true>(code, cell == agent_cell_of(P, h.x), hold_of(h.x)));
     }
 }
 
@@ -2563,7 +2554,15 @@ static void cw_launch_sweep(const CwParams &P, const CwTuning &tn, uint8_t *fram
 static inline int cw_wave_blocks(int waves) { return (waves + CW_RESET_WAVES - 1) / CW_RESET_WAVES; }
 // the shapes the CPU tests can call are cw_host.h's: the reset-shaped grid, the masked / snapshot kernels' (epb, workgroups), the envs per wave
 static inline int cw_reset_grid(const CwTuning &tn, int jobs) { return cwh_reset_grid(jobs, tn.n_cu, tn.reset_blocks_per_cu); }
-static inline int cw_masked_launch(const CwParams *P, const CwTuning *T, int *blocks) { return cwh_masked_launch(P->n_envs, T->n_cu, T->reset_blocks_per_cu, blocks); }
+// one launch of a dealt kernel (deal_envs) in the masked shape: `epb` envs per workgroup and round, as many workgroups as that takes; epb is the kernel's last argument
+template <typename Kernel, typename... Args>
+static inline hipError_t cw_launch_dealt(Kernel kernel, const CwParams *P, const CwTuning *T, hipStream_t st, Args... args)
+{
+    int blocks;
+    const int epb = cwh_masked_launch(P->n_envs, T->n_cu, T->reset_blocks_per_cu, &blocks);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, args..., epb);
+    return hipGetLastError();
+}
 // workgroups of 256 threads of the export kernels, one thread per cell of `total`, grid-stride above 32 workgroups per CU
 static inline int cw_export_grid(const CwTuning &tn, size_t total)
 {
@@ -2643,51 +2642,30 @@ hipError_t cwk_launch_reset_all(const CwParams *P, const CwTuning *T, int obs_mo
 // reset() of the envs with mask[i] != 0 (cw_reset_masked_kernel): one launch, nothing else, in the masked shape (cw_host.h: cwh_masked_launch)
 hipError_t cwk_launch_reset_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int obs_mode, hipStream_t st)
 {
-    int blocks;
-    const int epb = cw_masked_launch(P, T, &blocks);
-    if (obs_mode != 0) hipLaunchKernelGGL(cw_reset_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
-    else hipLaunchKernelGGL(cw_reset_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, epb);
-    return hipGetLastError();
+    return cw_launch_dealt(obs_mode != 0 ? cw_reset_masked_kernel<true> : cw_reset_masked_kernel<false>, P, T, st, mask);
 }
 
 // imagine_obs() / sample_state() of the envs with mask[i] != 0 (NULL: all): one launch each, in cwk_launch_reset_masked's shape
 hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, const uint16_t *desired, int commit, int obs_mode,
                                      uint8_t *out_frames, uint8_t *out_onehot, hipStream_t st)
 {
-    int blocks;
-    const int epb = cw_masked_launch(P, T, &blocks);
     const int paint_goal = obs_mode != 0;
-    if (out_frames || (commit && paint_goal))
-        hipLaunchKernelGGL(cw_imagine_masked_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, desired, commit, paint_goal,
-                           out_frames, out_onehot, epb);
-    else
-        hipLaunchKernelGGL(cw_imagine_masked_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, desired, commit, paint_goal,
-                           out_frames, out_onehot, epb);
-    return hipGetLastError();
+    return cw_launch_dealt((out_frames || (commit && paint_goal)) ? cw_imagine_masked_kernel<true> : cw_imagine_masked_kernel<false>, P, T, st, mask, desired,
+                           commit, paint_goal, out_frames, out_onehot);
 }
 hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st)
 {
-    int blocks;
-    const int epb = cw_masked_launch(P, T, &blocks);
-    hipLaunchKernelGGL(cw_sample_state_masked_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, mask, pooled, out_cells, epb);
-    return hipGetLastError();
+    return cw_launch_dealt(cw_sample_state_masked_kernel, P, T, st, mask, pooled, out_cells);
 }
 
 // snapshot save / load of the envs with rows[i] >= 0: one launch each, in the masked kernels' shape
 hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st)
 {
-    int blocks;
-    const int epb = cw_masked_launch(P, T, &blocks);
-    hipLaunchKernelGGL(cw_snapshot_save_kernel, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, epb);
-    return hipGetLastError();
+    return cw_launch_dealt(cw_snapshot_save_kernel, P, T, st, *B, rows);
 }
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st)
 {
-    int blocks;
-    const int epb = cw_masked_launch(P, T, &blocks);
-    if (obs_mode != 0) hipLaunchKernelGGL(cw_snapshot_load_kernel<true>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
-    else hipLaunchKernelGGL(cw_snapshot_load_kernel<false>, dim3(blocks), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, *B, rows, with_stream, epb);
-    return hipGetLastError();
+    return cw_launch_dealt(obs_mode != 0 ? cw_snapshot_load_kernel<true> : cw_snapshot_load_kernel<false>, P, T, st, *B, rows, with_stream);
 }
 
 // cw_plan: one launch, grid = (ceil(n_states / 256), 6 first actions)
