@@ -70,6 +70,11 @@ class cw_plan_out(C.Structure):
                 ('slot_pos', C.c_void_p), ('plan', C.c_void_p)]
 
 
+class cw_shoot_out(C.Structure):
+    _fields_ = [('best_ret', C.c_void_p), ('best_sample', C.c_void_p), ('best_action', C.c_void_p), ('length', C.c_void_p), ('done', C.c_void_p),
+                ('achieved', C.c_void_p), ('hdr', C.c_void_p), ('slot_pos', C.c_void_p), ('plan', C.c_void_p), ('ret', C.c_void_p)]
+
+
 class cw_profile(C.Structure):
     _fields_ = [('steps', C.c_int32), ('ms_step_kernel', C.c_float), ('ms_reset_kernel', C.c_float),
                 ('ms_render_kernel', C.c_float), ('ms_render_kernel_max', C.c_float), ('ms_render_kernel_min', C.c_float),
@@ -103,6 +108,8 @@ ABI = {
     'cw_export_onehot_states': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_simulate': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.POINTER(cw_simulate_out), _VP]),
     'cw_plan': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_plan_out), _VP]),
+    'cw_shoot': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, C.POINTER(cw_shoot_out), _VP]),
+    'cw_shoot_actions': (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
@@ -151,6 +158,8 @@ CWH_REC_OK, CWH_REC_NO_FIELD, CWH_REC_N_STATES, CWH_REC_N_STEPS, CWH_REC_PAIR, C
 CWH_REC_PLAN_WORK = 7
 CWH_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_PLAN_MAX_DEPTH, CWH_PLAN_MAX_LEAVES = 8, 1 << 32
+CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
+CWH_SHOOT_MAX_SAMPLES, CWH_SHOOT_MAX_WORK = 65536, 1 << 32
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -176,6 +185,11 @@ HOST_HELPERS = {
     'cwh_envs_per_wave_of': (C.c_int, [C.c_int, C.c_int]),
     'cwh_records_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int]),
     'cwh_plan_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
+    'cwh_shoot_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
+    'cwh_shoot_actions_args': (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    'cwh_shoot_draw_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
+    'cwh_shoot_action_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
+    'cwh_shoot_lanes_of': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),

@@ -39,6 +39,10 @@ hipError_t cwk_launch_render_onehot(const CwParams *P, const uint8_t *onehot, in
 hipError_t cwk_launch_render_restore(const CwParams *P, const CwTuning *T, hipStream_t st);
 hipError_t cwk_launch_plan(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, int depth, const CwPlanOut *O,
                            hipStream_t st);
+hipError_t cwk_launch_shoot(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, int n_steps, int n_samples,
+                            unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights, const CwShootOut *O, hipStream_t st);
+hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsigned long long seed, const unsigned long long *seed_dev,
+                                    const uint16_t *weights, const int32_t *samples, uint8_t *out, hipStream_t st);
 hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
                                int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
@@ -214,7 +218,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -1002,6 +1006,67 @@ int cw_plan(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const ui
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.plan = out->plan;
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     HIP_TRY(cwk_launch_plan(&e->P, env_of, h, p, n_states, depth, &O, (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ shoot: the best of n_samples drawn plans of n_steps steps per state
+// cw_plan's shape: checks (cwh_shoot_args: cw_plan's rules on the records, the steps, the samples and the cap on one launch's work; the large outputs may
+// overlap neither the records read nor the weights), then ONE kernel.  Writes nothing of the engine but counters[7].
+int cw_shoot(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t n_steps, int32_t n_samples,
+             uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights, const cw_shoot_out *out, cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_shoot: null %s", !e ? "engine" : "out");
+    const int n_fields = !!out->best_ret + !!out->best_sample + !!out->best_action + !!out->length + !!out->done + !!out->achieved + !!out->hdr +
+                         !!out->slot_pos + !!out->plan + !!out->ret;
+    switch (cwh_shoot_args(e->n, env_of != nullptr, hdr_in != nullptr, slot_pos_in != nullptr, n_states, n_steps, n_samples, n_fields)) {
+    case CWH_REC_SHOOT_SAMPLES: return fail(CW_ERR_INVALID, "cw_shoot: n_samples = %d must be 1 .. %d", n_samples, CWH_SHOOT_MAX_SAMPLES);
+    case CWH_REC_SHOOT_WORK:
+        return fail(CW_ERR_INVALID, "cw_shoot: n_states = %d times n_samples = %d times n_steps = %d is above 2^32 steps in one call", n_states, n_samples, n_steps);
+    default: break;
+    }
+    const int bad = records_args("cw_shoot", e, env_of, hdr_in, slot_pos_in, n_states, n_steps, CWH_SIM_MAX_STEPS, false, n_fields, out->hdr, out->slot_pos);
+    if (bad != CW_OK) return bad;
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    const uint64_t m = (uint64_t)n_states, rec_bytes = 16ull * m, w_bytes = weights ? 12ull * (uint64_t)n_steps * m : 0;
+    const struct { const void *at; uint64_t bytes; const char *name; } outs[4] = {
+        {out->hdr, rec_bytes, "hdr"}, {out->slot_pos, rec_bytes, "slot_pos"}, {out->plan, (uint64_t)n_steps * m, "plan"}, {out->ret, 4ull * (uint64_t)n_samples * m, "ret"}};
+    for (int k = 0; k < 4; k++) {
+        if (!outs[k].at) continue;
+        if (overlaps_records(outs[k].at, outs[k].bytes, h, p, rec_bytes)) return fail(CW_ERR_INVALID, "cw_shoot: out->%s overlaps the records read", outs[k].name);
+        if (cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k].at, outs[k].bytes, (uint64_t)(uintptr_t)weights, w_bytes))
+            return fail(CW_ERR_INVALID, "cw_shoot: out->%s overlaps the weights", outs[k].name);
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_shoot called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    CwShootOut O;
+    O.best_ret = out->best_ret; O.best_sample = out->best_sample; O.best_action = out->best_action; O.length = out->length; O.done = out->done;
+    O.achieved = out->achieved; O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.plan = out->plan; O.ret = out->ret;
+    HIP_TRY(cwk_launch_shoot(&e->P, env_of, h, p, n_states, n_steps, n_samples, (unsigned long long)seed, (const unsigned long long *)seed_dev, weights, &O,
+                             (hipStream_t)stream));
+    return in.done();
+}
+
+// ... and the draws themselves: the engine contributes its stream bookkeeping and the has_reset rule, nothing of it is read by the kernel
+int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights, const int32_t *samples,
+                     int32_t n_rows, uint8_t *out, cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_shoot_actions: null %s", !e ? "engine" : "out");
+    switch (cwh_shoot_actions_args(n_states, n_steps, n_rows)) {
+    case CWH_REC_OK: break;
+    case CWH_REC_N_STATES: return fail(CW_ERR_INVALID, "cw_shoot_actions: n_states = %d must be 0 .. %d", n_states, CWH_MAX_STATES);
+    case CWH_REC_SHOOT_SAMPLES: return fail(CW_ERR_INVALID, "cw_shoot_actions: n_rows = %d must be 0 .. %d", n_rows, CWH_MAX_STATES);
+    case CWH_REC_N_STEPS: return fail(CW_ERR_INVALID, "cw_shoot_actions: n_steps = %d must be 1 .. %d", n_steps, CWH_SIM_MAX_STEPS);
+    default:
+        return fail(CW_ERR_INVALID, "cw_shoot_actions: n_rows = %d times n_states = %d times n_steps = %d is above 2^32 actions in one call", n_rows, n_states, n_steps);
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_shoot_actions called before cw_reset");
+    if (n_states == 0 || n_rows == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_shoot_actions(n_states, n_steps, n_rows, (unsigned long long)seed, (const unsigned long long *)seed_dev, weights, samples, out,
+                                     (hipStream_t)stream));
     return in.done();
 }
 

@@ -203,6 +203,33 @@ int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot
     return rc;
 }
 
+int cwh_shoot_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int32_t n_samples,
+                   int n_out_fields)
+{
+    const int rc = cwh_records_args(num_envs, has_env_of, has_hdr_in, has_slot_pos_in, n_states, n_steps, n_out_fields, CWH_SIM_MAX_STEPS, 0);
+    if (rc == CWH_REC_NO_FIELD || rc == CWH_REC_N_STATES || rc == CWH_REC_N_STEPS) return rc;
+    if (n_samples < 1 || n_samples > CWH_SHOOT_MAX_SAMPLES) return CWH_REC_SHOOT_SAMPLES;
+    if ((uint64_t)n_states * (uint64_t)n_samples * (uint64_t)n_steps > CWH_SHOOT_MAX_WORK) return CWH_REC_SHOOT_WORK;      // (<= 2^27 * 2^16 * 2^15)
+    return rc;
+}
+
+int cwh_shoot_actions_args(int32_t n_states, int32_t n_steps, int32_t n_rows)
+{
+    if (n_states < 0 || n_states > CWH_MAX_STATES) return CWH_REC_N_STATES;
+    if (n_rows < 0 || n_rows > CWH_MAX_STATES) return CWH_REC_SHOOT_SAMPLES;
+    if (n_steps < 1 || n_steps > CWH_SIM_MAX_STEPS) return CWH_REC_N_STEPS;
+    const uint64_t columns = (uint64_t)n_rows * (uint64_t)n_states;   // (<= 2^54)
+    if (columns > CWH_SHOOT_MAX_WORK || columns * (uint64_t)n_steps > CWH_SHOOT_MAX_WORK) return CWH_REC_SHOOT_WORK;
+    return CWH_REC_OK;
+}
+
+uint32_t cwh_shoot_draw_of(uint64_t seed, uint32_t state, uint32_t sample, uint32_t step) { return cwh_shoot_draw(seed, state, sample, step); }
+uint32_t cwh_shoot_action_of(uint64_t seed, uint32_t state, uint32_t sample, uint32_t step, const uint16_t *weights)
+{
+    return cwh_shoot_action(cwh_shoot_draw(seed, state, sample, step), weights, 1);
+}
+int cwh_shoot_lanes_of(int32_t n_states, int32_t n_samples) { return cwh_shoot_lanes(n_states, n_samples); }
+
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)
 {
     if (!a_bytes || !b_bytes) return 0;

@@ -118,6 +118,64 @@ int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot
 // the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
 
+// ---- cw_shoot / cw_shoot_actions: THE DRAW (include/craftingworld.h states it), shared by the kernels and the host -- integers only, so a CPU model is exact.
+// cwh_shoot_prefix is the part that does not depend on the step: the kernels compute it once per sample, outside the step loop.
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_mix(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_prefix(uint64_t seed, uint32_t state, uint32_t sample)
+{
+    const uint32_t x = cwh_shoot_mix((uint32_t)seed ^ state * 0x9E3779B1u);
+    return cwh_shoot_mix(x ^ ((uint32_t)(seed >> 32) + sample * 0x85EBCA77u));
+}
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_step(uint32_t prefix, uint32_t step) { return cwh_shoot_mix(prefix ^ step * 0xC2B2AE3Du); }
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_draw(uint64_t seed, uint32_t state, uint32_t sample, uint32_t step)
+{
+    return cwh_shoot_step(cwh_shoot_prefix(seed, state, sample), step);
+}
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_mulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
+// the action of a draw under six weights (all 0: uniform, like no weights at all): how many of the first five partial sums lie at or below mulhi32(r, W)
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_action_w(uint32_t r, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5)
+{
+    const uint32_t c0 = w0, c1 = c0 + w1, c2 = c1 + w2, c3 = c2 + w3, c4 = c3 + w4, W = c4 + w5;
+    if (W == 0u) return cwh_shoot_mulhi(r, 6u);
+    const uint32_t x = cwh_shoot_mulhi(r, W);
+    return (uint32_t)(c0 <= x) + (uint32_t)(c1 <= x) + (uint32_t)(c2 <= x) + (uint32_t)(c3 <= x) + (uint32_t)(c4 <= x);
+}
+static inline CWH_HOST_DEVICE uint32_t cwh_shoot_action(uint32_t r, const uint16_t *w, size_t stride)
+{
+    if (!w) return cwh_shoot_mulhi(r, 6u);
+    return cwh_shoot_action_w(r, w[0], w[stride], w[2 * stride], w[3 * stride], w[4 * stride], w[5 * stride]);
+}
+// (the draw and its action, exported for the CPU tests: weights null or six uint16, contiguous)
+uint32_t cwh_shoot_draw_of(uint64_t seed, uint32_t state, uint32_t sample, uint32_t step);
+uint32_t cwh_shoot_action_of(uint64_t seed, uint32_t state, uint32_t sample, uint32_t step, const uint16_t *weights);
+// THE lanes cw_shoot_kernel gives one state (they play its samples g, g + G, ...): the smallest power of two G with n_states * G >= 65 536 -- a small batch
+// spreads its samples over the wave --, at most 64 and at most the largest power of two <= n_samples (so one sample is one lane).  n_states * G < 2^28.
+#ifndef CWH_SHOOT_FILL
+#define CWH_SHOOT_FILL 65536     // (one wave on each SIMD of 256 CUs; an experimental build may set another target: make exp EXP='-DCWH_SHOOT_FILL=...')
+#endif
+static inline int cwh_shoot_lanes(int32_t n_states, int32_t n_samples)
+{
+    int g = 1;
+    while (g < CW_WAVE && 2 * g <= n_samples && (int64_t)n_states * g < CWH_SHOOT_FILL) g <<= 1;
+    return g;
+}
+int cwh_shoot_lanes_of(int32_t n_states, int32_t n_samples);       // (the same, exported for the CPU tests)
+// the argument rules of cw_shoot: cwh_records_args as cw_plan calls it (its own states once) with 1 <= n_steps <= CWH_SIM_MAX_STEPS, then
+// 1 <= n_samples <= CWH_SHOOT_MAX_SAMPLES (CWH_REC_SHOOT_SAMPLES) and the cap on the work of ONE launch, n_states * n_samples * n_steps <=
+// CWH_SHOOT_MAX_WORK (CWH_REC_SHOOT_WORK: 65 536 states x 1 024 samples x 64 steps), both behind the step check and before the pointer rules.
+#define CWH_SHOOT_MAX_SAMPLES 65536
+#define CWH_SHOOT_MAX_WORK (1ull << 32)
+enum { CWH_REC_SHOOT_WORK = 8, CWH_REC_SHOOT_SAMPLES = 9 };
+int cwh_shoot_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int32_t n_samples,
+                   int n_out_fields);
+// ... and of cw_shoot_actions, in order: 0 <= n_states <= CWH_MAX_STATES (CWH_REC_N_STATES), 0 <= n_rows <= CWH_MAX_STATES (CWH_REC_SHOOT_SAMPLES),
+// 1 <= n_steps <= CWH_SIM_MAX_STEPS (CWH_REC_N_STEPS), n_rows * n_states * n_steps <= CWH_SHOOT_MAX_WORK (CWH_REC_SHOOT_WORK)
+int cwh_shoot_actions_args(int32_t n_states, int32_t n_steps, int32_t n_rows);
+
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).
 typedef struct cwh_guard {

@@ -20,6 +20,8 @@
 //                     action bytes fetched a block of steps ahead; writes nothing of the engine.
 //   cw_plan_kernel    the best return within D steps after each first action of M such states and the plan that reaches it: one lane per (first action,
 //                     state) pair, a depth-first search with its stack in registers and a wave-uniform action at every level; writes nothing of the engine.
+//   cw_shoot_kernel   random shooting: the best of K sampled T-step plans of M such states, the actions drawn where they are used by a counter-based
+//                     integer mix (no action tensor), G lanes per state and a shuffle reduction; cw_shoot_actions_kernel decodes the draws.  Pure.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -621,12 +623,13 @@ __global__ __launch_bounds__(256) void cw_step_kernel(CwParams P, const void *ac
 }
 
 // ------------------------------------------------------------------------------------ the caller's states
-// The prologue of the pure kernels (cw_expand_kernel, cw_simulate_kernel, cw_plan_kernel), one lane per state j of n_states: the env the state belongs to
+// The prologue of the pure kernels (cw_expand_kernel, cw_simulate_kernel, cw_plan_kernel, cw_shoot_kernel), one lane per state j of n_states: the env the state belongs to
 // (it supplies init_pos), or a negative value when the state takes no part -- such a lane returns at once and writes no row.  env_of == null: env j % n_envs;
 // else env_of[j] -- negative: no part; an index only behind cwh_expand_env_ok, else the state is SKIPPED and, where `count` is set, counted in counters[7],
 // once a wave by ballot (`count` is wave-uniform, and every lane of the wave calls this: kernels whose grid visits a state several times, one wave per first
-// action, set it in the action-0 waves only).  The records themselves are only ever compared, never used as addresses.
-__device__ __forceinline__ int state_env(const CwParams &P, const int32_t *__restrict__ env_of, int j, int n_states, bool count)
+// action, set it in the action-0 waves only; a kernel that gives one state several LANES of a wave, cw_shoot_kernel, passes first_lane = the state's
+// lane 0, and the ballot counts those).  The records themselves are only ever compared, never used as addresses.
+__device__ __forceinline__ int state_env(const CwParams &P, const int32_t *__restrict__ env_of, int j, int n_states, bool count, bool first_lane = true)
 {
     int env = -1;
     bool skipped = false;
@@ -640,7 +643,7 @@ __device__ __forceinline__ int state_env(const CwParams &P, const int32_t *__res
         }
     }
     if (count) {
-        const unsigned long long m_skip = CW_BALLOT(skipped);
+        const unsigned long long m_skip = CW_BALLOT(skipped && first_lane);
         if (m_skip && (threadIdx.x & (CW_WAVE - 1)) == 0) atomicAdd(&P.counters[7], (unsigned long long)__popcll(m_skip));
     }
     return env;
@@ -837,6 +840,165 @@ __global__ __launch_bounds__(256) void cw_plan_kernel(CwParams P, const int32_t 
     if (O.plan) {
         uint8_t *const pl = O.plan + (size_t)a0 * (size_t)depth * M + (size_t)j;
         for (int t = 0; t < depth; t++) pl[(size_t)t * M] = (uint8_t)((b.digits >> (3 * t)) & 7u);
+    }
+}
+
+// ------------------------------------------------------------------------------------ shoot
+// cw_shoot: random shooting -- K sampled plans of T steps per state, the best of them and what cw_simulate returns for it -- as cw_simulate_kernel's
+// register-resident step loop with the action bytes replaced by THE DRAW (cw_host.h: cwh_shoot_prefix / _step / _action_w, a counter-based integer mix of
+// (seed, state, sample, step): no generator state, no action tensor, every sample reproducible from its index), crossed with a reduction over the samples.
+// LANES: a state has G = 1 << lg lanes (cwh_shoot_lanes: a power of two that divides the wave), lane (j, g) at global lane j * G + g, so a state's lanes are
+// adjacent in one wave; lane g plays samples g, g + G, ... one after the other.  The three 16-byte record loads happen once per lane (the G lanes of a state
+// read the same address).  The sample loop is wave-uniform: a lane whose k has passed K plays on, `valid` false, and its results are dropped.
+// INSIDE THE STEP LOOP there is no memory access in the uniform instance.  The WEIGHTED instance (its own template instance: the uniform one carries no loads
+// at all) reads six uint16 a step, whose addresses depend on the step and the state only, not on the sample: they are fetched CW_SHOOT_WBLOCK steps at a
+// time, one block AHEAD of the steps that use them, as cw_simulate_kernel fetches its action bytes -- and the block fetched ahead of a sample's last block
+// is block 0, the next sample's first (`held` says which block the registers hold: a wave that left the step loop early reloads block 0).
+// A sample ends at its first done step: frozen by selection; the wave leaves the step loop on a ballot once every lane's sample has ended.
+// THE BEST of a lane (CwPlanBest's shape: return, sample, length | done << 16, the final record) is replaced only on a STRICTLY greater return; a lane's
+// samples ascend, so what stays is its smallest maximiser.  The G lanes then agree on the key (return, then the smaller sample) by xor-shuffles, and the lane
+// that holds the winning sample WRITES ITS OWN RECORD: the winner is not simulated a second time.  ret[k][j] is written by the lane that played k.  `plan`
+// is regenerated from the draw alone (T mixes, no step_env), the G lanes sharing its rows.  state_env is called by every lane; the state's lane 0 counts.
+#define CW_SHOOT_WBLOCK 4
+struct CwShootBest {
+    int32_t ret;
+    int32_t k;
+    uint32_t meta;           // length | done << 16
+    uint4 h, pos;
+};
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void cw_shoot_kernel(CwParams P, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                       const uint4 *__restrict__ pos_in, int n_states, int T, int K, int lg, unsigned long long seed,
+                                                       const unsigned long long *__restrict__ seed_dev, const uint16_t *__restrict__ weights, CwShootOut O)
+{
+    constexpr int B = WEIGHTED ? CW_SHOOT_WBLOCK : 1;
+    const int lane_id = (int)(blockIdx.x * blockDim.x + threadIdx.x);    // (n_states << lg < 2^28: cwh_shoot_lanes)
+    const int G = 1 << lg, j = lane_id >> lg, g = lane_id & (G - 1);
+    const int env = state_env(P, env_of, j, n_states, true, g == 0);
+    if (env < 0) return;                                                  // (all G lanes of the state alike)
+    const size_t M = (size_t)n_states;
+    const unsigned long long s = seed + (seed_dev ? *seed_dev : 0ull);
+    const uint4 h0 = hdr_in[j], p0 = pos_in[j], ip = P.init_pos[env];
+    const uint16_t *const wp = WEIGHTED ? weights + j : nullptr;
+    uint32_t wraw[B * 6];
+    int held = -1;                                                        // the block (its first step) wraw holds; uniform
+    auto load_block = [&](int tb) {
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int i = 0; i < B; i++)
+#pragma unroll
+                for (int a = 0; a < 6; a++) wraw[i * 6 + a] = wp[((size_t)min(tb + i, T - 1) * 6 + (size_t)a) * M];
+        }
+        held = tb;
+    };
+    CwShootBest b;
+    b.ret = INT32_MIN; b.k = INT32_MAX; b.meta = 0; b.h = h0; b.pos = p0;
+
+    for (int k0 = 0; k0 < K; k0 += G) {                                   // (uniform)
+        const int k = k0 + g;
+        const bool valid = k < K;
+        const uint32_t px = cwh_shoot_prefix(s, (uint32_t)j, (uint32_t)k);
+        uint4 h = h0;
+        uint32_t sp[8];
+        unpack_pos(p0, sp);
+        int32_t ret = 0, length = T;
+        bool active = valid, any_done = false;
+        if (WEIGHTED && held != 0) load_block(0);
+        for (int t0 = 0; t0 < T; t0 += B) {
+            uint32_t w[B * 3];
+            if constexpr (WEIGHTED) {
+#pragma unroll
+                for (int i = 0; i < B * 3; i++) w[i] = wraw[2 * i] | (wraw[2 * i + 1] << 16);
+                load_block(t0 + B < T ? t0 + B : 0);                      // in flight while this block steps
+            }
+            if (!CW_BALLOT(active)) break;                                // every sample of the wave has ended
+#pragma unroll
+            for (int i = 0; i < B; i++) {
+                const int t = t0 + i;
+                if (B > 1 && t >= T) break;                               // (uniform)
+                const uint32_t r = cwh_shoot_step(px, (uint32_t)t);
+                int a;
+                if constexpr (WEIGHTED)
+                    a = (int)cwh_shoot_action_w(r, w[3 * i] & 0xFFFFu, w[3 * i] >> 16, w[3 * i + 1] & 0xFFFFu, w[3 * i + 1] >> 16, w[3 * i + 2] & 0xFFFFu,
+                                                w[3 * i + 2] >> 16);
+                else
+                    a = (int)cwh_shoot_mulhi(r, 6u);
+                uint4 h2 = h;
+                uint32_t sp2[8];
+#pragma unroll
+                for (int q = 0; q < 8; q++) sp2[q] = sp[q];
+                const CwStepOut o = step_env(P, h2, sp2, a, [&]() { return ip; });
+                const bool done_now = active && o.done;
+                h.x = active ? h2.x : h.x; h.y = active ? h2.y : h.y; h.z = active ? h2.z : h.z; h.w = active ? h2.w : h.w;
+#pragma unroll
+                for (int q = 0; q < 8; q++) sp[q] = active ? sp2[q] : sp[q];
+                ret += active ? o.reward : 0;
+                length = (done_now && !any_done) ? t + 1 : length;
+                any_done = any_done || done_now;
+                active = active && !o.done;
+            }
+        }
+        if (valid) {
+            if (O.ret) O.ret[(size_t)k * M + (size_t)j] = ret;
+            if (ret > b.ret) {
+                b.ret = ret;
+                b.k = k;
+                b.meta = (uint32_t)length | (any_done ? 0x10000u : 0u);
+                b.h = h;
+                b.pos = pack_pos(sp);
+            }
+        }
+    }
+
+    int32_t win_ret = b.ret, win_k = b.k;                                 // the key of the state's best: every lane has played a sample (G <= K)
+    for (int off = 1; off < G; off <<= 1) {
+        const int32_t o_ret = __shfl_xor(win_ret, off), o_k = __shfl_xor(win_k, off);
+        const bool take = o_ret > win_ret || (o_ret == win_ret && o_k < win_k);
+        win_ret = take ? o_ret : win_ret;
+        win_k = take ? o_k : win_k;
+    }
+    const uint32_t wx = cwh_shoot_prefix(s, (uint32_t)j, (uint32_t)win_k);
+    auto drawn = [&](int t) -> uint8_t {                                  // action t of the winning sample
+        const uint32_t r = cwh_shoot_step(wx, (uint32_t)t);
+        if constexpr (WEIGHTED) return (uint8_t)cwh_shoot_action(r, wp + (size_t)t * 6 * M, M);
+        else return (uint8_t)cwh_shoot_mulhi(r, 6u);
+    };
+    if (win_k == b.k) {                                                   // the lane that played it (the samples of a state's lanes are disjoint)
+        if (O.best_ret) O.best_ret[j] = b.ret;
+        if (O.best_sample) O.best_sample[j] = b.k;
+        if (O.best_action) O.best_action[j] = drawn(0);
+        if (O.length) O.length[j] = (int32_t)(b.meta & 0xFFFFu);
+        if (O.done) O.done[j] = (uint8_t)(b.meta >> 16);
+        if (O.achieved) O.achieved[j] = (uint16_t)(b.h.y & 0xFFFFu);
+        if (O.hdr) O.hdr[j] = b.h;
+        if (O.pos) O.pos[j] = b.pos;
+    }
+    if (O.plan)
+        for (int t = g; t < T; t += G) O.plan[(size_t)t * M + (size_t)j] = drawn(t);
+}
+
+// cw_shoot_actions: the drawn actions themselves, out[t][r][j] of sample samples[r][j] (null: r) of state j -- one lane per (row, state) column, grid-stride,
+// a loop over t; a negative sample leaves its column unwritten.  Reads nothing of the engine.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void cw_shoot_actions_kernel(int n_states, int T, int n_rows, unsigned long long seed,
+                                                               const unsigned long long *__restrict__ seed_dev, const uint16_t *__restrict__ weights,
+                                                               const int32_t *__restrict__ samples, uint8_t *__restrict__ out)
+{
+    const size_t M = (size_t)n_states, columns = (size_t)n_rows * M;
+    const unsigned long long s = seed + (seed_dev ? *seed_dev : 0ull);
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < columns; c += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = c / M, j = c - r * M;
+        const int32_t k = samples ? samples[c] : (int32_t)r;
+        if (k < 0) continue;
+        const uint32_t px = cwh_shoot_prefix(s, (uint32_t)j, (uint32_t)k);
+        for (int t = 0; t < T; t++) {
+            const uint32_t x = cwh_shoot_step(px, (uint32_t)t);
+            uint32_t a;
+            if constexpr (WEIGHTED) a = cwh_shoot_action(x, weights + (size_t)t * 6 * M + j, M);
+            else a = cwh_shoot_mulhi(x, 6u);
+            out[(size_t)t * columns + c] = (uint8_t)a;
+        }
     }
 }
 
@@ -2673,6 +2835,33 @@ hipError_t cwk_launch_plan(const CwParams *P, const int32_t *env_of, const uint4
                            hipStream_t st)
 {
     hipLaunchKernelGGL(cw_plan_kernel, dim3((unsigned)((n_states + 255) / 256), 6u), dim3(256), 0, st, *P, env_of, hdr_in, pos_in, n_states, depth, *O);
+    return hipGetLastError();
+}
+
+// cw_shoot: one launch of n_states * G lanes (G = cwh_shoot_lanes); the weighted draw is its own instance
+hipError_t cwk_launch_shoot(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, int n_steps, int n_samples,
+                            unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights, const CwShootOut *O, hipStream_t st)
+{
+    int lg = 0;
+    while ((1 << lg) < cwh_shoot_lanes(n_states, n_samples)) lg++;
+    const dim3 grid((unsigned)((((size_t)n_states << lg) + 255) / 256)), block(256);
+    if (weights)
+        hipLaunchKernelGGL(cw_shoot_kernel<true>, grid, block, 0, st, *P, env_of, hdr_in, pos_in, n_states, n_steps, n_samples, lg, seed, seed_dev, weights, *O);
+    else
+        hipLaunchKernelGGL(cw_shoot_kernel<false>, grid, block, 0, st, *P, env_of, hdr_in, pos_in, n_states, n_steps, n_samples, lg, seed, seed_dev, weights, *O);
+    return hipGetLastError();
+}
+
+// cw_shoot_actions: one grid-stride launch over the n_rows * n_states columns
+hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsigned long long seed, const unsigned long long *seed_dev,
+                                    const uint16_t *weights, const int32_t *samples, uint8_t *out, hipStream_t st)
+{
+    const size_t columns = (size_t)n_rows * (size_t)n_states, want = (columns + 255) / 256;
+    const dim3 grid((unsigned)(want < 65536 ? want : 65536)), block(256);
+    if (weights)
+        hipLaunchKernelGGL(cw_shoot_actions_kernel<true>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
+    else
+        hipLaunchKernelGGL(cw_shoot_actions_kernel<false>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
     return hipGetLastError();
 }
 

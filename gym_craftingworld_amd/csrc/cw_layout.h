@@ -126,6 +126,20 @@ struct CwPlanOut {
     uint8_t *plan;           // [6][D][M] its actions, step-major; 0 behind its end
 };
 
+// Where cw_shoot_kernel leaves the best of each state's K sampled plans (the public cw_shoot_out with the records typed).  A null field is not written.
+struct CwShootOut {
+    int32_t *best_ret;       // [M] the largest return of any sample
+    int32_t *best_sample;    // [M] the smallest sample that reaches it
+    uint8_t *best_action;    // [M] its first action
+    int32_t *length;         // [M] steps it takes
+    uint8_t *done;           // [M] it ends inside the horizon
+    uint16_t *achieved;      // [M]
+    uint4 *hdr;              // [M] record after its last step
+    uint4 *pos;              // [M]
+    uint8_t *plan;           // [T][M] all T drawn actions of it, step-major
+    int32_t *ret;            // [K][M] the return of every sample
+};
+
 // Everything the kernels need, passed by value.
 struct CwParams {
     // per-env state (SoA of 16-byte records unless noted)

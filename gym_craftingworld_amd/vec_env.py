@@ -296,6 +296,59 @@ def plan_args(num_envs, depth, hdr, slot_pos, env_of):
     return _plan_depth(depth, m), m
 
 
+SHOOT_FIELDS = ('best_ret', 'best_sample', 'best_action', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'ret')
+SHOOT_MAX_SAMPLES, SHOOT_MAX_WORK = 65536, 2 ** 32
+
+
+def _shoot_int(v, what, lo, hi):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError('%s must be an integer %d .. %d, got %r' % (what, lo, hi, v))
+    if not lo <= int(v) <= hi:
+        raise ValueError('%s = %d: %d .. %d in one call' % (what, int(v), lo, hi))
+    return int(v)
+
+
+def _shoot_tk(horizon, samples, m):
+    """shoot_args on the horizon, the number of samples and the number of states: -> (T, K)"""
+    T, K = _shoot_int(horizon, 'horizon', 1, SIMULATE_MAX_STEPS), _shoot_int(samples, 'samples', 1, SHOOT_MAX_SAMPLES)
+    if m * K * T > SHOOT_MAX_WORK:
+        raise ValueError('%d states x %d samples x %d steps are %d steps: at most 2**32 in one call' % (m, K, T, m * K * T))
+    return T, K
+
+
+def shoot_args(num_envs, horizon, samples, hdr, slot_pos, env_of):
+    """What cw_shoot is handed, validated on the host: -> (T, K, M).  horizon: an integer 1 .. 32 767, samples: an integer 1 .. 65 536, with
+    M * samples * horizon <= 2**32 (65 536 states x 1 024 samples x 64 steps); hdr / slot_pos / env_of: numpy inputs under expand_args' rules (both records
+    or neither, env_of only with them, IndexError for an entry >= num_envs).  ValueError for everything else."""
+    m = expand_args(num_envs, hdr, slot_pos, env_of)
+    return _shoot_tk(horizon, samples, m) + (m,)
+
+
+def shoot_seed(seed):
+    """the scalar seed of shoot() / shoot_actions(): an integer 0 .. 2**64 - 1 (ValueError otherwise)"""
+    return _shoot_int(seed, 'seed', 0, 2 ** 64 - 1)
+
+
+def shoot_weights(weights, horizon, m):
+    """The weights of shoot() / shoot_actions() on the host-validated path: integers 0 .. 65 535 of shape [T, 6, M] or [T, 6] (every state alike: BROADCAST
+    WITH A COPY to [T, 6, M]) -> contiguous np.uint16 [T, 6, M].  Floats raise TypeError: the draw is integer arithmetic, and how probabilities become
+    integers is the caller's choice (np.round(p * 65535).astype(np.uint16) keeps 16 bits; a weight that must stay possible has to stay >= 1).  ValueError
+    for another dtype, shape or a value outside 0 .. 65 535."""
+    w = np.asarray(weights)
+    if np.issubdtype(w.dtype, np.floating):
+        raise TypeError('weights are integers 0 .. 65535 (the draw is exact integer arithmetic): quantise probabilities yourself, e.g. '
+                        'np.round(p * 65535).astype(np.uint16), got %s' % w.dtype)
+    if w.dtype == np.bool_ or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError('weights must be integers 0 .. 65535 (uint16 goes over in place), got %s' % w.dtype)
+    if w.shape not in ((horizon, 6, m), (horizon, 6)):
+        raise ValueError('weights must be [T, 6, M] = %s or [T, 6], got %s' % ((horizon, 6, m), w.shape))
+    if w.size and (int(w.min()) < 0 or int(w.max()) > 65535):
+        raise ValueError('weights must lie in 0 .. 65535, got %d .. %d' % (int(w.min()), int(w.max())))
+    if w.ndim == 2:
+        w = np.broadcast_to(w[:, :, None], (horizon, 6, m))
+    return np.ascontiguousarray(w, dtype=np.uint16)
+
+
 def _render_records_m(frame_shape, lead, mask, out):
     """render_records_args on the records' leading shape and the (shape, numpy dtype) of mask and out (None: not given)"""
     lead, frame_shape = tuple(int(x) for x in lead), tuple(int(x) for x in frame_shape)
@@ -763,7 +816,7 @@ class CraftingWorldVecEnv:
     # ------------------------------------------------------------------ looking one step ahead
     @property
     def expand_skipped(self):
-        """how many states expand() and simulate() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
+        """how many states expand(), simulate(), plan() and shoot() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
         return int(self._counters_raw[7].item())
 
     def _records(self, hdr, slot_pos, env_of):
@@ -888,6 +941,89 @@ class CraftingWorldVecEnv:
         if ids is None:
             ids = self._plan_ids = torch.arange(6, dtype=torch.uint8, device=self.device).reshape(6, 1)
         return ids
+
+    # ------------------------------------------------------------------ shooting plans
+    def _shoot_seed(self, seed):
+        """seed as shoot() takes it -> (the scalar, the device word or None)"""
+        if type(seed) is torch.Tensor:
+            if seed.numel() != 1 or seed.dtype not in (torch.int64, torch.uint64) or seed.device != self.device or not seed.is_contiguous():
+                raise ValueError('a seed tensor must hold one int64 / uint64 element on %s, got %s %s on %s' % (self.device, seed.dtype, tuple(seed.shape), seed.device))
+            return 0, seed
+        return shoot_seed(seed), None
+
+    def _shoot_weights(self, weights, T, m):
+        """weights as shoot() takes them -> a uint16 [T, 6, M] tensor on the env's device, or None"""
+        if weights is None or self._in_place(weights, (torch.uint16,), (T, 6, m)):
+            return weights
+        if self._in_place(weights, (torch.uint16,), (T, 6)):
+            return weights[:, :, None].expand(T, 6, m).contiguous()
+        if torch.is_tensor(weights) and weights.dtype.is_floating_point:
+            shoot_weights(np.empty(0, np.float32), T, m)                 # (the TypeError, without a copy of the tensor)
+        return torch.as_tensor(shoot_weights(as_numpy(weights), T, m)).to(self.device)
+
+    def shoot(self, horizon, samples, seed=0, hdr=None, slot_pos=None, env_of=None, *, weights=None, fields=None, out=None):
+        """Which of `samples` random plans of `horizon` steps does best from here?  (cw_shoot: ONE kernel that draws every action where it is used --
+        a counter-based integer function of (seed, state, sample, step), stated in include/craftingworld.h and reproduced by shoot_actions() -- so no
+        [T, K, M] action tensor exists; no host round trip, capturable; no env is touched.)  horizon: 1 .. 32 767, samples: 1 .. 65 536, with
+        M * samples * horizon <= 2**32.  seed: an int 0 .. 2**64 - 1, or a one-element int64 / uint64 tensor on the env's device, which the KERNEL reads:
+        a captured graph draws new plans on every replay once the caller has changed the word.  The states are plan()'s: without records the envs' current
+        ones (M = num_envs), else hdr [..., 16] / slot_pos [..., 8] / env_of under expand()'s rules (a negative env_of entry takes no part and none of its
+        rows is written, an entry >= num_envs handed over on the device is skipped and counted once in expand_skipped).  weights: None (uniform actions)
+        or integers 0 .. 65 535 of shape [T, 6, M] -- weights[t, a, j] is the weight of action a at step t of state j, 0 forbids it, six zeros mean
+        uniform -- or [T, 6], every state alike, which is BROADCAST WITH A COPY; a uint16 tensor on the env's device goes over in place, other integers
+        are validated and converted on the host, floats raise TypeError (shoot_weights).
+        -> a dict of device tensors: 'best_ret' int32 [M], the largest return simulate(stop_at_done=True) gives any sample; 'best_sample' int32 [M], the
+        SMALLEST sample that reaches it; 'best_action' uint8 [M], its first action; 'length' int32 [M], 'done' bool [M], 'achieved_mask' [M], 'hdr' uint8
+        [M, 16] and 'slot_pos' int16 [M, 8]: what simulate() returns for it; 'plan' uint8 [T, M]: all T actions drawn for it, as simulate() takes them;
+        'ret' int32 [K, M]: the return of every sample (CEM's elite selection; shoot_actions(samples=elites) gives their actions).  fields: a subset of
+        SHOOT_FIELDS (default: all but 'hdr', 'slot_pos' and 'ret').  out: a dict returned by an earlier call with the same horizon, samples, M and
+        fields, written again."""
+        names = _field_names(fields, SHOOT_FIELDS, tuple(f for f in SHOOT_FIELDS if f not in ('hdr', 'slot_pos', 'ret')))
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        T, K = _shoot_tk(horizon, samples, m)
+        seed, seed_dev = self._shoot_seed(seed)
+        weights = self._shoot_weights(weights, T, m)
+        spec = {'best_ret': ((m,), torch.int32), 'best_sample': ((m,), torch.int32), 'best_action': ((m,), torch.uint8), 'length': ((m,), torch.int32),
+                'done': ((m,), torch.bool), 'achieved_mask': ((m,), self.achieved_mask.dtype), 'hdr': ((m, 16), torch.uint8),
+                'slot_pos': ((m, 8), self.slot_pos.dtype), 'plan': ((T, m), torch.uint8), 'ret': ((K, m), torch.int32)}
+        out = self._out_dict(out, names, spec)
+        if m:
+            self._call('cw_shoot', env_of, hdr, slot_pos, m, T, K, seed, seed_dev, weights, C.byref(_out_struct(L.cw_shoot_out, out)), keep=out)
+        return out
+
+    def shoot_actions(self, horizon, seed=0, *, samples=None, rows=None, weights=None, n_states=None, out=None):
+        """The actions shoot() draws, themselves (cw_shoot_actions: one kernel, pure) -> uint8 [T, R, M]: entry [t, r, j] is step t of sample
+        samples[r, j] of state j -- or, with samples=None, of sample r, rows = R = K giving the whole action tensor in simulate()'s broadcast layout.
+        samples: int32 [R, M] (an int32 tensor on the env's device goes over in place); a NEGATIVE entry leaves its column of `out` unwritten.
+        horizon, seed and weights as shoot() takes them (the same seed and weights give the same draws); n_states: M (default num_envs).  out: a
+        contiguous uint8 tensor [T, R, M] on the env's device, written again."""
+        m = self.num_envs if n_states is None else _shoot_int(n_states, 'n_states', 0, 2 ** 27)
+        T = _shoot_int(horizon, 'horizon', 1, SIMULATE_MAX_STEPS)
+        if samples is None:
+            if rows is None:
+                raise ValueError('give samples, or rows: how many samples 0 .. rows - 1 to decode')
+            R = _shoot_int(rows, 'rows', 0, 2 ** 27)
+        else:
+            if not self._in_place(samples, (torch.int32,)):
+                s = as_numpy(samples)
+                if not np.issubdtype(s.dtype, np.integer) or s.dtype == np.bool_:
+                    raise ValueError('samples must be integers (int32 goes over in place), got %s' % s.dtype)
+                if s.size and int(s.max()) >= 2 ** 31:
+                    raise ValueError('samples must fit int32, got %d' % int(s.max()))
+                samples = torch.as_tensor(np.ascontiguousarray(np.maximum(s.astype(np.int64), -1), dtype=np.int32)).to(self.device)
+            if samples.dim() != 2 or samples.shape[1] != m or rows is not None and rows != samples.shape[0]:
+                raise ValueError('samples must be [R, M] with M = %d%s, got %s' % (m, '' if rows is None else ' and R = rows = %r' % (rows,), tuple(samples.shape)))
+            R = int(samples.shape[0])
+            if R > 2 ** 27:
+                raise ValueError('%d rows: at most 2**27 in one call' % R)
+        if R * m * T > SHOOT_MAX_WORK:
+            raise ValueError('%d rows x %d states x %d steps are %d actions: at most 2**32 in one call' % (R, m, T, R * m * T))
+        seed, seed_dev = self._shoot_seed(seed)
+        weights = self._shoot_weights(weights, T, m)
+        out = self._out(out, (T, R, m))
+        if R and m:
+            self._call('cw_shoot_actions', m, T, seed, seed_dev, weights, samples, R, out)
+        return out
 
     def one_hot_states(self, hdr, slot_pos, out=None):
         """obs_one_hot (ray.py:119) of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() takes and returns them):

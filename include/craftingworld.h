@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -127,7 +127,7 @@ typedef struct cw_buffer_table {
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
                               *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
-                              *      for a bad row number, [7] counts the states skipped by cw_expand, cw_simulate or cw_plan for an env index at or above num_envs.
+                              *      for a bad row number, [7] counts the states skipped by cw_expand, cw_simulate, cw_plan or cw_shoot for an env index at or above num_envs.
                               *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
@@ -390,6 +390,61 @@ typedef struct cw_plan_out {   /* DEVICE pointers (host_outputs engines: or GPU-
  *   (21x21, launch included: 65 536 envs 23 us at depth 1, 1.08 ms at 4, 5.9 ms at 5, 33.5 ms at 6 with no goal in reach -- the whole tree; the enumeration through cw_simulate: 311 us / 2.47 ms at depths 1 / 4, over its cap from 5 on: tools/measure_plan.py, profiles/r10_plan.txt.) */
 int cw_plan(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t depth,
             const cw_plan_out *out, cw_stream_t stream);
+
+/* --- shooting plans: the best of K SAMPLED plans of T steps per state, at horizons cw_plan cannot reach (random shooting; with `weights` and `ret` the two halves
+ * of a CEM iteration) -- the actions are drawn where they are used, so no [T][K][M] action tensor exists.  M = n_states, T = n_steps, K = n_samples.
+ * THE DRAW is a public, exact, integer function of (seed, state, sample, step); callers reproduce it (uint32 arithmetic wraps; mulhi32(a, b) = (a * b) >> 32 in 64 bits):
+ *   mix(x):   x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16        (uint32, wrapping)
+ *   draw(seed, state, sample, step):                                                            (seed uint64, the rest uint32)
+ *             x = mix((uint32)seed ^ state * 0x9E3779B1)
+ *             x = mix(x ^ ((uint32)(seed >> 32) + sample * 0x85EBCA77))
+ *             return mix(x ^ step * 0xC2B2AE3D)
+ *   action(r, w == NULL)   = mulhi32(r, 6)                                                      (uniform over 0..5)
+ *   action(r, w[0..5] u16) = W = w0 + .. + w5;  W == 0: as w == NULL;
+ *                            else x = mulhi32(r, W);  the number of a in 0..4 with w0 + .. + wa <= x
+ * `state` is the input row j (not its env), `sample` is k, `step` is t.  No float appears anywhere.  The effective seed is s = seed + (seed_dev ? *seed_dev : 0)
+ * mod 2^64; seed_dev is a DEVICE word the kernel reads, so a captured graph draws new plans on every replay once the caller bumps the word.
+ * Sample k of state j plays the actions a(k, t) = action(draw(s, j, k, t), weights ? the six uint16 weights[(t * 6 + a) * M + j], a = 0..5 : NULL); weights is
+ * DEVICE uint16 [T][6][M], only read (a zero weight forbids its action at that step of that state; all six zero: uniform).  R(k) is cw_simulate's `ret` for
+ * state j along those actions with n_steps = T and stop_at_done = 1.  k* is the SMALLEST k with R(k) = max R; length, done, achieved, hdr and slot_pos are what
+ * cw_simulate returns for sample k*, hdr and slot_pos byte for byte. */
+typedef struct cw_shoot_out {   /* DEVICE pointers (host_outputs engines: or mapped host memory); NULL = not written; all NULL: CW_ERR_INVALID */
+    int32_t  *best_ret;     /* [M]     max over k of R(k)                                                   */
+    int32_t  *best_sample;  /* [M]     k*: the SMALLEST k that reaches it                                   */
+    uint8_t  *best_action;  /* [M]     the first action of sample k*                                        */
+    int32_t  *length;       /* [M]     of sample k*, as cw_simulate (stop_at_done = 1)                      */
+    uint8_t  *done;         /* [M]                                                                          */
+    uint16_t *achieved;     /* [M]                                                                          */
+    uint8_t  *hdr;          /* [M][16] record after k*'s last step taken, byte for byte cw_simulate's; 16-byte aligned */
+    uint16_t *slot_pos;     /* [M][8]  16-byte aligned                                                      */
+    uint8_t  *plan;         /* [T][M]  ALL T drawn actions of sample k*, step-major: feeds cw_simulate as it is */
+    int32_t  *ret;          /* [K][M]  R(k) of every sample (CEM's elite selection)                         */
+} cw_shoot_out;
+/* The inputs follow cw_plan's rules exactly.  hdr_in == NULL: the engine's CURRENT states, n_states == num_envs, slot_pos_in and env_of NULL.  Otherwise n_states
+ *   records of the caller's (hdr_in [M][16], slot_pos_in [M][8], both required, 16-byte aligned, only read); the env of state j is j % num_envs, or env_of[j]
+ *   (DEVICE int32 [M]): a negative entry takes no part and NO row of it is written, ret[k][j] and plan[t][j] included; an entry >= num_envs is SKIPPED: no row is
+ *   written either and counters[7] is incremented once per state.  No entry becomes an address without that check.
+ * 1 <= n_steps <= 32 767, 1 <= n_samples <= 65 536, and n_states * n_samples * n_steps <= 2^32: one launch on a shared card must stay short (65 536 states x
+ *   1 024 samples x 64 steps).  out->hdr / slot_pos / plan / ret must overlap neither the records read nor weights.
+ * PURE: nothing of the engine is written except counters[7]; nothing is drawn from any RNG stream of the engine.
+ * Enqueues ONE kernel (cw_shoot_kernel: G lanes per state, G a power of two <= 64 chosen so that a small batch spreads its samples over the wave, each lane
+ *   playing samples g, g + G, ... with the state in registers; the lanes reduce by shuffles and the winning lane writes its own record; no memory access inside
+ *   the step loop but the six weights a step, fetched a block ahead) on `stream` -- no host synchronisation, no allocation -- and can be captured into a HIP graph
+ *   with cw_step / cw_expand / cw_simulate / cw_plan.  Every obs_mode, with and without auto_reset, host_outputs engines included.  n_states == 0 (with hdr_in):
+ *   CW_OK, nothing enqueued.  CW_ERR_STATE before the first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID: a null engine or out, all ten fields NULL, n_states < 0
+ *   or above 2^27, n_steps < 1 or above 32 767, n_samples < 1 or above 65 536, the product above 2^32, hdr_in without slot_pos_in or the reverse, env_of without
+ *   hdr_in, n_states != num_envs without hdr_in, a misaligned hdr_in / slot_pos_in / out->hdr / out->slot_pos, an overlap as above.
+ *   (21x21, launch included, no goal in reach: 4 096 envs x 16 samples 23 us at 8 steps and 81 us at 64, against 114 / 131 us for torch.randint + cw_simulate + the reduction in torch; NOT faster than that route from 4 096 x 64 x 32 on and at 65 536 envs -- 63.8 against 25.5 ms at 65 536 x 1 024 x 64 -- because the lane rule fills the card with one wave per SIMD: tools/measure_shoot.py, profiles/r11_shoot.txt.) */
+int cw_shoot(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t n_steps, int32_t n_samples,
+             uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights, const cw_shoot_out *out, cw_stream_t stream);
+/* THE DECODER: out[t][r][j] = action(draw(s, j, samples ? samples[r * M + j] : r, t), weights as above), uint8 [T][n_rows][M] in device memory.  samples: DEVICE
+ * int32 [n_rows][M], only read; a NEGATIVE entry leaves that column of that row unwritten (cw_shoot's best_sample of a state that took no part, once the caller
+ * has filled it with -1).  samples == NULL with n_rows = K materialises the whole action tensor in cw_simulate's broadcast layout (the bridge to cw_simulate);
+ * samples = the elites' indices gives a CEM refit its elites' actions.  One grid-stride kernel (cw_shoot_actions_kernel), pure: the engine contributes only its
+ * stream bookkeeping and CW_ERR_STATE before the first cw_reset.  0 <= n_rows, n_states <= 2^27, 1 <= n_steps <= 32 767, n_rows * n_states * n_steps <= 2^32, else
+ * CW_ERR_INVALID, as for a null engine or out; n_states == 0 or n_rows == 0: CW_OK, nothing enqueued. */
+int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights,
+                     const int32_t *samples, int32_t n_rows, uint8_t *out /* [T][n_rows][M] */, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
