@@ -1,17 +1,15 @@
-"""What "a plan call did exactly what it should" means for cw_plan, in one place.  oracle_plan() is nothing but simulate_check.oracle_simulate(...,
-stop_at_done=True) over all 6^D action strings of every state, plus the reduction of craftingworld.h: q[a][j] = the largest return of a string that begins
-with a, the best plan = the lexicographically smallest string that reaches it, which is in canonical form (zeros behind its end).  check_plan() compares
-what a call wrote with that: EVERY written row against the oracle, every row that must not be written against the sentinel the test pre-filled, and the
-engine before and after the call (masked_check.take() snapshots): nothing may have changed but counters[7].  recipe() is the batch of states the tests
-share, built from the oracle alone, and coverage() counts what it exercises.  Pure CPU: numpy arrays in, no GPU.  A plain module, not a fixture;
-tests/test_plan_logic.py tests the comparison itself."""
+"""What "a plan call did exactly what it should" means for cw_plan: records_check.check_records_call with a row per (first action, state) and oracle_plan()
+as what to expect.  oracle_plan() is nothing but records_check.oracle_simulate(..., stop_at_done=True) over all 6^D action strings of every state, plus
+the reduction of craftingworld.h: q[a][j] = the largest return of a string that begins with a, the best plan = the lexicographically smallest string that
+reaches it, which is in canonical form (zeros behind its end).  recipe() is the batch of states the tests share, built from the oracle alone, and
+coverage() counts what it exercises.  Pure CPU: numpy arrays in, no GPU.  A plain module, not a fixture; tests/test_plan_logic.py tests the comparison
+itself."""
 import functools
 
 import numpy as np
 
-from expand_check import DENSE, POS_GONE, SKIPPED, decode, participation
-from oracle_replay import same
-from simulate_check import RECIPE_KW, oracle_simulate
+from records_check import DENSE, check_records_call, oracle_simulate, rows
+from simulate_check import RECIPE_KW
 
 FIELDS = ('q', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan')
 MAX_DEPTH = 8
@@ -24,7 +22,7 @@ def strings(depth):
 
 
 def oracle_plan(states, init_grids, depth, oracle_kw):
-    """M dense states (expand_check.decode()'s fields; init_grids uint8 [M, S, S]) -> dict of arrays [6, M, ...]: q, length, done, n_success (1: the best
+    """M dense states (records_check.decode()'s fields; init_grids uint8 [M, S, S]) -> dict of arrays [6, M, ...]: q, length, done, n_success (1: the best
     plan ends by success), ties (how many distinct TAKEN prefixes reach q: 2 or more = the tie rule decided), plan [6, D, M] and the dense final state of
     the best plan (grid, agent, hold, achieved, desired, step_num, flags).  Every one of the 6^D strings of every state goes through oracle_simulate with
     stop_at_done=True; numpy's argmax returns the FIRST maximum, which in lexicographic order is the smallest maximiser."""
@@ -50,82 +48,20 @@ def oracle_plan(states, init_grids, depth, oracle_kw):
     return out
 
 
+def layout(depth):
+    """{field: the shape in front of the M states}: a row per (first action, state), plan a row per (first action, step, state)"""
+    return {f: (6, depth) if f == 'plan' else (6,) for f in FIELDS}
+
+
 def check_plan(before, after, inputs, env_of, depth, outputs, sentinel, *, oracle_kw, expected=None):
-    """Pure CPU.  cw_plan ran between the snapshots `before` and `after` (masked_check.take()).  inputs: None (the engine's own states: before['hdr'] /
-    before['slot_pos']) or dict(hdr=[M, 16], slot_pos=[M, 8]), the records it read; env_of: None or the M entries it read; outputs: {field of FIELDS:
-    [6, M, ...], plan [6, D, M]} what the call left in the buffers it was given; sentinel: the byte every one of them was filled with before the call.
-    EVERY row (a, j) of a state that takes part: q, length, done, achieved_mask, plan and the decoded final record (grid, agent, hold, both masks, step_num,
-    flags, the slot marked held; the menu byte as in the input) equal oracle_plan of input state j with the start state of its env.  Every row of a state
-    that takes no part (negative entry) or is skipped (entry >= num_envs), plan rows included: sentinel bytes.  The engine: `after` equals `before`
-    everywhere, counters[7] == before + the skipped states.  ValueError when no row would be compared with the oracle.
+    """Pure CPU.  cw_plan ran between the snapshots `before` and `after` (masked_check.take()); inputs, env_of, outputs ({field of FIELDS: [6, M, ...],
+    plan [6, D, M]}), sentinel and what is compared: records_check.check_records_call.  Row (a, j) of a state that takes part, its plan rows included,
+    equals oracle_plan of input state j with the start state of its env.
     expected: (dense states, oracle_plan of them) a test has computed already for the states that take part, in order: the records the call read must then
     decode to exactly these states, and the oracle is not run again.  -> (states that took part, states skipped)."""
-    if set(before) != set(after):
-        raise ValueError('the snapshots hold different entries: %s' % sorted(set(before) ^ set(after)))
-    if not outputs or set(outputs) - set(FIELDS):
-        raise ValueError('outputs must hold some of %s' % (FIELDS,))
-    N, S = len(before['rng_pos']), before['state_grid'].shape[1]
-    if inputs is None:
-        if env_of is not None:
-            raise ValueError('env_of goes with caller-supplied records')
-        inputs = dict(hdr=before['hdr'], slot_pos=before['slot_pos'])
-    states = decode(inputs['hdr'], inputs['slot_pos'], S)
-    M = len(states['hold'])
-    env, skipped = participation(env_of, M, N)
-    part, rest = np.flatnonzero(env >= 0), np.flatnonzero(env < 0)
-    if len(part) == 0:
-        raise ValueError('no state takes part: nothing would be compared with the oracle')
-    for f, got in outputs.items():
-        if np.shape(got)[:3 if f == 'plan' else 2] != ((6, depth, M) if f == 'plan' else (6, M)):
-            raise ValueError('%s has shape %s for D = %d, M = %d' % (f, np.shape(got), depth, M))
-    sub = {k: v[part] for k, v in states.items()}
-    if expected is None:
-        want = oracle_plan(sub, before['state_init_grid'][env[part]], depth, oracle_kw)
-    else:
-        mine, want = expected
-        for k in DENSE:
-            same('the records the call read: ' + k, part, sub[k], np.asarray(mine[k]))
-    for a in range(6):
-        tag = 'first action %d: ' % a
-        for f, k in (('q', 'q'), ('length', 'length'), ('done', 'done'), ('achieved_mask', 'achieved')):
-            if f in outputs:
-                got = np.asarray(outputs[f])[a, part]
-                got = got.view(np.uint16) if f == 'achieved_mask' and got.dtype == np.int16 else got
-                same(tag + f, part, got.astype(np.int64), want[k][a].astype(np.int64))
-        if 'plan' in outputs:
-            got = np.asarray(outputs['plan'])
-            for t in range(depth):
-                same(tag + 'plan, step %d' % t, part, got[a, t, part].astype(np.int64), want['plan'][a, t])
-        if 'hdr' in outputs and 'slot_pos' in outputs:
-            got = decode(np.asarray(outputs['hdr'])[a, part], np.asarray(outputs['slot_pos'])[a, part], S)
-            for k in DENSE:
-                same(tag + 'final ' + k, part, got[k], want[k][a])
-            same(tag + 'final record: the slot marked held', part, got['held_code'], want['hold'][a])
-            same(tag + 'final menu byte', part, got['menu'], sub['menu'])
-        elif 'hdr' in outputs:                  # (without the slots: the header's own fields)
-            got = decode(np.asarray(outputs['hdr'])[a, part], np.full((len(part), 8), POS_GONE, np.uint16), S)
-            for k in ('agent', 'hold', 'achieved', 'desired', 'step_num', 'flags'):
-                same(tag + 'final ' + k, part, got[k], want[k][a])
-            same(tag + 'final menu byte', part, got['menu'], sub['menu'])
-        elif 'slot_pos' in outputs:             # (without the codes: where the objects are)
-            p = np.asarray(outputs['slot_pos'])[a, part].reshape(len(part), 8).view(np.uint16)
-            occ = np.zeros((len(part), S * S + 1), bool)
-            occ[np.arange(len(part))[:, None], np.minimum(p.astype(np.int64), S * S)] = True
-            same(tag + 'final occupied cells', part, occ[:, :S * S].reshape(-1, S, S), want['grid'][a] != 0)
-        for f, got in outputs.items():
-            g = np.asarray(got)
-            for t in (range(depth) if f == 'plan' else (None,)):
-                rows = g[a, rest] if t is None else g[a, t, rest]
-                raw = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rest), g.dtype.itemsize * int(np.prod(rows.shape[1:], dtype=np.int64)))
-                same(tag + f + (' of the rows' if t is None else ', step %d, of the rows' % t) + ' that must not be written', rest, raw, np.full_like(raw, sentinel))
-    for k in sorted(before):
-        if k == 'counters':
-            w = before[k].copy()
-            w[SKIPPED] += skipped
-            assert np.array_equal(after[k], w), 'counters after a plan with %d skipped states: %s, expected %s' % (skipped, after[k].tolist(), w.tolist())
-        else:
-            same('after a plan: ' + k, 0, after[k], before[k])
-    return len(part), skipped
+    def expect(states, env, part):
+        return expected or (None, oracle_plan(rows(states, part), before['state_init_grid'][env[part]], depth, oracle_kw))
+    return check_records_call(before, after, inputs, env_of, outputs, sentinel, name='cw_plan', layout=layout(depth), expect=expect)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the shared batch of states

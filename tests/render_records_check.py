@@ -5,7 +5,7 @@ every byte before and after the array against the sentinel the test pre-filled. 
 tests/test_render_records_logic.py tests the comparison itself."""
 import numpy as np
 
-from expand_check import encode
+from records_check import encode
 from state_tables import oracle_frame
 
 CW_WAVE, WAVES_PER_BLOCK = 64, 4
@@ -26,7 +26,7 @@ def records_launch(n_states, n_cu):
 
 
 def dense_of(states):
-    """painted_states()-style tuples (name, grid, init_grid, agent, hold) -> the dense fields expand_check.encode takes (the masks and counters of a record
+    """painted_states()-style tuples (name, grid, init_grid, agent, hold) -> the dense fields records_check.encode takes (the masks and counters of a record
     do not matter to a painter: fixed values)"""
     n = len(states)
     z = np.zeros(n, np.int64)

@@ -1,17 +1,15 @@
-"""What "a shoot call did exactly what it should" means for cw_shoot, in one place.  draw() / action() are the numpy model of the draw function, written
-from the text of include/craftingworld.h (uint64 arithmetic masked to 32 bits); model_actions() is the action tensor the kernel never materialises;
-expected_shoot() sends those actions through simulate_check.oracle_simulate(..., stop_at_done=True) and reduces by the header's rule: the largest return,
-the SMALLEST sample that reaches it.  check_shoot() compares what a call wrote with that: EVERY written row against the oracle, `plan` against the model,
-every row that must not be written against the sentinel the test pre-filled, and the engine before and after the call (masked_check.take() snapshots):
-nothing may have changed but counters[7], up by the skipped states.  coverage() counts what a batch exercises.  Pure CPU: numpy arrays in, no GPU.  A plain
-module, not a fixture; tests/test_shoot_logic.py tests the model and the comparison themselves."""
+"""What "a shoot call did exactly what it should" means for cw_shoot: records_check.check_records_call with a row per state, plan a row per step, ret a
+row per sample, and expected_shoot() as what to expect.  draw() / action() are the numpy model of the draw function, written from the text of
+include/craftingworld.h (uint64 arithmetic masked to 32 bits); model_actions() is the action tensor the kernel never materialises; expected_shoot() sends
+those actions through records_check.oracle_simulate(..., stop_at_done=True) and reduces by the header's rule: the largest return, the SMALLEST sample that
+reaches it.  `plan` is compared against the model.  coverage() counts what a batch exercises.  Pure CPU: numpy arrays in, no GPU.  A plain module, not a
+fixture; tests/test_shoot_logic.py tests the model and the comparison themselves."""
 import functools
 
 import numpy as np
 
-from expand_check import DENSE, POS_GONE, SKIPPED, decode, participation
-from oracle_replay import same
-from simulate_check import RECIPE_KW, oracle_simulate, recipe
+from records_check import DENSE, check_records_call, oracle_simulate, rows
+from simulate_check import RECIPE_KW, recipe
 
 FIELDS = ('best_ret', 'best_sample', 'best_action', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'ret')
 M32 = np.uint64(0xFFFFFFFF)
@@ -67,7 +65,7 @@ def model_actions(seed, M, K, T, weights=None, samples=None):
 
 
 def expected_shoot(dense, init_grids, T, K, seed, oracle_kw, weights=None):
-    """M dense states (expand_check.decode()'s fields; init_grids uint8 [M, S, S]) -> dict: actions [T, K, M] (the model's), ret [K, M] (oracle_simulate's
+    """M dense states (records_check.decode()'s fields; init_grids uint8 [M, S, S]) -> dict: actions [T, K, M] (the model's), ret [K, M] (oracle_simulate's
     `ret` of every sample with stop_at_done=True), best_ret, best_sample (numpy's argmax returns the FIRST maximum: the smallest sample), best_action, length,
     done, n_success (1: the best sample ends by success), ties (how many samples reach best_ret) [M], plan [T, M] (all T drawn actions of the best sample)
     and the dense final state of the best sample (grid, agent, hold, achieved, desired, step_num, flags)."""
@@ -86,90 +84,25 @@ def expected_shoot(dense, init_grids, T, K, seed, oracle_kw, weights=None):
     return out
 
 
+def layout(T, K):
+    """{field: the shape in front of the M states}: a row per state, plan a row per (step, state), ret a row per (sample, state)"""
+    return dict({f: () for f in FIELDS}, plan=(T,), ret=(K,))
+
+
 def check_shoot(before, after, inputs, env_of, T, K, seed, weights, outputs, sentinel, *, oracle_kw, expected=None):
-    """Pure CPU.  cw_shoot ran between the snapshots `before` and `after` (masked_check.take()).  inputs: None (the engine's own states: before['hdr'] /
-    before['slot_pos']) or dict(hdr=[M, 16], slot_pos=[M, 8]), the records it read; env_of: None or the M entries it read; T, K, seed (the EFFECTIVE seed, a
-    Python int) and weights (None or [T, 6, M]) as the call had them; outputs: {field of FIELDS: [M, ...], plan [T, M], ret [K, M]} what the call left in the
-    buffers it was given; sentinel: the byte every one of them was filled with before the call.
-    EVERY row of a state j that takes part: best_ret, best_sample, best_action, length, done, achieved_mask, ret[:, j] and the decoded final record (grid,
-    agent, hold, both masks, step_num, flags, the slot marked held; the menu byte as in the input) equal expected_shoot of input state j -- ROW j, whatever
-    its env -- with the start state of its env; plan[:, j] equals the model's actions of sample best_sample, all T of them.  Every row of a state that takes
-    no part (negative entry) or is skipped (entry >= num_envs), ret and plan columns included: sentinel bytes.  The engine: `after` equals `before` everywhere,
-    counters[7] == before + the skipped states.  ValueError when no row would be compared with the oracle.
+    """Pure CPU.  cw_shoot ran between the snapshots `before` and `after` (masked_check.take()); inputs, env_of, outputs ({field of FIELDS: [M, ...], plan
+    [T, M], ret [K, M]}), sentinel and what is compared: records_check.check_records_call.  T, K, seed (the EFFECTIVE seed, a Python int) and weights
+    (None or [T, 6, M]) as the call had them.  Every row of a state j that takes part, ret[:, j] included, equals expected_shoot of input state j -- ROW j,
+    whatever its env -- with the start state of its env; plan[:, j] equals the model's actions of sample best_sample, all T of them.
     expected: (dense states, expected_shoot of them) a test has computed already for ALL M input states in order (the draw is keyed by the row): the records
     the call read must then decode to exactly these states, and the oracle is not run again.  -> (states that took part, states skipped)."""
-    if set(before) != set(after):
-        raise ValueError('the snapshots hold different entries: %s' % sorted(set(before) ^ set(after)))
-    if not outputs or set(outputs) - set(FIELDS):
-        raise ValueError('outputs must hold some of %s' % (FIELDS,))
-    N, S = len(before['rng_pos']), before['state_grid'].shape[1]
-    if inputs is None:
-        if env_of is not None:
-            raise ValueError('env_of goes with caller-supplied records')
-        inputs = dict(hdr=before['hdr'], slot_pos=before['slot_pos'])
-    states = decode(inputs['hdr'], inputs['slot_pos'], S)
-    M = len(states['hold'])
-    env, skipped = participation(env_of, M, N)
-    part, rest = np.flatnonzero(env >= 0), np.flatnonzero(env < 0)
-    if len(part) == 0:
-        raise ValueError('no state takes part: nothing would be compared with the oracle')
-    lead = {'plan': (T, M), 'ret': (K, M)}
-    for f, got in outputs.items():
-        if np.shape(got)[:len(lead.get(f, (M,)))] != lead.get(f, (M,)):
-            raise ValueError('%s has shape %s for T = %d, K = %d, M = %d' % (f, np.shape(got), T, K, M))
-    if expected is None:
+    def expect(states, env, part):
         # the draw is keyed by the ROW: the states that take no part are simulated too (with env 0's start state) and never compared
-        want = expected_shoot(states, before['state_init_grid'][np.maximum(env, 0)], T, K, seed, oracle_kw, weights)
-    else:
-        mine, want = expected
-        for k in DENSE:
-            same('the records the call read: ' + k, part, states[k][part], np.asarray(mine[k])[part])
-    sub = {k: v[part] for k, v in states.items()}
-    for f, k in (('best_ret', 'best_ret'), ('best_sample', 'best_sample'), ('best_action', 'best_action'), ('length', 'length'), ('done', 'done'),
-                 ('achieved_mask', 'achieved')):
-        if f in outputs:
-            got = np.asarray(outputs[f])[part]
-            got = got.view(np.uint16) if f == 'achieved_mask' and got.dtype == np.int16 else got
-            same(f, part, got.astype(np.int64), want[k][part].astype(np.int64))
-    if 'ret' in outputs:
-        got = np.asarray(outputs['ret'])
-        for k in range(K):
-            same('ret of sample %d' % k, part, got[k, part].astype(np.int64), want['ret'][k, part])
-    if 'plan' in outputs:
-        got = np.asarray(outputs['plan'])
-        model = model_actions(seed, M, K, T, weights, samples=want['best_sample'][None])[:, 0]
-        for t in range(T):
-            same('plan, step %d' % t, part, got[t, part].astype(np.int64), model[t, part])
-    if 'hdr' in outputs and 'slot_pos' in outputs:
-        got = decode(np.asarray(outputs['hdr'])[part], np.asarray(outputs['slot_pos'])[part], S)
-        for k in DENSE:
-            same('final ' + k, part, got[k], want[k][part])
-        same('final record: the slot marked held', part, got['held_code'], want['hold'][part])
-        same('final menu byte', part, got['menu'], sub['menu'])
-    elif 'hdr' in outputs:                      # (without the slots: the header's own fields)
-        got = decode(np.asarray(outputs['hdr'])[part], np.full((len(part), 8), POS_GONE, np.uint16), S)
-        for k in ('agent', 'hold', 'achieved', 'desired', 'step_num', 'flags'):
-            same('final ' + k, part, got[k], want[k][part])
-        same('final menu byte', part, got['menu'], sub['menu'])
-    elif 'slot_pos' in outputs:                 # (without the codes: where the objects are)
-        p = np.asarray(outputs['slot_pos'])[part].reshape(len(part), 8).view(np.uint16)
-        occ = np.zeros((len(part), S * S + 1), bool)
-        occ[np.arange(len(part))[:, None], np.minimum(p.astype(np.int64), S * S)] = True
-        same('final occupied cells', part, occ[:, :S * S].reshape(-1, S, S), want['grid'][part] != 0)
-    for f, got in outputs.items():
-        g = np.asarray(got)
-        for t in (range(g.shape[0]) if f in lead else (None,)):
-            rows = g[rest] if t is None else g[t, rest]
-            raw = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rest), g.dtype.itemsize * int(np.prod(rows.shape[1:], dtype=np.int64)))
-            same(f + (' of the rows' if t is None else ', row %d, of the columns' % t) + ' that must not be written', rest, raw, np.full_like(raw, sentinel))
-    for k in sorted(before):
-        if k == 'counters':
-            w = before[k].copy()
-            w[SKIPPED] += skipped
-            assert np.array_equal(after[k], w), 'counters after a shoot with %d skipped states: %s, expected %s' % (skipped, after[k].tolist(), w.tolist())
-        else:
-            same('after a shoot: ' + k, 0, after[k], before[k])
-    return len(part), skipped
+        mine, want = expected or (None, expected_shoot(states, before['state_init_grid'][np.maximum(env, 0)], T, K, seed, oracle_kw, weights))
+        want = dict(want, plan=model_actions(seed, len(env), K, T, weights, samples=want['best_sample'][None])[:, 0])
+        cut = {f: want[f][..., part] for f in ('best_ret', 'best_sample', 'best_action', 'length', 'done', 'plan', 'ret')}
+        return mine and rows({k: mine[k] for k in DENSE}, part), dict(cut, **rows({k: want[k] for k in DENSE}, part))
+    return check_records_call(before, after, inputs, env_of, outputs, sentinel, name='cw_shoot', layout=layout(T, K), expect=expect)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the shared batch of states

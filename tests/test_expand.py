@@ -10,35 +10,23 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import DENSE, FIELDS, POS_HELD, check_expand, decode, oracle_successors
+from engines import ENGINES, K5, N1, SIZES, k_of, n_cu
+from expand_check import FIELDS, LAYOUT, check_expand, oracle_successors
 from masked_check import spread, take
 from oracle_replay import make_env, np_states, one_hot_of, same
+from records_check import DENSE, POS_HELD, decode
+from records_gpu import SENT, caller_records, env_of_cases, host as _host, sentinel_out, walked_engine
 from state_tables import oracle_frame as _oracle_frame, table_coverage, table_desired, wall_table
-from test_masked_shapes import _n_cu
-from test_snapshot import ENGINES, K5, N1, SIZES, k_of
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-INT32_MAX = 2 ** 31 - 1
 _WIDTH = {'reward': 4, 'done': 1, 'changed': 1, 'achieved_mask': 2, 'hdr': 16, 'slot_pos': 16}
 _DTYPE = {'reward': torch.int32, 'done': torch.bool, 'changed': torch.bool, 'achieved_mask': torch.int16, 'hdr': torch.uint8, 'slot_pos': torch.int16}
 
 
-def _sentinel_out(M, fields=FIELDS):
+def _sentinel_out(M):
     """output buffers as expand(out=...) takes them, every byte SENT"""
-    out = {}
-    for f in fields:
-        raw = torch.full((6, M, _WIDTH[f]), SENT, dtype=torch.uint8, device='cuda')
-        t = raw.view(_DTYPE[f])
-        out[f] = t if f == 'hdr' or f == 'slot_pos' else t.squeeze(-1)
-        assert out[f].is_contiguous() and out[f].shape[:2] == (6, M)
-    return out
-
-
-def _host(r):
-    """an expand() result as numpy, done / changed as the bytes the kernel wrote"""
-    return {f: (t.view(torch.uint8) if t.dtype is torch.bool else t).cpu().numpy() for f, t in r.items()}
+    return sentinel_out(LAYOUT, _WIDTH, _DTYPE, M)
 
 
 def _dense_of(snap):
@@ -219,7 +207,7 @@ def test_the_far_corner_table_on_large_grids(S):
         assert torch.equal(host[f], r2[f]), f
     del r2, host, h2
     # ---- the one-hot view of the successors of Up and Right: more than one round of the export's grid-stride loop
-    assert 2 * n * S * S > _n_cu() * 32 * 256
+    assert 2 * n * S * S > n_cu() * 32 * 256
     oh = env.one_hot_states(r1['hdr'][:2], r1['slot_pos'][:2])
     assert tuple(oh.shape) == (2, n, S, S, 12)
     for a in range(2):
@@ -305,22 +293,9 @@ def test_host_outputs_engine():
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ 3. shapes and edges
-def _env_of(M, N):
-    """M entries: random envs (repeats), and from 63 states on -1, -7, N, N + 31 and INT32_MAX, the wave's last lane among their places"""
-    e = np.random.RandomState(M).randint(0, N, M).astype(np.int64)
-    if M >= 63:
-        e[[3, 17, 31, 40, 62]] = [-1, N, -7, N + 31, INT32_MAX]
-        e[5] = e[6] = e[7]
-    if M >= 257:
-        e[[63, 64, 128, 255, 256]] = [N, -1, INT32_MAX, N + 31, N]
-    return e
-
-
 @pytest.fixture(scope='module')
 def engine70():
-    env, _, _ = make_env(N1, *np_states(N1, 54000), obs_mode='state', auto_reset=False, **K5)
-    env.reset()
-    spread(env, 9, 3)
+    env = walked_engine(54000, 9)
     yield env
     env.close()
 
@@ -330,13 +305,10 @@ def test_shapes_and_edges(engine70, M):
     """M states taken from a 70-env engine, env_of on the device and handed over in place: every written and every unwritten row, and the skipped states
     counted once each -- not once per action"""
     env = engine70
-    e = _env_of(M, N1)
+    e = env_of_cases(M, N1)
     src = np.where((e >= 0) & (e < N1), e, 0)
     before = take(env)
-    hdr = before['hdr'][src].copy()
-    hdr[:, 8] = (hdr[:, 8] + np.arange(M)) % K5['max_steps']                      # records of the caller's: other step counts than the envs' own
-    hdr[:, 3] = np.arange(M) % 5                                                  # ... and menu bytes, which a successor keeps
-    pos = before['slot_pos'][src].copy()
+    hdr, pos = caller_records(before, e, M, N1, K5['max_steps'])
     t_hdr, t_pos, t_env = torch.as_tensor(hdr, device='cuda'), torch.as_tensor(pos, device='cuda'), torch.as_tensor(e.astype(np.int32), device='cuda')
     out = _sentinel_out(M)
     skipped0 = env.expand_skipped
@@ -478,7 +450,7 @@ def test_grid_and_one_hot_exports_past_their_first_round():
     3 envs more than one round holds, the second trip of the loop writes the last envs.  grid() and one_hot() of the current, goal and init state
     against get_state()."""
     S = 255
-    per_round = _n_cu() * 32 * 256
+    per_round = n_cu() * 32 * 256
     N = -(-per_round // (S * S)) + 3
     assert N * S * S > per_round and (N - 3) * S * S >= per_round                  # (the last three envs lie wholly in the second round)
     env, _, _ = make_env(N, *np_states(N, 57000), obs_mode='state', size=(S, S), max_steps=17)

@@ -1,32 +1,14 @@
-"""CPU tier: the checker of the expand tests (tests/expand_check.py) itself.  The outputs a correct cw_expand would leave are synthesised on the CPU -- the
+"""CPU tier: the checker of the expand tests (expand_check.py over records_check.py) itself.  The outputs a correct cw_expand would leave are synthesised on the CPU -- the
 oracle's successors, encoded into packed records by the test-side encoder -- and must pass; each planted fault must be caught."""
 import numpy as np
 import pytest
 
-from expand_check import POS_GONE, POS_HELD, check_expand, decode, encode, oracle_successors
+from expand_check import check_expand, oracle_successors
+from records_check import POS_GONE, POS_HELD, decode, encode
+from records_fixtures import ENV_OF, M, N, S, SENT, snap, world as _world
 
-N, S, MAX_STEPS, SENT = 5, 5, 9, 0xA5
+MAX_STEPS = 9
 OKW = dict(size=(S, S), max_steps=MAX_STEPS)
-ENV_OF = np.array([0, 4, -1, 2, 2, 7, 1, -7, 3, 5 + 31, 0, 2 ** 31 - 1], np.int64)       # 12 states: 7 take part (env 2 and 0 twice), 2 take none, 3 are skipped
-M = len(ENV_OF)
-
-
-def _world():
-    """N oracle envs some steps into their episodes -> (dense states [N], their init grids)"""
-    from oracle import OracleEnv
-    rng = np.random.RandomState(5)
-    st = []
-    for i in range(N):
-        o = OracleEnv(**OKW)
-        o.seed_int(100 + i)
-        o.reset()
-        for a in rng.randint(0, 6, 4 + i):
-            o.step(int(a))
-        st.append(o.state())
-    dense = dict(grid=np.stack([s['grid'] for s in st]), agent=np.array([s['agent'] for s in st]), hold=np.array([s['hold'] for s in st]),
-                 achieved=np.array([s['achieved'] for s in st]), desired=np.array([s['desired'] for s in st]),
-                 step_num=np.array([min(s['step_num'], MAX_STEPS - 2) for s in st]), flags=np.array([2 * (i % 2) for i in range(N)]))
-    return dense, np.stack([s['init_grid'] for s in st])
 
 
 @pytest.fixture(scope='module')
@@ -34,18 +16,9 @@ def world():
     return _world()
 
 
-def _snap(dense, init_grids):
-    """a take()-shaped snapshot of the N envs (what check_expand reads of it, and some buffers it must find unchanged)"""
-    hdr, pos = encode(dense, menu=3)
-    r = np.random.RandomState(2)
-    return dict(state_grid=dense['grid'].copy(), state_init_grid=init_grids.copy(), rng_pos=r.randint(1, 625, N).astype(np.int32),
-                rng_key=r.randint(0, 2 ** 31, (N, 624)).astype(np.uint32), hdr=hdr, slot_pos=pos.view(np.int16), reward=np.full(N, -1, np.int32),
-                done=np.zeros(N, bool), counters=np.arange(8, dtype=np.int64) * 11)
-
-
 def _correct(dense, init_grids, env_of):
     """what a correct call leaves: (inputs, outputs, after-snapshot) for the M states ENV_OF picks (env_of None: the engine's own states)"""
-    before = _snap(dense, init_grids)
+    before = snap(dense, init_grids)
     if env_of is None:
         env, inputs, sub = np.arange(N), None, dense
         menu = np.full(N, 3)
@@ -99,6 +72,33 @@ def test_oracle_successors_are_steps_of_the_oracle(world):
         assert np.array_equal(suc['changed'][a], (d != 0).any(axis=1))
     assert np.array_equal(suc['changed'][4], suc['hold'][4] != dense['hold']) and np.array_equal(suc['changed'][5], suc['hold'][5] != dense['hold'])
     assert suc['changed'].any() and not suc['changed'].all() and set(np.unique(suc['reward'])) <= {-1, MAX_STEPS}
+
+
+def test_oracle_successors_against_the_oracles_own_wrappers(world):
+    """one action at a time by OracleEnv.set_state + .step, under each state's own reward rule: every field, `changed` and the flags word worked by hand --
+    oracle_successors is pinned to the oracle, not to oracle_simulate"""
+    from oracle import OracleEnv
+    dense, init_grids = world
+    dense = dict(dense, flags=dense['flags'] | 1 | (np.arange(N) * 4), desired=np.where(np.arange(N) % 2, dense['desired'], 0))   # (an empty goal pays at once)
+    suc = oracle_successors(dense, init_grids, OKW)
+    assert (suc['reward'] == MAX_STEPS).any() and (suc['reward'] == -1).any()
+    for j in range(N):
+        o = OracleEnv(reward_style='subset' if dense['flags'][j] & 2 else None, **OKW)
+        for a in range(6):
+            o.set_state(dense['grid'][j], init_grids[j], dense['agent'][j], dense['hold'][j], dense['achieved'][j], dense['desired'][j], dense['step_num'][j])
+            _, r, d, _ = o.step(a)
+            s = o.state()
+            assert (suc['reward'][a, j], suc['done'][a, j]) == (r, d)
+            assert np.array_equal(suc['grid'][a, j], s['grid']) and tuple(suc['agent'][a, j]) == tuple(s['agent'])
+            assert (suc['hold'][a, j], suc['achieved'][a, j], suc['desired'][a, j], suc['step_num'][a, j]) == (s['hold'], s['achieved'], s['desired'], s['step_num'])
+            moved = not np.array_equal(s['grid'], dense['grid'][j]) or tuple(s['agent']) != tuple(dense['agent'][j]) or s['hold'] != dense['hold'][j]
+            assert suc['changed'][a, j] == moved
+            assert suc['flags'][a, j] == (dense['flags'][j] & 2) | (((dense['flags'][j] >> 2) + (r == MAX_STEPS)) << 2)
+    assert {k: (v.shape, v.dtype) for k, v in suc.items()} == dict(
+        reward=((6, N), np.int64), done=((6, N), bool), changed=((6, N), bool), grid=((6, N, S, S), np.uint8), agent=((6, N, 2), np.int64),
+        hold=((6, N), np.int64), achieved=((6, N), np.int64), desired=((6, N), np.int64), step_num=((6, N), np.int64), flags=((6, N), np.int64))
+    top = oracle_successors(dict(dense, flags=np.full(N, 0x3FFF << 2)), init_grids, OKW)['flags']      # (the count saturates)
+    assert (top == 0x3FFF << 2).all()
 
 
 @pytest.mark.parametrize('own', [True, False])

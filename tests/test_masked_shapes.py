@@ -11,12 +11,12 @@ import pytest
 import torch
 
 import imagine_model as M
+from engines import K5, n_cu
 from masked_check import check_masked_call, masked_launch, model_imagine, spread, take, untouched
 from oracle_replay import assert_counters, make_env, np_states, oracle_kw, replay_against_oracle, same, same_states
 
 pytestmark = pytest.mark.gpu
 
-K5 = dict(size=(5, 5), max_steps=17)
 # width -> (epb, N from most = n_cu workgroups, chunks); on 256 CUs: N = 509, 2 053, 4 099, 8 209, 16 411 and 20 011 (313 chunks on 256 workgroups)
 WIDTHS = {'epb4': (4, lambda most: 2 * most - 3, lambda most: (2 * most) // 4),
           'epb8': (8, lambda most: 8 * most + 5, lambda most: most + 1),
@@ -27,13 +27,9 @@ WIDTHS = {'epb4': (4, lambda most: 2 * most - 3, lambda most: (2 * most) // 4),
 ALL_WIDTHS = list(WIDTHS)
 
 
-def _n_cu():
-    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-
-
 def _width(width):
     """-> (N, epb, chunks) of a width case on this card, asserted against the launch rule"""
-    most = _n_cu()
+    most = n_cu()
     epb, n_of, chunks_of = WIDTHS[width]
     N, chunks = n_of(most), chunks_of(most)
     assert masked_launch(N, most, 1) == (epb, chunks, min(chunks, most)), (width, most, N, masked_launch(N, most, 1))
@@ -315,7 +311,7 @@ def test_tiny_and_boundary_batches(monkeypatch, N):
     """default tuning (epb = 4), 4x4: reset_envs(all ones) against reset() of a twin, one selected env through reset (oracle), imagine and sample (model),
     and every env through imagine (own masks, then desired given) and sample"""
     from oracle import OracleBatch
-    assert masked_launch(N, _n_cu())[0] == 4
+    assert masked_launch(N, n_cu())[0] == 4
     kw = dict(size=(4, 4), max_steps=9)
     env, keys, pos = _engine(monkeypatch, N, blocks=None, obs_mode='state', auto_reset=False, **kw)
     twin, _, _ = _engine(monkeypatch, N, blocks=None, obs_mode='state', auto_reset=False, **kw)

@@ -6,42 +6,28 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import POS_HELD, encode
+from engines import ENGINES, K5, N1, k_of
 from masked_check import spread, take
 from oracle_replay import make_env, np_states
-from plan_check import FIELDS, RECIPE_KW, RECIPE_N, RECIPE_PART, assert_recipe_coverage, check_plan, coverage, recipe, recipe_plans
+from plan_check import FIELDS, RECIPE_KW, RECIPE_N, RECIPE_PART, assert_recipe_coverage, check_plan, coverage, layout, recipe, recipe_plans
+from records_check import POS_HELD, encode
+from records_gpu import SENT, caller_records, dev as _dev, env_of_cases as _env_of, host, sentinel_out, walk_goals as _walk_goals, walked_engine
 from state_tables import painted_batch, wall_table
-from test_expand import _env_of
-from test_snapshot import ENGINES, K5, N1, k_of
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
 _WIDTH = dict(q=4, length=4, done=1, achieved_mask=2, hdr=16, slot_pos=16, plan=1)
 _DTYPE = dict(q=torch.int32, length=torch.int32, done=torch.bool, achieved_mask=torch.int16, hdr=torch.uint8, slot_pos=torch.int16, plan=torch.uint8)
 PER_PLAN = ('length', 'done', 'achieved_mask', 'hdr', 'slot_pos')      # what simulate() returns for a plan besides its return
 
 
-def _sentinel_out(D, M, fields=FIELDS):
+def _sentinel_out(D, M):
     """output buffers as plan(out=...) takes them, every byte SENT"""
-    out = {}
-    for f in fields:
-        if f == 'plan':
-            out[f] = torch.full((6, D, M), SENT, dtype=torch.uint8, device='cuda')
-            continue
-        t = torch.full((6, M, _WIDTH[f]), SENT, dtype=torch.uint8, device='cuda').view(_DTYPE[f])
-        out[f] = t if f == 'hdr' or f == 'slot_pos' else t.squeeze(-1)
-        assert out[f].is_contiguous() and tuple(out[f].shape[:2]) == (6, M)
-    return out
+    return sentinel_out(layout(D), _WIDTH, _DTYPE, M)
 
 
 def _host(r):
-    """a plan() result as numpy, done as the bytes the kernel wrote"""
-    return {f: (t.view(torch.uint8) if t.dtype is torch.bool else t).cpu().numpy() for f, t in r.items() if f in FIELDS}
-
-
-def _dev(a, dtype=np.uint8):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device='cuda')
+    return host(r, FIELDS)
 
 
 def _enumerated(env, D, hdr, pos, env_of=None):
@@ -63,15 +49,6 @@ def _enumerated(env, D, hdr, pos, env_of=None):
     plan = torch.stack([(first // 6 ** (D - 1 - t)) % 6 for t in range(D)], dim=1)
     out['plan'] = torch.where(torch.arange(D, device='cuda')[None, :, None] < out['length'][:, None, :], plan, 0).to(torch.uint8)
     return out
-
-
-def _walk_goals(env, steps, seed, every=2):
-    """desired of every `every`-th env := the achieved mask it reaches after `steps` steps of a random walk (simulate(), no env touched): goals within reach"""
-    walk = _dev(np.random.RandomState(seed).randint(0, 6, (steps, env.num_envs)))
-    reached = env.simulate(walk, stop_at_done=False)['achieved_mask'].cpu().numpy().view(np.uint16)
-    des = env.get_state()['desired'].astype(np.uint16)
-    des[::every] = reached[::every]
-    env.set_state(desired=des)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ 1. the shared recipe
@@ -245,20 +222,13 @@ def test_following_best_action_reaches_the_goal_on_the_planned_step():
 # ------------------------------------------------------------------------------------------------------------------------------ 5. env_of
 @pytest.fixture(scope='module')
 def engine70():
-    env, _, _ = make_env(N1, *np_states(N1, 87000), obs_mode='state', auto_reset=False, **K5)
-    env.reset()
-    spread(env, 9, 3)
-    _walk_goals(env, 2, 88)
+    env = walked_engine(87000, 9, goals=(2, 88))
     yield env
     env.close()
 
 
 def _records(before, e, M):
-    src = np.where((e >= 0) & (e < N1), e, 0)
-    hdr = before['hdr'][src].copy()
-    hdr[:, 8] = (hdr[:, 8] + np.arange(M)) % K5['max_steps']                      # records of the caller's: other step counts than the envs' own
-    hdr[:, 3] = np.arange(M) % 5                                                  # ... and menu bytes, which a plan keeps
-    return hdr, before['slot_pos'][src].copy()
+    return caller_records(before, e, M, N1, K5['max_steps'])
 
 
 @pytest.mark.parametrize('M,D', [(63, 3), (65, 2), (257, 2), (1000, 1)])

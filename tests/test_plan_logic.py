@@ -1,20 +1,17 @@
-"""CPU tier: the checker of the plan tests (tests/plan_check.py) itself.  The outputs a correct cw_plan would leave are synthesised on the CPU -- the
+"""CPU tier: the checker of the plan tests (tests/plan_check.py over records_check.py) itself.  The outputs a correct cw_plan would leave are synthesised on the CPU -- the
 oracle's enumeration, reduced, encoded into packed records by the test-side encoder -- and must pass; each planted fault must be caught.  Also here: what
 the shared batch of states (plan_check.recipe) exercises, counted from the oracle alone."""
 import numpy as np
 import pytest
 
-from expand_check import DENSE, encode
 from gym_craftingworld_amd.vec_env import PLAN_FIELDS
 from plan_check import (COVERAGE_MIN, FIELDS, RECIPE_KW, RECIPE_N, RECIPE_PART, assert_recipe_coverage, check_plan, coverage, far_goals, oracle_plan,
                         recipe, recipe_env_of, recipe_plans, strings)
-from simulate_check import oracle_simulate
-from test_expand_logic import _snap, _world
+from records_check import DENSE, encode, oracle_simulate
+from records_fixtures import ENV_OF, M, N, S, SENT, snap, world as _world
 
-N, S, MAX_STEPS, SENT, D = 5, 5, 9, 0xA5, 3
+MAX_STEPS, D = 9, 3
 OKW = dict(size=(S, S), max_steps=MAX_STEPS)
-ENV_OF = np.array([0, 4, -1, 2, 2, 7, 1, -7, 3, 5 + 31, 0, 2 ** 31 - 1], np.int64)       # 12 states: 7 take part (env 2 and 0 twice), 2 take none, 3 are skipped
-M = len(ENV_OF)
 
 
 def test_the_checker_knows_the_seven_fields_the_kernel_writes():
@@ -24,7 +21,7 @@ def test_the_checker_knows_the_seven_fields_the_kernel_writes():
 
 @pytest.fixture(scope='module')
 def world():
-    """the N oracle envs of test_expand_logic, with a goal two steps away where there is one, else one step away, else as they are"""
+    """the N oracle envs of records_fixtures, with a goal two steps away where there is one, else one step away, else as they are"""
     dense, init_grids = _world()
     two, one = far_goals(dense, init_grids, np.full(N, 2), OKW), far_goals(dense, init_grids, np.full(N, 1), OKW)
     goal = np.where(two >= 0, two, one)
@@ -46,7 +43,7 @@ def _rows(want, menu):
 
 def _correct(dense, init_grids, env_of):
     """what a correct call leaves: (before, after, inputs, outputs, the oracle's plans, the states that take part and their init grids)"""
-    before = _snap(dense, init_grids)
+    before = snap(dense, init_grids)
     if env_of is None:
         env, inputs, sub, menu = np.arange(N), None, dense, np.full(N, 3)
     else:

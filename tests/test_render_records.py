@@ -10,9 +10,10 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import decode
+from engines import K5, n_cu
 from masked_check import spread, take
 from oracle_replay import make_env, np_states
+from records_check import decode
 from render_records_check import check_frames, dense_of, frame_bytes, frame_shape, oracle_frames, records_launch, records_of
 from state_tables import painted_states
 
@@ -20,11 +21,6 @@ pytestmark = pytest.mark.gpu
 
 SENT = 0xA5
 RASTERS = ['ray', 'alt']
-K5 = dict(size=(5, 5), max_steps=17)
-
-
-def _n_cu():
-    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
 
 
 def _engine(S, raster, N=2, **kw):
@@ -124,9 +120,9 @@ def test_launch_shapes(raster):
     source state's"""
     alt = raster == 'alt'
     hdr, pos, want, ps = _painted(5, alt)
-    n_cu = _n_cu()
-    big = 4 * n_cu + 5
-    assert records_launch(big, n_cu) == 4 * n_cu < big and records_launch(65, n_cu) == 68
+    cus = n_cu()
+    big = 4 * cus + 5
+    assert records_launch(big, cus) == 4 * cus < big and records_launch(65, cus) == 68
     env = _engine(5, raster)
     for M in (1, 63, 64, 65, big):
         src = np.arange(M) % len(ps)

@@ -8,47 +8,30 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import encode
+from engines import ENGINES, K5, N1, k_of
 from hostlib import host_lib
 from masked_check import spread, take
 from oracle_replay import make_env, np_states
-from shoot_check import FIELDS, LONG, RECIPE_KW, SHAPES, assert_coverage, check_shoot, coverage, model_actions, recipe_shots
-from test_expand import _env_of
-from test_plan import _walk_goals
-from test_snapshot import ENGINES, K5, N1, k_of
+from records_check import encode
+from records_gpu import SENT, caller_records, dev as _dev, env_of_cases as _env_of, host, sentinel_out, walk_goals as _walk_goals, walked_engine
+from shoot_check import FIELDS, LONG, RECIPE_KW, SHAPES, assert_coverage, check_shoot, coverage, layout, model_actions, recipe_shots
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-_WIDTH = dict(best_ret=4, best_sample=4, best_action=1, length=4, done=1, achieved_mask=2, hdr=16, slot_pos=16)
+_WIDTH = dict(best_ret=4, best_sample=4, best_action=1, length=4, done=1, achieved_mask=2, hdr=16, slot_pos=16, plan=1, ret=4)
 _DTYPE = dict(best_ret=torch.int32, best_sample=torch.int32, best_action=torch.uint8, length=torch.int32, done=torch.bool, achieved_mask=torch.int16,
-              hdr=torch.uint8, slot_pos=torch.int16)
+              hdr=torch.uint8, slot_pos=torch.int16, plan=torch.uint8, ret=torch.int32)
 PER_PLAN = ('length', 'done', 'achieved_mask', 'hdr', 'slot_pos')      # what simulate() returns for a plan besides its return
 KS = (1, 2, 3, 5, 8, 16, 33, 64, 100)
 
 
-def _sentinel_out(T, K, M, fields=FIELDS):
+def _sentinel_out(T, K, M):
     """output buffers as shoot(out=...) takes them, every byte SENT"""
-    out = {}
-    for f in fields:
-        if f == 'plan':
-            out[f] = torch.full((T, M), SENT, dtype=torch.uint8, device='cuda')
-        elif f == 'ret':
-            out[f] = torch.full((K, M, 4), SENT, dtype=torch.uint8, device='cuda').view(torch.int32).squeeze(-1)
-        else:
-            t = torch.full((M, _WIDTH[f]), SENT, dtype=torch.uint8, device='cuda').view(_DTYPE[f])
-            out[f] = t if f == 'hdr' or f == 'slot_pos' else t.squeeze(-1)
-        assert out[f].is_contiguous()
-    return out
+    return sentinel_out(layout(T, K), _WIDTH, _DTYPE, M)
 
 
 def _host(r):
-    """a shoot() result as numpy, done as the bytes the kernel wrote"""
-    return {f: (t.view(torch.uint8) if t.dtype is torch.bool else t).cpu().numpy() for f, t in r.items() if f in FIELDS}
-
-
-def _dev(a, dtype=np.uint8):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device='cuda')
+    return host(r, FIELDS)
 
 
 def _lanes(M, K):
@@ -115,20 +98,13 @@ def test_every_winning_length_occurs():
 # ------------------------------------------------------------------------------------------------------------------------------ 2. every lane-group width and tail
 @pytest.fixture(scope='module')
 def engine70():
-    env, _, _ = make_env(N1, *np_states(N1, 87000), obs_mode='state', auto_reset=False, **K5)
-    env.reset()
-    spread(env, 9, 3)
-    _walk_goals(env, 2, 88)
+    env = walked_engine(87000, 9, goals=(2, 88))
     yield env
     env.close()
 
 
 def _records(before, e, M):
-    src = np.where((e >= 0) & (e < N1), e, 0)
-    hdr = before['hdr'][src].copy()
-    hdr[:, 8] = (hdr[:, 8] + np.arange(M)) % K5['max_steps']                      # records of the caller's: other step counts than the envs' own
-    hdr[:, 3] = np.arange(M) % 5                                                  # ... and menu bytes, which a plan keeps
-    return hdr, before['slot_pos'][src].copy()
+    return caller_records(before, e, M, N1, K5['max_steps'])
 
 
 def test_the_shapes_hit_every_width():

@@ -1,4 +1,4 @@
-"""CPU tier: the draw function of cw_shoot and the checker of the shoot tests (tests/shoot_check.py) themselves.  The numpy model, written from the header's
+"""CPU tier: the draw function of cw_shoot and the checker of the shoot tests (tests/shoot_check.py over records_check.py).  The numpy model, written from the header's
 text, against the library's own function bit for bit; the statistics the header's function was chosen on; then the outputs a correct cw_shoot would leave,
 synthesised on the CPU -- the model's actions through the oracle, reduced, encoded into packed records by the test-side encoder -- which must pass, and each
 planted fault, which must be caught.  Also here: what the shared batch of states exercises, counted from the oracle alone."""
@@ -7,19 +7,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from expand_check import DENSE, encode
 from gym_craftingworld_amd.vec_env import SHOOT_FIELDS
 from hostlib import host_lib
 from plan_check import far_goals
+from records_check import DENSE, encode, oracle_simulate
+from records_fixtures import ENV_OF, M, N, S, SENT, snap, world as _world
 from shoot_check import (FIELDS, LONG, RECIPE_KW, SHAPES, action, assert_coverage, check_shoot, coverage, draw, expected_shoot, mix, model_actions,
                          recipe_shots)
-from simulate_check import oracle_simulate
-from test_expand_logic import _snap, _world
 
-N, S, MAX_STEPS, SENT, T, K, SEED = 5, 5, 9, 0xA5, 4, 12, 0x123456789ABCDEF
+MAX_STEPS, T, K, SEED = 9, 4, 12, 0x123456789ABCDEF
 OKW = dict(size=(S, S), max_steps=MAX_STEPS)
-ENV_OF = np.array([0, 4, -1, 2, 2, 7, 1, -7, 3, 5 + 31, 0, 2 ** 31 - 1], np.int64)       # 12 states: 7 take part (env 2 and 0 twice), 2 take none, 3 are skipped
-M = len(ENV_OF)
 GRID_SEEDS = (0, 1, 2, 0xDEADBEEF12345678, 2 ** 64 - 1)
 
 
@@ -140,7 +137,7 @@ def test_model_actions_layout():
 # ------------------------------------------------------------------------------------------------------------------------------ the checker
 @pytest.fixture(scope='module')
 def world():
-    """the N oracle envs of test_expand_logic, with a goal two steps away where there is one, else one step away, else as they are"""
+    """the N oracle envs of records_fixtures, with a goal two steps away where there is one, else one step away, else as they are"""
     dense, init_grids = _world()
     two, one = far_goals(dense, init_grids, np.full(N, 2), OKW), far_goals(dense, init_grids, np.full(N, 1), OKW)
     goal = np.where(two >= 0, two, one)
@@ -157,7 +154,7 @@ def _rows(want, menu):
 
 def _correct(dense, init_grids, env_of, weights=None):
     """what a correct call leaves: (before, after, inputs, outputs, expected_shoot, the input states and their init grids)"""
-    before = _snap(dense, init_grids)
+    before = snap(dense, init_grids)
     if env_of is None:
         env, inputs, sub, menu = np.arange(N), None, dense, np.full(N, 3)
     else:

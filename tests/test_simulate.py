@@ -7,17 +7,16 @@ import numpy as np
 import pytest
 import torch
 
-from expand_check import DENSE, POS_GONE, POS_HELD, decode
+from engines import ENGINES, K5, N1, SIZES, k_of
 from masked_check import spread, take
 from oracle_replay import make_env, np_states, record_steps, same
-from simulate_check import FIELDS, RECIPE_KW, RECIPE_N, TRACES, assert_recipe_coverage, check_simulate, coverage, oracle_simulate, recipe
+from records_check import DENSE, POS_GONE, POS_HELD, decode, oracle_simulate
+from records_gpu import SENT, caller_records, dev as _dev, env_of_cases, host as _host, sentinel_out, walked_engine
+from simulate_check import FIELDS, RECIPE_KW, RECIPE_N, TRACES, assert_recipe_coverage, check_simulate, coverage, layout, recipe
 from state_tables import painted_batch, wall_table
-from test_expand import _env_of
-from test_snapshot import ENGINES, K5, N1, SIZES, k_of
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
 BLOCK = 8                                       # CW_SIM_BLOCK: the action bytes are fetched this many steps at a time
 _WIDTH = dict(ret=4, length=4, done=1, achieved_mask=2, hdr=16, slot_pos=16, rewards=4, dones=1)
 _DTYPE = dict(ret=torch.int32, length=torch.int32, done=torch.bool, achieved_mask=torch.int16, hdr=torch.uint8, slot_pos=torch.int16, rewards=torch.int32,
@@ -26,27 +25,12 @@ _DTYPE = dict(ret=torch.int32, length=torch.int32, done=torch.bool, achieved_mas
 
 def _sentinel_out(T, M, fields=FIELDS):
     """output buffers as simulate(out=...) takes them, every byte SENT"""
-    out = {}
-    for f in fields:
-        lead = (T, M) if f in TRACES else (M,)
-        t = torch.full(lead + (_WIDTH[f],), SENT, dtype=torch.uint8, device='cuda').view(_DTYPE[f])
-        out[f] = t if f == 'hdr' or f == 'slot_pos' else t.squeeze(-1)
-        assert out[f].is_contiguous() and tuple(out[f].shape[:len(lead)]) == lead
-    return out
-
-
-def _host(r):
-    """a simulate() result as numpy, done / dones as the bytes the kernel wrote"""
-    return {f: (t.view(torch.uint8) if t.dtype is torch.bool else t).cpu().numpy() for f, t in r.items()}
+    return sentinel_out({f: layout(T)[f] for f in fields}, _WIDTH, _DTYPE, M)
 
 
 def _dense_of(snap, rows=None):
     d = decode(snap['hdr'], snap['slot_pos'], snap['state_grid'].shape[1])
     return {k: (v if rows is None else v[rows]) for k, v in d.items()}
-
-
-def _dev(a, dtype=np.uint8):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device='cuda')
 
 
 def _plans(seed, T, M, noops=0.0):
@@ -273,25 +257,18 @@ def test_host_outputs_engine():
 # ------------------------------------------------------------------------------------------------------------------------------ 5. launch and loop edges
 @pytest.fixture(scope='module')
 def engine70():
-    env, _, _ = make_env(N1, *np_states(N1, 71000), obs_mode='state', auto_reset=False, **K5)
-    env.reset()
-    spread(env, 6, 3)
+    env = walked_engine(71000, 6)
     yield env
     env.close()
 
 
 def _records(before, M, seed, with_env_of=True):
-    """M records of the caller's from a 70-env engine: the envs' own with other step counts and menu bytes -> (env_of as test_expand._env_of draws it, or
-    None: record j is env j % 70's; hdr, pos)"""
-    if with_env_of:
-        e = _env_of(M, N1) if M >= 63 else np.random.RandomState(seed).randint(0, N1, M).astype(np.int64)
-        src = np.where((e >= 0) & (e < N1), e, 0)
-    else:
-        e, src = None, np.arange(M) % N1
-    hdr = before['hdr'][src].copy()
-    hdr[:, 8] = (hdr[:, 8] + np.arange(M)) % K5['max_steps']
-    hdr[:, 3] = np.arange(M) % 5
-    return e, hdr, before['slot_pos'][src].copy()
+    """M records of the caller's from a 70-env engine: the envs' own with other step counts and menu bytes -> (env_of as records_gpu.env_of_cases draws
+    it, or None: record j is env j % 70's; hdr, pos)"""
+    if not with_env_of:
+        return (None,) + caller_records(before, np.arange(M) % N1, M, N1, K5['max_steps'])
+    e = env_of_cases(M, N1) if M >= 63 else np.random.RandomState(seed).randint(0, N1, M).astype(np.int64)
+    return (e,) + caller_records(before, e, M, N1, K5['max_steps'])
 
 
 def _edge_call(env, M, T, stop, seed, fields=FIELDS, with_env_of=True, noops=0.08):

@@ -1,22 +1,20 @@
-"""CPU tier: the checker of the simulate tests (tests/simulate_check.py) itself.  The outputs a correct cw_simulate would leave are synthesised on the CPU --
+"""CPU tier: the checker of the simulate tests (simulate_check.py, records_check.py) itself.  The outputs a correct cw_simulate would leave are synthesised on the CPU --
 the oracle's rollouts, encoded into packed records by the test-side encoder -- and must pass; each planted fault must be caught.  Also here: what the shared
 batch of plans (simulate_check.recipe) exercises, counted from the oracle alone."""
 import numpy as np
 import pytest
 
-from expand_check import encode
-from simulate_check import RECIPE_KW, RECIPE_N, assert_recipe_coverage, check_simulate, coverage, oracle_simulate, recipe
-from test_expand_logic import _snap, _world
+from records_check import decode, encode, oracle_simulate
+from records_fixtures import ENV_OF, M, N, S, SENT, snap, world as _world
+from simulate_check import RECIPE_KW, RECIPE_N, assert_recipe_coverage, check_simulate, coverage, recipe
 
-N, S, MAX_STEPS, SENT, T = 5, 5, 17, 0xA5, 7
+MAX_STEPS, T = 17, 7
 OKW = dict(size=(S, S), max_steps=MAX_STEPS)
-ENV_OF = np.array([0, 4, -1, 2, 2, 7, 1, -7, 3, 5 + 31, 0, 2 ** 31 - 1], np.int64)       # 12 states: 7 take part (env 2 and 0 twice), 2 take none, 3 are skipped
-M = len(ENV_OF)
 
 
 @pytest.fixture(scope='module')
 def world():
-    """the N oracle envs of test_expand_logic"""
+    """the N oracle envs of records_fixtures"""
     return _world()
 
 
@@ -26,7 +24,7 @@ def _plans(m):
 
 def _correct(dense, init_grids, env_of, stop):
     """what a correct call leaves: (before, after, inputs, actions, outputs) for the M states ENV_OF picks (env_of None: the engine's own states, 2 plans each)"""
-    before = _snap(dense, init_grids)
+    before = snap(dense, init_grids)
     if env_of is None:
         env = np.arange(2 * N) % N
         sub, inputs, menu = {k: v[env] for k, v in dense.items()}, None, np.full(2 * N, 3)
@@ -41,7 +39,7 @@ def _correct(dense, init_grids, env_of, stop):
         two = oracle_simulate(dense, init_grids, acts[:2, :N], False, OKW)
         dense = dict(dense, desired=np.where(np.arange(N) % 2 == 0, two['achieved'], dense['desired']))
         sub = {k: v[env] for k, v in dense.items()}
-        before = _snap(dense, init_grids)
+        before = snap(dense, init_grids)
     else:
         two = oracle_simulate(sub, init_grids[env], acts[:2], False, OKW)
         sub['desired'] = np.where(np.arange(m) % 2 == 0, two['achieved'], sub['desired'])
@@ -163,7 +161,6 @@ def _plant(name, before, after, inputs, acts, out, want):
 
 
 def _decode_inputs(inputs):
-    from expand_check import decode
     return {k: v for k, v in decode(inputs['hdr'], inputs['slot_pos'], S).items() if k not in ('menu', 'held_code')}
 
 

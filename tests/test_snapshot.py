@@ -9,23 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from engines import ENGINES, K5, MENUS, N1, SIZES, k_of, n_cu
 from masked_check import masked_launch, spread, take
 from oracle_replay import FRAMES, make_env, np_states, oracle_kw, record_steps, same, same_states, snapshot
 from snapshot_check import check_load, check_save
 from state_tables import oracle_frame, painted_batch
-from test_masked_shapes import _engine, _n_cu, _width
+from test_masked_shapes import _engine, _width
 
 pytestmark = pytest.mark.gpu
-
-K5 = dict(size=(5, 5), max_steps=17)
-SIZES = [5, 4, 7, 8, 21]              # 7 / 8: the full-frame engine changes painter (gather up to 7, piece sweep from 8); 21: the headline frame
-
-
-def k_of(S):
-    """the configuration of the round-trip and expand tests at size S: max_steps stays 17, so 2 * 17 + 3 steps reset every env twice at any size"""
-    return dict(K5, size=(S, S))
-MENUS = [dict(), dict(selected_tasks=['ChopTree', 'MoveAxe', 'EatBread', 'GoToHouse'], number_of_tasks=2)]      # (the same reward rule: with_stream=False keeps the row's)
-
 
 def _dev(a):
     return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device='cuda')
@@ -46,11 +37,7 @@ def _step_recorded(env, acts):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ 1. round trip and fork
-N1, CAP1 = 70, 96
-ENGINES = {'state_manual': dict(obs_mode='state', auto_reset=False),
-           'dirty_ray_auto': dict(obs_mode='pixels_dirty', raster='ray'),
-           'pixels_alt_auto': dict(obs_mode='pixels', raster='alt'),
-           'state_auto_pool_menus': dict(obs_mode='state', fixed_init_state=3, task_menus=MENUS, env_menu=(np.arange(N1) % 2).astype(np.uint8))}
+CAP1 = 96
 SNAPSHOT_ENGINES = dict(ENGINES, pixels_ray_auto=dict(obs_mode='pixels', raster='ray'))      # the full-frame sweep of the ray raster (tests/test_expand.py runs ENGINES)
 
 
@@ -192,7 +179,7 @@ def test_save_and_load_at_every_dealing_width(monkeypatch, width, pattern):
     from the row of the NEXT selected env, then with the stream from their own"""
     N, epb, chunks = _width(width)
     env, _, _ = _engine(monkeypatch, N, obs_mode='state', auto_reset=False, **K5)
-    assert masked_launch(N, _n_cu(), 1)[:2] == (epb, chunks)
+    assert masked_launch(N, n_cu(), 1)[:2] == (epb, chunks)
     env.snapshot_reserve(N)
     env.reset()
     spread(env, 4, 6)

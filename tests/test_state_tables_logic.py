@@ -4,7 +4,8 @@ packed record format holds.  No GPU."""
 import numpy as np
 import pytest
 
-from expand_check import POS_HELD, decode, encode, oracle_successors
+from expand_check import oracle_successors
+from records_check import POS_HELD, decode, encode
 from state_tables import (LARGE_CAP, oracle_frame, painted_batch, painted_states, table_coverage, table_desired, wall_table)
 
 MAX_STEPS = 9
