@@ -75,6 +75,10 @@ class cw_shoot_out(C.Structure):
                 ('achieved', C.c_void_p), ('hdr', C.c_void_p), ('slot_pos', C.c_void_p), ('plan', C.c_void_p), ('ret', C.c_void_p)]
 
 
+class cw_seen_out(C.Structure):
+    _fields_ = [('fresh', C.c_void_p), ('first', C.c_void_p)]
+
+
 class cw_profile(C.Structure):
     _fields_ = [('steps', C.c_int32), ('ms_step_kernel', C.c_float), ('ms_reset_kernel', C.c_float),
                 ('ms_render_kernel', C.c_float), ('ms_render_kernel_max', C.c_float), ('ms_render_kernel_min', C.c_float),
@@ -110,6 +114,11 @@ ABI = {
     'cw_plan': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_plan_out), _VP]),
     'cw_shoot': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, C.POINTER(cw_shoot_out), _VP]),
     'cw_shoot_actions': (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    'cw_seen_reserve': (C.c_int, [_VP, C.c_int64, C.c_int32]),
+    'cw_seen_clear': (C.c_int, [_VP, _VP]),
+    'cw_seen_insert': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_seen_out), _VP]),
+    'cw_seen_counters': (C.c_int, [_VP, C.POINTER(_VP)]),
+    'cw_seen_slots': (C.c_size_t, [_VP]),
     'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
@@ -160,6 +169,8 @@ CWH_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_PLAN_MAX_DEPTH, CWH_PLAN_MAX_LEAVES = 8, 1 << 32
 CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
 CWH_SHOOT_MAX_SAMPLES, CWH_SHOOT_MAX_WORK = 65536, 1 << 32
+CWH_SEEN_OK, CWH_SEEN_NO_RECORDS, CWH_SEEN_NO_FIELD, CWH_SEEN_N_STATES, CWH_SEEN_ALIGN, CWH_SEEN_OVERLAP = range(6)
+CWH_SEEN_KEY_WORDS, CWH_SEEN_MAX_CAPACITY, CWH_SEEN_PROBES = 9, 1 << 28, 128
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -190,6 +201,10 @@ HOST_HELPERS = {
     'cwh_shoot_draw_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     'cwh_shoot_action_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     'cwh_shoot_lanes_of': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_seen_key_of': (None, [C.c_int32, _VP, _VP, _VP]),
+    'cwh_seen_hash_of': (C.c_uint64, [_VP]),
+    'cwh_seen_slots_of': (C.c_int64, [C.c_int64]),
+    'cwh_seen_args': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),

@@ -43,6 +43,9 @@ hipError_t cwk_launch_shoot(const CwParams *P, const int32_t *env_of, const uint
                             unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights, const CwShootOut *O, hipStream_t st);
 hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsigned long long seed, const unsigned long long *seed_dev,
                                     const uint16_t *weights, const int32_t *samples, uint8_t *out, hipStream_t st);
+hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const CwSeen *S, const int32_t *group, const uint4 *hdr, const uint4 *pos, int n_states,
+                                  uint8_t *fresh, int32_t *first, hipStream_t st);
+hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st);
 hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
                                int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
@@ -103,6 +106,9 @@ struct cw_engine {
     void *bank = nullptr;              // the snapshot bank's one allocation (cw_snapshot_reserve), or null: none reserved
     CwBank B{};                        // ... its sections (cw_host.cpp: cwh_snapshot_section_bytes)
     size_t bank_row_bytes = 0;
+    void *seen = nullptr;              // the visited set's one allocation (cw_seen_reserve), or null: none reserved
+    CwSeen Sn{};                       // ... its arrays (cw_layout.h)
+    int64_t seen_slots = 0;
     int n = 0, S = 0, ncell = 0, K = 0;
     // resident stepper of the single-env loop (cw_step_resident; cw_kernels.hip: cw_resident_kernel)
     CwResident *res = nullptr;         // pinned coherent host memory, or null (engine not eligible)
@@ -218,7 +224,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -660,6 +666,7 @@ int cw_destroy(cw_engine *e)
     for (auto &smp : e->guard_ring) for (hipEvent_t ev : smp.ev) if (ev) (void)hipEventDestroy(ev);
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->bank) (void)hipFree(e->bank);
+    if (e->seen) (void)hipFree(e->seen);
     for (void *p : e->host_allocs) (void)hipHostFree(p);
     delete e;
     return CW_OK;
@@ -1067,6 +1074,102 @@ int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t s
     if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_shoot_actions(n_states, n_steps, n_rows, (unsigned long long)seed, (const unsigned long long *)seed_dev, weights, samples, out,
                                      (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ seen: the visited set of packed records
+// One allocation of the engine's, like the snapshot bank and as far from every checkpoint blob and snapshot row: the control block (256 bytes), then the tags,
+// the owners and the two halves of the stored keys, 48 bytes a slot.  A reserve drops everything seen: the new set is cleared before the call returns.
+static void seen_free(cw_engine *e)
+{
+    if (e->seen) (void)hipFree(e->seen);
+    e->seen = nullptr;
+    e->Sn = CwSeen{};
+    e->seen_slots = 0;
+}
+
+int cw_seen_reserve(cw_engine *e, int64_t capacity, int32_t tag_bits)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_seen_reserve: null engine");
+    const int64_t slots = cwh_seen_slots_of(capacity);
+    if (slots < 0) return fail(CW_ERR_INVALID, "cw_seen_reserve: capacity = %lld must be 0 .. %lld", (long long)capacity, (long long)CWH_SEEN_MAX_CAPACITY);
+    if (tag_bits < 0 || tag_bits > 63) return fail(CW_ERR_INVALID, "cw_seen_reserve: tag_bits = %d must be 0 (the full hash) .. 63", tag_bits);
+    SyncEntry in(e);                                 // (the engine's own work: an insert in flight uses the set about to go)
+    if (in.rc != CW_OK) return in.rc;
+    seen_free(e);
+    if (slots == 0) return CW_OK;
+    const size_t n = (size_t)slots, ctl_bytes = 256;
+    void *p = nullptr;
+    if (hipMalloc(&p, ctl_bytes + n * 48) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CW_ERR_HIP, "cw_seen_reserve: no device memory for %lld slots of 48 bytes", (long long)slots);
+    }
+    char *const b = (char *)p;
+    CwSeen S{};
+    S.ctl = (unsigned long long *)b;
+    S.tag = (unsigned long long *)(b + ctl_bytes);
+    S.owner = (unsigned long long *)(b + ctl_bytes + n * 8);
+    S.key_a = (uint4 *)(b + ctl_bytes + n * 16);
+    S.key_b = (uint4 *)(b + ctl_bytes + n * 32);
+    S.mask = (uint32_t)(n - 1);
+    S.probes = slots < CWH_SEEN_PROBES ? (int32_t)slots : CWH_SEEN_PROBES;
+    S.tag_bits = tag_bits;
+    if (cwk_launch_seen_clear(&e->tune, &S, e->aux) != hipSuccess || hipStreamSynchronize(e->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return fail(CW_ERR_HIP, "cw_seen_reserve: clearing the set failed");
+    }
+    e->seen = p;
+    e->Sn = S;
+    e->seen_slots = slots;
+    return CW_OK;
+}
+
+size_t cw_seen_slots(const cw_engine *e)
+{
+    if (!e) { (void)fail(CW_ERR_INVALID, "cw_seen_slots: null engine"); return 0; }
+    return e->seen ? (size_t)e->seen_slots : 0;
+}
+
+int cw_seen_counters(const cw_engine *e, const uint64_t **counters)
+{
+    if (!e || !counters) return fail(CW_ERR_INVALID, "cw_seen_counters: null %s", !e ? "engine" : "counters");
+    *counters = e->seen ? (const uint64_t *)e->Sn.ctl : nullptr;
+    return e->seen ? CW_OK : fail(CW_ERR_STATE, "cw_seen_counters: no set reserved (cw_seen_reserve)");
+}
+
+// Only enqueues ONE kernel: no wait, no allocation, the same call whether it runs or is captured.
+int cw_seen_clear(cw_engine *e, cw_stream_t stream)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_seen_clear: null engine");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_seen_clear called before cw_reset");
+    if (!e->seen) return fail(CW_ERR_STATE, "cw_seen_clear: no set reserved (cw_seen_reserve)");
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_seen_clear(&e->tune, &e->Sn, (hipStream_t)stream));
+    return in.done();
+}
+
+// Checks (cwh_seen_args, tested on the CPU), then TWO kernels.  Of the engine only the set is written.
+int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, const cw_seen_out *out, cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_seen_insert: null %s", !e ? "engine" : "out");
+    switch (cwh_seen_args((uint64_t)(uintptr_t)group, (uint64_t)(uintptr_t)hdr, (uint64_t)(uintptr_t)slot_pos, n_states, (uint64_t)(uintptr_t)out->fresh,
+                          (uint64_t)(uintptr_t)out->first)) {
+    case CWH_SEEN_OK: break;
+    case CWH_SEEN_NO_RECORDS: return fail(CW_ERR_INVALID, "cw_seen_insert: null %s", !hdr ? "hdr" : "slot_pos");
+    case CWH_SEEN_NO_FIELD: return fail(CW_ERR_INVALID, "cw_seen_insert: every field of out is null");
+    case CWH_SEEN_N_STATES: return fail(CW_ERR_INVALID, "cw_seen_insert: n_states = %d must be 0 .. %d", n_states, CWH_MAX_STATES);
+    case CWH_SEEN_ALIGN: return fail(CW_ERR_INVALID, "cw_seen_insert: hdr / slot_pos must be 16-byte aligned, group / out->first 4-byte aligned");
+    default: return fail(CW_ERR_INVALID, "cw_seen_insert: an output overlaps the records, group or the other output");
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_seen_insert called before cw_reset");
+    if (!e->seen) return fail(CW_ERR_STATE, "cw_seen_insert: no set reserved (cw_seen_reserve)");
+    if (n_states == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_seen_insert(&e->P, &e->tune, &e->Sn, group, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out->fresh, out->first,
+                                   (hipStream_t)stream));
     return in.done();
 }
 

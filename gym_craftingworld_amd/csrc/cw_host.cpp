@@ -237,6 +237,47 @@ int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_byte
     return a < b_end && b < a_end;
 }
 
+// ------------------------------------------------------------------------------ the visited set's key, size and argument rules
+void cwh_seen_key_of(int32_t group, const uint8_t *hdr, const uint16_t *slot_pos, uint32_t *key)
+{
+    uint32_t h[4], p[4];
+    for (int i = 0; i < 4; i++) {
+        h[i] = (uint32_t)hdr[4 * i] | (uint32_t)hdr[4 * i + 1] << 8 | (uint32_t)hdr[4 * i + 2] << 16 | (uint32_t)hdr[4 * i + 3] << 24;
+        uint16_t lo, hi;
+        memcpy(&lo, (const char *)slot_pos + 4 * i, 2);
+        memcpy(&hi, (const char *)slot_pos + 4 * i + 2, 2);
+        p[i] = (uint32_t)lo | (uint32_t)hi << 16;
+    }
+    cwh_seen_key(group, h, p, key);
+}
+uint64_t cwh_seen_hash_of(const uint32_t *key) { return cwh_seen_hash(key); }
+
+int64_t cwh_seen_slots_of(int64_t capacity)
+{
+    if (capacity < 0 || capacity > CWH_SEEN_MAX_CAPACITY) return -1;
+    if (capacity == 0) return 0;
+    int64_t slots = 2;
+    while (slots < 2 * capacity) slots <<= 1;
+    return slots;
+}
+
+int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_states, uint64_t fresh, uint64_t first)
+{
+    if (!hdr || !slot_pos) return CWH_SEEN_NO_RECORDS;
+    if (!fresh && !first) return CWH_SEEN_NO_FIELD;
+    if (n_states < 0 || n_states > CWH_MAX_STATES) return CWH_SEEN_N_STATES;
+    if ((hdr & 15u) || (slot_pos & 15u) || (group & 3u) || (first & 3u)) return CWH_SEEN_ALIGN;
+    const uint64_t m = (uint64_t)n_states;
+    const uint64_t outs[2][2] = {{fresh, m}, {first, 4 * m}}, ins[3][2] = {{hdr, 16 * m}, {slot_pos, 16 * m}, {group, 4 * m}};
+    for (int o = 0; o < 2; o++) {
+        if (!outs[o][0]) continue;
+        for (int i = 0; i < 3; i++)
+            if (ins[i][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_SEEN_OVERLAP;
+    }
+    if (fresh && first && cwh_ranges_overlap(fresh, m, first, 4 * m)) return CWH_SEEN_OVERLAP;
+    return CWH_SEEN_OK;
+}
+
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule
 static double period_ns(int32_t sweep_waves, double tb_per_s) { return (double)sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }
 void cwh_sweep_periods(double rate, int32_t sweep_waves, double head_notch, double busy_notch, int32_t *period16, int32_t *period16_head, int32_t *period16_busy)

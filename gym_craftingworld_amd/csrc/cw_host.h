@@ -176,6 +176,52 @@ int cwh_shoot_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slo
 // 1 <= n_steps <= CWH_SIM_MAX_STEPS (CWH_REC_N_STEPS), n_rows * n_states * n_steps <= CWH_SHOOT_MAX_WORK (CWH_REC_SHOOT_WORK)
 int cwh_shoot_actions_args(int32_t n_states, int32_t n_steps, int32_t n_rows);
 
+// ---- cw_seen_*: the visited set of packed records.  THE KEY of a record (include/craftingworld.h states it): everything step_env reads of a state but the two
+// step counters, and the group that says which records may be merged at all -- group, hdr bytes 0-2, 4-7, bit 1 of byte 10, 12-15 and the 16 bytes of slot_pos:
+// 36 bytes as nine dwords.  hdr and slot_pos as the four little-endian dwords of a record each (the uint4 the kernels load).  Shared by the kernels and the host.
+#define CWH_SEEN_KEY_WORDS 9
+static inline CWH_HOST_DEVICE void cwh_seen_key(int32_t group, const uint32_t hdr[4], const uint32_t pos[4], uint32_t key[CWH_SEEN_KEY_WORDS])
+{
+    key[0] = (uint32_t)group;
+    key[1] = hdr[0] & 0x00FFFFFFu;              // agent row, agent col, hold; not the menu id
+    key[2] = hdr[1];                            // achieved | desired << 16
+    key[3] = (hdr[2] >> 17) & 1u;               // the subset reward rule; not step_num, flag bit 0 or the success count
+    key[4] = hdr[3];                            // the eight slot codes
+    key[5] = pos[0]; key[6] = pos[1]; key[7] = pos[2]; key[8] = pos[3];
+}
+// its 64-bit hash: splitmix64's finaliser folded over the nine dwords (any value, 0 included; the slot tag is made from it by cwh_seen_tag)
+static inline CWH_HOST_DEVICE uint64_t cwh_seen_mix(uint64_t x)
+{
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+static inline CWH_HOST_DEVICE uint64_t cwh_seen_hash(const uint32_t key[CWH_SEEN_KEY_WORDS])
+{
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < CWH_SEEN_KEY_WORDS - 1; i += 2) h = cwh_seen_mix(h ^ ((uint64_t)key[i] | (uint64_t)key[i + 1] << 32));
+    return cwh_seen_mix(h ^ (uint64_t)key[CWH_SEEN_KEY_WORDS - 1]);
+}
+// the tag a slot holds for that hash: all 64 bits, or the low tag_bits of them (1 .. 63: tests and tools/measure_seen.py drive the same-tag-different-key path
+// with it); never 0, which marks an empty slot
+static inline CWH_HOST_DEVICE uint64_t cwh_seen_tag(uint64_t hash, int32_t tag_bits)
+{
+    const uint64_t t = tag_bits > 0 && tag_bits < 64 ? hash & ((1ull << tag_bits) - 1ull) : hash;
+    return t ? t : 1ull;
+}
+void cwh_seen_key_of(int32_t group, const uint8_t *hdr /* [16] */, const uint16_t *slot_pos /* [8] */, uint32_t *key /* [9] */);   // (exported for the CPU tests;
+uint64_t cwh_seen_hash_of(const uint32_t *key /* [9] */);                                                                         //  any alignment, little-endian)
+// slots of a set meant to hold `capacity` distinct keys: the next power of two >= 2 * capacity (2 at least); 0 for capacity 0 (no set), -1 outside 0 .. 2^28
+#define CWH_SEEN_MAX_CAPACITY (1ll << 28)
+#define CWH_SEEN_PROBES 128         // slots a row looks at, linearly from hash & (slots - 1), before it gives up and is counted as overflow (fewer in a smaller set)
+#define CWH_SEEN_ROW_BITS 28        // an owner word is epoch << 28 | row: rows below 2^27, 36 bits of epoch
+#define CWH_SEEN_MAX_EPOCH ((1ull << 36) - 2ull)
+int64_t cwh_seen_slots_of(int64_t capacity);
+// the argument rules of cw_seen_insert, in the order they are tested; addresses as integers (0: null), so the rules need no HIP: records given
+// (CWH_SEEN_NO_RECORDS), some output (CWH_SEEN_NO_FIELD), 0 <= n_states <= CWH_MAX_STATES (CWH_SEEN_N_STATES), hdr and slot_pos 16-byte aligned and group,
+// first 4-byte aligned (CWH_SEEN_ALIGN), neither output sharing a byte with hdr, slot_pos, group or the other output (CWH_SEEN_OVERLAP)
+enum { CWH_SEEN_OK = 0, CWH_SEEN_NO_RECORDS = 1, CWH_SEEN_NO_FIELD = 2, CWH_SEEN_N_STATES = 3, CWH_SEEN_ALIGN = 4, CWH_SEEN_OVERLAP = 5 };
+int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_states, uint64_t fresh, uint64_t first);
+
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).
 typedef struct cwh_guard {

@@ -22,6 +22,8 @@
 //                     state) pair, a depth-first search with its stack in registers and a wave-uniform action at every level; writes nothing of the engine.
 //   cw_shoot_kernel   random shooting: the best of K sampled T-step plans of M such states, the actions drawn where they are used by a counter-based
 //                     integer mix (no action tensor), G lanes per state and a shuffle reduction; cw_shoot_actions_kernel decodes the draws.  Pure.
+//   cw_seen_claim_kernel / cw_seen_resolve_kernel  the visited set of such records: which of M rows brings a key the set has not held, and which is the first
+//                     of its key in the call -- an open-addressed table, one lane per row, atomics on the slot words and no wait; cw_seen_clear_kernel empties it.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -1000,6 +1002,142 @@ __global__ __launch_bounds__(256) void cw_shoot_actions_kernel(int n_states, int
             out[(size_t)t * columns + c] = (uint8_t)a;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------ seen: the visited set of packed records
+// cw_seen_insert: which of M records has the set not held before, and which is the first of its key in this call?  An open-addressed table (CwSeen,
+// cw_layout.h), one lane per row, grid-stride, TWO kernels and no wait of one lane for another anywhere: every loop below has a fixed bound.
+//   cw_seen_claim_kernel    packs the row's key (cwh_seen_key), hashes it and probes linearly from hash & mask, CWH_SEEN_PROBES slots at most: a slot whose tag
+//                           is 0 is taken by a compare-and-swap, a slot whose tag is the row's own is shared; there the row bids for the slot with
+//                           atomicMin(owner, epoch << 28 | row) and stops.  Tags never change once set, so every row of one key stops at the same slot, whatever
+//                           order the waves arrive in, and after the kernel its owner names the smallest of them -- or an earlier call's winner, whose epoch is
+//                           smaller than any bid of this one.
+//   cw_seen_resolve_kernel  walks the same probes again (plain loads now: the tags are final) and reads the owner.  An earlier epoch: the slot's stored key
+//                           decides between "seen" and a collision.  This epoch and this row: the WINNER, which stores its key and is counted.  This epoch and a
+//                           smaller row i: record i of the input arrays decides between "duplicate of i" and a collision.  No slot within the bound: overflow.
+//                           The key store is written by winners only and read for earlier epochs only: nothing races inside a call.  Overflow and collision rows
+//                           are reported fresh -- the safe direction -- and counted.  The workgroup that draws the last ticket advances the epoch ON THE DEVICE,
+//                           so a replayed graph tells "before this call" from "in this call" like a repeated call does.
+// Both are latency-bound random access: 8-byte atomics resolved in L2, no LDS, as many waves in flight as the card holds.  The repeated call (every key held)
+// issues no atomic at all: a tag or an earlier epoch's owner read by a device-scope load is final.  Neither kernel reads or writes anything of the engine.
+__device__ __forceinline__ bool seen_key_of_row(const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int j,
+                                                int n_envs, uint32_t key[CWH_SEEN_KEY_WORDS])
+{
+    const int32_t g = group ? group[j] : (int32_t)((uint32_t)j % (uint32_t)n_envs);
+    if (g < 0) return false;
+    const uint4 h = hdr_in[j], p = pos_in[j];
+    const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, pw[4] = {p.x, p.y, p.z, p.w};
+    cwh_seen_key(g, hw, pw, key);
+    return true;
+}
+// the stored form of a key: the nine dwords in eight (the reward rule's bit rides in the byte the menu id left free)
+__device__ __forceinline__ uint4 seen_key_a(const uint32_t key[CWH_SEEN_KEY_WORDS]) { return make_uint4(key[0], key[1] | (key[3] << 24), key[2], key[4]); }
+__device__ __forceinline__ uint4 seen_key_b(const uint32_t key[CWH_SEEN_KEY_WORDS]) { return make_uint4(key[5], key[6], key[7], key[8]); }
+__device__ __forceinline__ bool same4(const uint4 &a, const uint4 &b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+
+__global__ __launch_bounds__(256) void cw_seen_claim_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
+                                                            const uint4 *__restrict__ pos_in, int n_states, int n_envs)
+{
+    const unsigned long long epoch = S.ctl[CW_SEEN_EPOCH];
+    if (epoch > CWH_SEEN_MAX_EPOCH) return;          // (the epochs are used up: cw_seen_resolve_kernel reports every row as overflow until the next clear)
+    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < (size_t)n_states; jj += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)jj;
+        uint32_t key[CWH_SEEN_KEY_WORDS];
+        if (!seen_key_of_row(group, hdr_in, pos_in, j, n_envs, key)) continue;
+        const unsigned long long hash = cwh_seen_hash(key), tag = cwh_seen_tag(hash, S.tag_bits);
+        const unsigned long long bid = (epoch << CWH_SEEN_ROW_BITS) | (unsigned long long)j;
+        for (int p = 0; p < S.probes; p++) {
+            const uint32_t s = ((uint32_t)hash + (uint32_t)p) & S.mask;
+            unsigned long long t = __hip_atomic_load(&S.tag[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == 0ull) {
+                t = atomicCAS(&S.tag[s], 0ull, tag);
+                if (t == 0ull) t = tag;
+            }
+            if (t != tag) continue;
+            const unsigned long long o = __hip_atomic_load(&S.owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((o >> CWH_SEEN_ROW_BITS) >= epoch) atomicMin(&S.owner[s], bid);      // (an earlier epoch's owner is final and smaller than any bid)
+            break;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cw_seen_resolve_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
+                                                              const uint4 *__restrict__ pos_in, int n_states, int n_envs, uint8_t *__restrict__ fresh,
+                                                              int32_t *__restrict__ first)
+{
+    const unsigned long long epoch = S.ctl[CW_SEEN_EPOCH];
+    const bool spent = epoch > CWH_SEEN_MAX_EPOCH;
+    uint32_t n_won = 0, n_overflow = 0, n_collision = 0;
+    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < (size_t)n_states; jj += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)jj;
+        uint32_t key[CWH_SEEN_KEY_WORDS];
+        if (!seen_key_of_row(group, hdr_in, pos_in, j, n_envs, key)) continue;
+        const unsigned long long hash = cwh_seen_hash(key), tag = cwh_seen_tag(hash, S.tag_bits);
+        int32_t found = -1;
+        for (int p = 0; p < S.probes && !spent; p++) {
+            const uint32_t s = ((uint32_t)hash + (uint32_t)p) & S.mask;
+            const unsigned long long t = S.tag[s];
+            if (t == tag) { found = (int32_t)s; break; }
+            if (t == 0ull) break;                    // (cannot happen: the claim kernel took the first empty slot of this walk)
+        }
+        int32_t res = j;                             // overflow and collision rows: fresh, the safe direction
+        if (found < 0) {
+            n_overflow++;
+        } else {
+            const unsigned long long o = S.owner[found];
+            const uint4 ka = seen_key_a(key), kb = seen_key_b(key);
+            if ((o >> CWH_SEEN_ROW_BITS) < epoch) {                                   // held since an earlier call
+                if (same4(S.key_a[found], ka) && same4(S.key_b[found], kb)) res = -1; else n_collision++;
+            } else {
+                const int i = (int)(o & ((1ull << CWH_SEEN_ROW_BITS) - 1ull));
+                if (i == j) {                                                         // the winner brings the key in
+                    S.key_a[found] = ka;
+                    S.key_b[found] = kb;
+                    n_won++;
+                } else if (i >= 0 && i < j) {                                         // (i < j always: the owner is the smallest bidder)
+                    uint32_t other[CWH_SEEN_KEY_WORDS];
+                    bool eq = seen_key_of_row(group, hdr_in, pos_in, i, n_envs, other);
+                    for (int k = 0; k < CWH_SEEN_KEY_WORDS; k++) eq = eq && other[k] == key[k];
+                    if (eq) res = i; else n_collision++;
+                } else {
+                    n_collision++;
+                }
+            }
+        }
+        if (first) first[j] = res;
+        if (fresh) fresh[j] = res == j ? 1 : 0;
+    }
+    // the three counters, one add per wave and counter that has something to add
+    for (int d = CW_WAVE / 2; d > 0; d >>= 1) {
+        n_won += __shfl_down(n_won, d, CW_WAVE);
+        n_overflow += __shfl_down(n_overflow, d, CW_WAVE);
+        n_collision += __shfl_down(n_collision, d, CW_WAVE);
+    }
+    if ((threadIdx.x & (CW_WAVE - 1)) == 0) {
+        if (n_won) atomicAdd(&S.ctl[CW_SEEN_SIZE], (unsigned long long)n_won);
+        if (n_overflow) atomicAdd(&S.ctl[CW_SEEN_OVERFLOW], (unsigned long long)n_overflow);
+        if (n_collision) atomicAdd(&S.ctl[CW_SEEN_COLLISIONS], (unsigned long long)n_collision);
+    }
+    // every lane of this workgroup has used `epoch` by now; the workgroup that draws the last ticket knows that of all the others and moves it on
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&S.ctl[CW_SEEN_TICKET], 1ull) == (unsigned long long)gridDim.x - 1ull) {
+            __hip_atomic_store(&S.ctl[CW_SEEN_TICKET], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!spent) __hip_atomic_store(&S.ctl[CW_SEEN_EPOCH], epoch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// cw_seen_clear: every slot empty (tag 0, owner all ones; the keys stay, unread), the counters, the epoch and the ticket 0
+__global__ __launch_bounds__(256) void cw_seen_clear_kernel(CwSeen S)
+{
+    const size_t slots = (size_t)S.mask + 1;
+    for (size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (size_t)gridDim.x * blockDim.x) {
+        S.tag[s] = 0ull;
+        S.owner[s] = ~0ull;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < CW_SEEN_CTL_WORDS) S.ctl[threadIdx.x] = 0ull;
 }
 
 // ------------------------------------------------------------------------------------ reset
@@ -2862,6 +3000,28 @@ hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsig
         hipLaunchKernelGGL(cw_shoot_actions_kernel<true>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
     else
         hipLaunchKernelGGL(cw_shoot_actions_kernel<false>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
+    return hipGetLastError();
+}
+
+// cw_seen_insert: two grid-stride launches of one lane per row, CW_SEEN_BLOCKS_PER_CU workgroups of 256 per CU at most (eight waves per SIMD: the kernels wait
+// for L2 round trips and nothing else); cw_seen_clear: one over the slots
+#define CW_SEEN_BLOCKS_PER_CU 8
+static unsigned cw_seen_grid(const CwTuning &T, size_t items)
+{
+    const size_t want = (items + 255) / 256, most = (size_t)T.n_cu * CW_SEEN_BLOCKS_PER_CU;
+    return (unsigned)(want < most ? (want < 1 ? 1 : want) : most);
+}
+hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const CwSeen *S, const int32_t *group, const uint4 *hdr, const uint4 *pos, int n_states,
+                                  uint8_t *fresh, int32_t *first, hipStream_t st)
+{
+    const dim3 grid(cw_seen_grid(*T, (size_t)n_states)), block(256);
+    hipLaunchKernelGGL(cw_seen_claim_kernel, grid, block, 0, st, *S, group, hdr, pos, n_states, P->n_envs);
+    hipLaunchKernelGGL(cw_seen_resolve_kernel, grid, block, 0, st, *S, group, hdr, pos, n_states, P->n_envs, fresh, first);
+    return hipGetLastError();
+}
+hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_seen_clear_kernel, dim3(cw_seen_grid(*T, (size_t)S->mask + 1)), dim3(256), 0, st, *S);
     return hipGetLastError();
 }
 

@@ -91,6 +91,23 @@ struct CwBank {
     int32_t rows;            // the capacity: a row number is an index only after cwh_snapshot_row_ok(row, rows) (cw_host.h)
 };
 
+// The VISITED SET of an engine (cw_seen_reserve): an open-addressed table of `mask + 1` slots (a power of two) in device memory, one array per field, and a
+// control block.  A slot: tag (0: empty, else cwh_seen_tag of the key's hash), owner (all ones: empty, else epoch << CWH_SEEN_ROW_BITS | row of the smallest
+// row that claimed it in the call that filled it) and the key in its stored form, two uint4: a = (group, hdr.x & 0xFFFFFF | subset << 24, hdr.y, hdr.w),
+// b = slot_pos.  48 bytes a slot.  ctl: [0] keys held, [1] overflow, [2] collisions (the three public counters), [3] epoch: the number of inserts since the
+// last clear, advanced ON THE DEVICE by the last workgroup of every insert, [4] the ticket that finds that workgroup.
+#define CW_SEEN_CTL_WORDS 8
+enum { CW_SEEN_SIZE = 0, CW_SEEN_OVERFLOW = 1, CW_SEEN_COLLISIONS = 2, CW_SEEN_EPOCH = 3, CW_SEEN_TICKET = 4 };
+struct CwSeen {
+    unsigned long long *tag;     // [slots]
+    unsigned long long *owner;   // [slots]
+    uint4 *key_a, *key_b;        // [slots]
+    unsigned long long *ctl;     // [CW_SEEN_CTL_WORDS]
+    uint32_t mask;               // slots - 1: a hash becomes a slot index only through `& mask`
+    int32_t probes;              // min(CWH_SEEN_PROBES, slots)
+    int32_t tag_bits;            // 0: the full hash
+};
+
 // Where cw_expand_kernel leaves the six successors of M states (the public cw_expand_out with the records typed): every array ACTION-MAJOR, row a * M + j =
 // action a on input state j.  A null field is not written.
 struct CwExpandOut {

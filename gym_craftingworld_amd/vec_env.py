@@ -298,6 +298,7 @@ def plan_args(num_envs, depth, hdr, slot_pos, env_of):
 
 SHOOT_FIELDS = ('best_ret', 'best_sample', 'best_action', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'ret')
 SHOOT_MAX_SAMPLES, SHOOT_MAX_WORK = 65536, 2 ** 32
+SEEN_FIELDS = ('fresh', 'first')
 
 
 def _shoot_int(v, what, lo, hi):
@@ -1062,6 +1063,158 @@ class CraftingWorldVecEnv:
         if m:
             self._call('cw_render_records', hdr, slot_pos, mask, m, out)
         return out
+
+    # ------------------------------------------------------------------ searching deep
+    def seen_reserve(self, capacity, *, tag_bits=0):
+        """Allocate (or re-allocate: everything seen is dropped; 0 frees it) the engine's visited set for `capacity` distinct keys: the next power of two
+        >= 2 * capacity slots of 48 bytes in device memory (cw_seen_reserve; synchronises this engine's work).  tag_bits: 0, a slot is tagged with the
+        key's full 64-bit hash; 1 .. 63 truncates the tag -- results stay exact, only speed and seen_collisions depend on it (tests and
+        tools/measure_seen.py drive the same-tag-different-key path with it).  ValueError for capacity < 0 or above 2**28 or tag_bits outside 0 .. 63."""
+        capacity, tag_bits = _shoot_int(capacity, 'capacity', 0, 2 ** 28), _shoot_int(tag_bits, 'tag_bits', 0, 63)
+        self._settle()
+        self._seen_ctl = None
+        L.check(self._lib.cw_seen_reserve(self._h, capacity, tag_bits), 'cw_seen_reserve', self._lib)
+        if capacity:
+            p = C.c_void_p()
+            L.check(self._lib.cw_seen_counters(self._h, C.byref(p)), 'cw_seen_counters', self._lib)
+            self._seen_ctl = tensor_view(p.value, (3,), torch.int64, self.device.index)
+
+    def seen_clear(self):
+        """Empty the visited set and reset its counters (cw_seen_clear: one kernel, capturable)."""
+        self._call('cw_seen_clear')
+
+    def _seen_counter(self, k):
+        ctl = getattr(self, '_seen_ctl', None)
+        return 0 if ctl is None else int(ctl[k].item())
+
+    @property
+    def seen_size(self):
+        """how many keys the visited set holds (0 without a set; reading it synchronises, like expand_skipped)"""
+        return self._seen_counter(0)
+
+    @property
+    def seen_overflow(self):
+        """how many rows seen_insert() has reported fresh since the last clear because they found no slot within the probe bound -- a set filled beyond its
+        capacity (reading it synchronises)"""
+        return self._seen_counter(1)
+
+    @property
+    def seen_collisions(self):
+        """how many rows seen_insert() has reported fresh since the last clear because a slot held their tag under another key (reading it synchronises)"""
+        return self._seen_counter(2)
+
+    @property
+    def seen_slots(self):
+        """slots of the visited set (0 without a set)"""
+        return int(self._lib.cw_seen_slots(self._h))
+
+    def seen_insert(self, hdr, slot_pos, group=None, *, fields=None, out=None):
+        """Which of these records has the visited set not held before?  (cw_seen_insert: two kernels, no host round trip, capturable with expand(); no
+        env is touched.)  hdr [..., 16] / slot_pos [..., 8] as expand() takes and returns them (flattened to M): contiguous tensors on the env's device go
+        over in place -- no copy, no synchronisation --, anything else is validated on the host.  Two records are the same state if they are of one GROUP
+        and agree in agent, hold, both masks, the reward rule, the slot codes and the slot positions; the menu byte, step_num, flag bit 0 and the success
+        count do not count (include/craftingworld.h: THE KEY).  group: None (row j is of group j % num_envs -- its env, as expand() reads it), or an int32
+        tensor or integer array with the records' leading shape; a NEGATIVE entry: the row takes no part, nothing of it is written and it is not inserted.
+        -> {'fresh': bool [M], 'first': int32 [M]}: first[j] is -1 if the key was in the set before this call, else the smallest participating row of
+        this call with the same key (j itself for the row that brings it in); fresh[j] = (first[j] == j).  Afterwards every participating key is in the
+        set.  The result does not depend on scheduling.  A row that finds no slot (seen_overflow) or meets its tag under another key (seen_collisions) is
+        reported fresh and counted: the set never calls a new key seen.  fields: a subset of SEEN_FIELDS (default both).  out: a dict returned by an
+        earlier call with the same M and fields, written again (rows that take no part keep what it held)."""
+        names = _field_names(fields, SEEN_FIELDS, SEEN_FIELDS)
+        if hdr is None or slot_pos is None:
+            raise ValueError('seen_insert needs hdr and slot_pos')
+        m, lead, hdr, slot_pos, _ = self._records(hdr, slot_pos, None)
+        if group is not None and not self._in_place(group, (torch.int32,), lead, what='group tensor'):
+            g = as_numpy(group)
+            if g.dtype == np.bool_ or not np.issubdtype(g.dtype, np.integer) or tuple(g.shape) != lead:
+                raise ValueError('group must be integers of the records\' leading shape %s (int32 goes over in place), got %s %s' % (lead, g.dtype, g.shape))
+            if g.size and int(g.max()) >= 2 ** 31:
+                raise ValueError('group must fit int32, got %d' % int(g.max()))
+            group = torch.as_tensor(np.ascontiguousarray(np.maximum(g.astype(np.int64), -1), dtype=np.int32)).to(self.device)
+        out = self._out_dict(out, names, {'fresh': ((m,), torch.bool), 'first': ((m,), torch.int32)})
+        if m:
+            self._call('cw_seen_insert', group, hdr, slot_pos, m, C.byref(_out_struct(L.cw_seen_out, out)), keep=out)
+        return out
+
+    def reach(self, max_depth, hdr=None, slot_pos=None, env_of=None, *, max_rows=2 ** 22):
+        """The SHORTEST plan that ends in success, or "none within max_depth steps" -- exact, at depths plan() cannot reach: a breadth-first search over
+        STATES, not action strings (expand() + seen_insert() + torch compaction).  The start states follow plan()'s rules: without records the envs'
+        current states, else hdr [..., 16] / slot_pos [..., 8] / env_of (env j % num_envs or env_of[j]; a start row whose entry is negative or >= num_envs
+        takes no part and reports -1).  M0 start rows.
+        The engine's visited set is cleared (none reserved: seen_reserve(4 * max_rows)) and the start rows go in with group = their row number, so two
+        start rows are searched apart whatever they share.  Per level: expand() of the frontier; a successor whose reward is max_steps solves its start
+        row, which then leaves the search; a done successor is not expanded further (the time-out ends a branch); the rest go through seen_insert() and
+        the fresh ones form the next frontier.  ONE host synchronisation per level, for the frontier's size: the call is NOT capturable.  If the next
+        frontier would exceed max_rows the search stops before that level.
+        -> dict: 'distance' int32 [M0], the steps of a shortest plan that ends in success, -1 for none within the searched depth; 'plan' uint8
+        [max_depth, M0], that plan, zeros behind its end and for -1 rows -- it feeds simulate() as it is; 'first_action' uint8 [M0]; 'searched_depth' (an
+        int <= max_depth: every plan of at most that many steps has been considered); 'states' (seen_size afterwards); 'frontier' (a list: how many states each
+        level expanded).  Among equally short plans the one
+        returned is fixed by the smallest-row rule of seen_insert() and of the level's scan, so two calls agree -- it is NOT promised to be plan()'s
+        lexicographically smallest one.  The set is left filled: its keys are the states searched."""
+        D = _shoot_int(max_depth, 'max_depth', 1, SIMULATE_MAX_STEPS)
+        max_rows = _shoot_int(max_rows, 'max_rows', 1, 2 ** 27 // 6)
+        m0, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        dev, N = self.device, self.num_envs
+        if hdr is None:
+            hdr, slot_pos = self.hdr, self.slot_pos
+        hdr, slot_pos = hdr.reshape(m0, 16), slot_pos.reshape(m0, 8)
+        rows0 = torch.arange(m0, dtype=torch.int32, device=dev)
+        env0 = rows0 % N if env_of is None else env_of
+        part = (env0 >= 0) & (env0 < N)
+        if not self.seen_slots:
+            self.seen_reserve(4 * max_rows)
+        self.seen_clear()
+        dist = torch.full((m0,), -1, dtype=torch.int32, device=dev)
+        sol_action = torch.zeros((m0,), dtype=torch.int64, device=dev)
+        sol_parent = torch.zeros((m0,), dtype=torch.int64, device=dev)
+        plan = torch.zeros((D, m0), dtype=torch.uint8, device=dev)
+        active = part.clone()
+        if m0:
+            self.seen_insert(hdr, slot_pos, torch.where(part, rows0, -1), fields=('fresh',))
+        keep = torch.nonzero(part).reshape(-1)
+        f_hdr, f_pos, f_env, f_start = hdr[keep].contiguous(), slot_pos[keep].contiguous(), env0[keep].contiguous(), keep
+        links, sizes, searched = [], [], D
+        for d in range(1, D + 1):
+            F = int(f_start.numel())
+            if F == 0:                              # every branch has ended: nothing deeper exists
+                break
+            sizes.append(F)
+            r = self.expand(f_hdr, f_pos, f_env, fields=('reward', 'done', 'hdr', 'slot_pos'))
+            row = torch.arange(6 * F, dtype=torch.int64, device=dev)
+            parent = row % F
+            start = f_start[parent]
+            hit = (r['reward'].reshape(-1) == self.MAX_STEPS) & active[start]
+            best = torch.full((m0,), 6 * F, dtype=torch.int64, device=dev).scatter_reduce(0, start, torch.where(hit, row, 6 * F), 'amin')
+            new = best < 6 * F
+            dist = torch.where(new, d, dist)
+            sol_action, sol_parent = torch.where(new, best // F, sol_action), torch.where(new, best % F, sol_parent)
+            active = active & ~new
+            if d == D:
+                break
+            go = ~r['done'].reshape(-1) & active[start]
+            fresh = torch.zeros((6 * F,), dtype=torch.bool, device=dev)
+            s_hdr, s_pos = r['hdr'].reshape(6 * F, 16), r['slot_pos'].reshape(6 * F, 8)
+            self.seen_insert(s_hdr, s_pos, torch.where(go, start, -1).to(torch.int32), fields=('fresh',), out={'fresh': fresh})
+            nxt = torch.nonzero(fresh & go).reshape(-1)
+            if int(nxt.numel()) > max_rows:         # (the level's one synchronisation)
+                searched = d
+                break
+            par = parent[nxt]
+            links.append((par, nxt // F))
+            f_hdr, f_pos, f_env, f_start = s_hdr[nxt].contiguous(), s_pos[nxt].contiguous(), f_env[par].contiguous(), start[nxt]
+        # the plans, walked back level by level: cur is a solved row's state in the frontier of the level in hand
+        cur = torch.zeros((m0,), dtype=torch.int64, device=dev)
+        for lvl in range(len(links) + 1, 0, -1):
+            ends = dist == lvl
+            a, cur = torch.where(ends, sol_action, 0), torch.where(ends, sol_parent, cur)
+            if lvl <= len(links) and int(links[lvl - 1][0].numel()):
+                par, act = links[lvl - 1]
+                via = dist > lvl
+                at = torch.where(via, cur, 0)
+                a, cur = torch.where(via, act[at], a), torch.where(via, par[at], cur)
+            plan[lvl - 1] = a.to(torch.uint8)
+        return {'distance': dist, 'plan': plan, 'first_action': plan[0].clone(), 'searched_depth': searched, 'states': self.seen_size, 'frontier': sizes}
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

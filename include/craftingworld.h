@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -445,6 +445,56 @@ int cw_shoot(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const u
  * CW_ERR_INVALID, as for a null engine or out; n_states == 0 or n_rows == 0: CW_OK, nothing enqueued. */
 int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights,
                      const int32_t *samples, int32_t n_rows, uint8_t *out /* [T][n_rows][M] */, cw_stream_t stream);
+
+/* --- searching deep: "have I seen this state before?" -- a device-resident VISITED SET of packed records, filled by kernels (breadth-first search with duplicate
+ * detection, distance-to-goal labels, the "solvable within D steps" filter of a curriculum).  6^D action strings reach far fewer than 6^D states; cw_expand plus
+ * this set walk the states, not the strings.  The reference has no counterpart.
+ * THE KEY.  Two records of one GROUP are the same state if they agree in everything a step reads except the two step counters.  The 36-byte key is: group
+ *   (int32); hdr bytes 0-2 (agent row, agent col, hold); hdr bytes 4-7 (achieved mask, desired mask); bit 1 of hdr byte 10 (the subset reward rule); hdr bytes
+ *   12-15 (the eight slot codes); the 16 bytes of slot_pos.  NOT in the key: hdr byte 3 (the menu id: kept by a step, never read), hdr bytes 8-9 (step_num),
+ *   flags bit 0 and bits 2-15 (no step taken yet, the success count).  (csrc/cw_host.h: cwh_seen_key, shared by the kernels and the CPU tests.)
+ *   CONSEQUENCE: records with equal keys (the group being the env, or finer) have successors with equal keys under every action, and equal reward, changed and
+ *   achieved; done is equal except for its time-out term step_num >= max_steps.
+ *   The group says which records may be merged at all: by default the env index j % num_envs -- an episode's start positions decide its Move tasks --, or any
+ *   non-negative int32 of the caller's (a search from several start states of one env with different step budgets passes the start row).
+ * cw_seen_reserve: one set per engine, or a new one: everything seen is dropped.  `capacity` is the number of distinct keys the caller means to hold; the table
+ *   gets the next power of two >= 2 * capacity slots of 48 bytes (cw_seen_slots; 0 without a set); capacity == 0 frees it.  Synchronous; waits for this engine's
+ *   own work only, as cw_snapshot_reserve does.  CW_ERR_INVALID for capacity < 0 or above 2^28 or tag_bits outside 0 .. 63; CW_ERR_HIP when the allocation fails --
+ *   the engine is then left WITHOUT a set.  tag_bits: 0, a slot's tag is the full 64-bit hash of the key; 1 .. 63 truncates it to that many bits -- only speed
+ *   and the collisions counter depend on it (it lets tests and tools/measure_seen.py drive the same-tag-different-key path, which 64 bits never take in practice).
+ *   The set is not part of a checkpoint blob or of a snapshot row; cw_reset, cw_checkpoint_load and cw_seed_* leave it alone.
+ * cw_seen_clear: empties the set and resets its counters by ONE kernel (cw_seen_clear_kernel) on `stream`; capturable.
+ * cw_seen_counters: where the set's three counters live -- DEVICE uint64[3], read-only for callers, valid until the next cw_seen_reserve: [0] keys held,
+ *   [1] overflow, [2] collisions (below). */
+typedef struct cw_seen_out {   /* DEVICE pointers; a NULL field is not written; both NULL: CW_ERR_INVALID */
+    uint8_t *fresh;   /* [M]  1: this row brings its key into the set */
+    int32_t *first;   /* [M]  -1: the key was in the set BEFORE this call; else the smallest participating row of this call with the same key; 4-byte aligned */
+} cw_seen_out;
+/* cw_seen_insert: hdr [M][16] and slot_pos [M][8] are taken exactly as cw_expand takes records: device memory, 16-byte aligned, only read.  group: DEVICE
+ *   int32[M], only read, or NULL: row j is of group j % num_envs.  A NEGATIVE group entry: the row takes no part -- nothing of it is written, it is not inserted.
+ *   For a participating row j: first[j] = -1 if its key was in the set before this call; otherwise the smallest participating row of this call with the same
+ *   key -- j itself for the one row that brings the key in; fresh[j] = (first[j] == j).  After the call every participating key is in the set.
+ * The outputs are a function of the inputs and of the calls since the last clear, NOT of scheduling: the smallest row wins, whatever order the waves arrive in.
+ *   Two exceptions, both in the SAFE direction and both counted: counters[1] OVERFLOW -- a row found no slot within the probe bound (128 slots from its hash;
+ *   a set filled beyond its capacity) --, counters[2] COLLISIONS -- a row met a slot whose tag equals its own but whose key differs.  Such a row is reported
+ *   first = j, fresh = 1 and may not be remembered.  The opposite error is impossible by construction -- a key is reported as seen, or as a duplicate of row i,
+ *   only after a byte comparison with the stored key, or with record i --: a search on top of the set stays exact and at worst expands a state again.
+ *   counters[0] is the number of keys held.
+ * "Before this call" is told from "in this call" by an epoch word that lives in the set and advances ON THE DEVICE with every insert: a replayed graph behaves
+ *   like a repeated call.  2^36 - 1 inserts after a clear the epochs are used up: from then on every participating row is reported fresh and counted as
+ *   overflow, and nothing is inserted, until the next cw_seen_clear.
+ * PURE with respect to the engine: no env, stream, record, bank, frame or counters[0..7] of cw_buffer_table is read or written; the engine contributes its set,
+ *   num_envs for the default group and its stream bookkeeping.
+ * Enqueues TWO kernels (cw_seen_claim_kernel, cw_seen_resolve_kernel: one lane per row, grid-stride, atomics on the slot words, no lane ever waits for another)
+ *   on `stream` -- no host synchronisation, no allocation -- and can be captured into a HIP graph with cw_expand.  n_states == 0: CW_OK, nothing enqueued.
+ *   CW_ERR_STATE before the first cw_reset / cw_checkpoint_load and without a set.  CW_ERR_INVALID: a null engine, out, hdr or slot_pos, both fields NULL,
+ *   n_states < 0 or above 2^27, misaligned records (group and first: 4 bytes), an output overlapping the records, group or the other output.
+ *   (21x21, the 6 N successors of cw_expand, launch included: 31 us for 24 576 rows and 151 us for 393 216 into an empty set, 23 / 106 us for the same rows again; torch.unique over the same keys: 225 / 390 us, and it has no memory of earlier calls: tools/measure_seen.py, profiles/r12_seen.txt.) */
+int cw_seen_reserve(cw_engine *e, int64_t capacity, int32_t tag_bits);
+int cw_seen_clear(cw_engine *e, cw_stream_t stream);
+int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, const cw_seen_out *out, cw_stream_t stream);
+int cw_seen_counters(const cw_engine *e, const uint64_t **counters);   /* *counters = the DEVICE uint64[3]; CW_ERR_STATE (and NULL) without a set */
+size_t cw_seen_slots(const cw_engine *e);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
