@@ -79,6 +79,10 @@ class cw_seen_out(C.Structure):
     _fields_ = [('fresh', C.c_void_p), ('first', C.c_void_p)]
 
 
+class cw_reach_out(C.Structure):
+    _fields_ = [('distance', C.c_void_p), ('plan', C.c_void_p), ('first_action', C.c_void_p), ('frontier', C.c_void_p), ('searched_depth', C.c_void_p)]
+
+
 class cw_profile(C.Structure):
     _fields_ = [('steps', C.c_int32), ('ms_step_kernel', C.c_float), ('ms_reset_kernel', C.c_float),
                 ('ms_render_kernel', C.c_float), ('ms_render_kernel_max', C.c_float), ('ms_render_kernel_min', C.c_float),
@@ -119,6 +123,9 @@ ABI = {
     'cw_seen_insert': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_seen_out), _VP]),
     'cw_seen_counters': (C.c_int, [_VP, C.POINTER(_VP)]),
     'cw_seen_slots': (C.c_size_t, [_VP]),
+    'cw_reach_reserve': (C.c_int, [_VP, C.c_int64, C.c_int32]),
+    'cw_reach_bytes': (C.c_size_t, [_VP]),
+    'cw_reach': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_reach_out), _VP]),
     'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
@@ -171,6 +178,9 @@ CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
 CWH_SHOOT_MAX_SAMPLES, CWH_SHOOT_MAX_WORK = 65536, 1 << 32
 CWH_SEEN_OK, CWH_SEEN_NO_RECORDS, CWH_SEEN_NO_FIELD, CWH_SEEN_N_STATES, CWH_SEEN_ALIGN, CWH_SEEN_OVERLAP = range(6)
 CWH_SEEN_KEY_WORDS, CWH_SEEN_MAX_CAPACITY, CWH_SEEN_PROBES = 9, 1 << 28, 128
+CWH_REACH_OK, CWH_REACH_NO_FIELD, CWH_REACH_N_STATES, CWH_REACH_DEPTH, CWH_REACH_PAIR, CWH_REACH_ENV_OF, CWH_REACH_OWN_STATES, CWH_REACH_ALIGN, \
+    CWH_REACH_OVERLAP = range(9)
+CWH_REACH_CHUNK, CWH_REACH_MAX_ROWS, CWH_REACH_MAX_DEPTH, CWH_REACH_BLOCKS_PER_CU, CWH_REACH_SECTIONS = 4096, (2 ** 28 - 1) // 6 - 63, 32767, 8, 18
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -205,6 +215,13 @@ HOST_HELPERS = {
     'cwh_seen_hash_of': (C.c_uint64, [_VP]),
     'cwh_seen_slots_of': (C.c_int64, [C.c_int64]),
     'cwh_seen_args': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64]),
+    'cwh_reach_rows_of': (C.c_int64, [C.c_int64]),
+    'cwh_reach_chunks_of': (C.c_int64, [C.c_int64]),
+    'cwh_reach_grid_of': (C.c_int64, [C.c_int64, C.c_int32]),
+    'cwh_reach_layout': (C.c_int64, [C.c_int64, C.c_int32, _VP]),
+    'cwh_reach_bytes_of': (C.c_int64, [C.c_int64, C.c_int32]),
+    'cwh_reach_args': (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                 C.c_uint64]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),

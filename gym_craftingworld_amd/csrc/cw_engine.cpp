@@ -46,6 +46,8 @@ hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsig
 hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const CwSeen *S, const int32_t *group, const uint4 *hdr, const uint4 *pos, int n_states,
                                   uint8_t *fresh, int32_t *first, hipStream_t st);
 hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st);
+hipError_t cwk_launch_reach(const CwParams *P, const CwTuning *T, const CwSeen *S, const CwReach *R, const int32_t *env_of, const uint4 *hdr, const uint4 *pos,
+                            int n_states, int depth, const CwReachOut *O, hipStream_t st);
 hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
                                int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
@@ -109,6 +111,9 @@ struct cw_engine {
     void *seen = nullptr;              // the visited set's one allocation (cw_seen_reserve), or null: none reserved
     CwSeen Sn{};                       // ... its arrays (cw_layout.h)
     int64_t seen_slots = 0;
+    void *reach = nullptr;             // cw_reach's workspace, one allocation (cw_reach_reserve), or null: none reserved
+    CwReach Rc{};                      // ... its sections (cw_host.cpp: cwh_reach_layout)
+    size_t reach_bytes = 0;
     int n = 0, S = 0, ncell = 0, K = 0;
     // resident stepper of the single-env loop (cw_step_resident; cw_kernels.hip: cw_resident_kernel)
     CwResident *res = nullptr;         // pinned coherent host memory, or null (engine not eligible)
@@ -224,7 +229,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_reach, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -667,6 +672,7 @@ int cw_destroy(cw_engine *e)
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->bank) (void)hipFree(e->bank);
     if (e->seen) (void)hipFree(e->seen);
+    if (e->reach) (void)hipFree(e->reach);
     for (void *p : e->host_allocs) (void)hipHostFree(p);
     delete e;
     return CW_OK;
@@ -1170,6 +1176,103 @@ int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const
     if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_seen_insert(&e->P, &e->tune, &e->Sn, group, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out->fresh, out->first,
                                    (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ reach: breadth-first search without a host round trip
+// The workspace is one allocation of the engine's, like the visited set and as far from every checkpoint blob and snapshot row; its sections are
+// cw_host.cpp's (cwh_reach_layout).  Nothing of it needs an initial value: every call writes what it reads.
+static void reach_free(cw_engine *e)
+{
+    if (e->reach) (void)hipFree(e->reach);
+    e->reach = nullptr;
+    e->Rc = CwReach{};
+    e->reach_bytes = 0;
+}
+
+int cw_reach_reserve(cw_engine *e, int64_t max_rows, int32_t max_depth)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_reach_reserve: null engine");
+    uint64_t at[CWH_REACH_SECTIONS];
+    const int64_t bytes = max_rows == 0 ? 0 : cwh_reach_layout(max_rows, max_depth, at);
+    if (bytes < 0)
+        return fail(CW_ERR_INVALID, "cw_reach_reserve: max_rows = %lld must be 0 .. %lld and max_depth = %d 1 .. %d", (long long)max_rows,
+                    (long long)CWH_REACH_MAX_ROWS, max_depth, CWH_REACH_MAX_DEPTH);
+    SyncEntry in(e);                                 // (the engine's own work: a search in flight uses the workspace about to go)
+    if (in.rc != CW_OK) return in.rc;
+    reach_free(e);
+    if (bytes == 0) return CW_OK;
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CW_ERR_HIP, "cw_reach_reserve: no device memory for %lld bytes (%lld rows, %d levels)", (long long)bytes, (long long)max_rows, max_depth);
+    }
+    char *const b = (char *)p;
+    CwReach R{};
+    R.ctl = (int32_t *)(b + at[CWH_REACH_S_CTL]);
+    R.sizes = R.ctl + CWH_REACH_CTL_WORDS;
+    R.chunk = R.sizes + max_depth + 1;
+    for (int k = 0; k < 2; k++) {
+        R.f_hdr[k] = (uint4 *)(b + at[CWH_REACH_S_F_HDR0 + 4 * k]);
+        R.f_pos[k] = (uint4 *)(b + at[CWH_REACH_S_F_POS0 + 4 * k]);
+        R.f_env[k] = (int32_t *)(b + at[CWH_REACH_S_F_ENV0 + 4 * k]);
+        R.f_start[k] = (int32_t *)(b + at[CWH_REACH_S_F_START0 + 4 * k]);
+    }
+    R.s_hdr = (uint4 *)(b + at[CWH_REACH_S_HDR]);
+    R.s_pos = (uint4 *)(b + at[CWH_REACH_S_POS]);
+    R.s_grp = (int32_t *)(b + at[CWH_REACH_S_GRP]);
+    R.s_fresh = (uint8_t *)(b + at[CWH_REACH_S_FRESH]);
+    R.links = (int32_t *)(b + at[CWH_REACH_S_LINKS]);
+    R.dist = (int32_t *)(b + at[CWH_REACH_S_DIST]);
+    R.sol = (int32_t *)(b + at[CWH_REACH_S_SOL]);
+    R.bid = (int32_t *)(b + at[CWH_REACH_S_BID]);
+    R.active = (uint8_t *)(b + at[CWH_REACH_S_ACTIVE]);
+    R.max_rows = (int32_t)max_rows;
+    R.max_depth = max_depth;
+    e->reach = p;
+    e->Rc = R;
+    e->reach_bytes = (size_t)bytes;
+    return CW_OK;
+}
+
+size_t cw_reach_bytes(const cw_engine *e)
+{
+    if (!e) { (void)fail(CW_ERR_INVALID, "cw_reach_bytes: null engine"); return 0; }
+    return e->reach ? e->reach_bytes : 0;
+}
+
+// Checks (cwh_reach_args, tested on the CPU), then kernels only: no wait, no allocation, the same call whether it runs or is captured.  Of the engine the
+// set and the workspace are written, nothing else: a start row whose env index is outside the batch takes no part and is NOT counted in counters[7].
+int cw_reach(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t max_depth, const cw_reach_out *out,
+             cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_reach: null %s", !e ? "engine" : "out");
+    switch (cwh_reach_args(e->n, (uint64_t)(uintptr_t)env_of, (uint64_t)(uintptr_t)hdr_in, (uint64_t)(uintptr_t)slot_pos_in, n_states, max_depth,
+                           (uint64_t)(uintptr_t)out->distance, (uint64_t)(uintptr_t)out->plan, (uint64_t)(uintptr_t)out->first_action,
+                           (uint64_t)(uintptr_t)out->frontier, (uint64_t)(uintptr_t)out->searched_depth)) {
+    case CWH_REACH_OK: break;
+    case CWH_REACH_NO_FIELD: return fail(CW_ERR_INVALID, "cw_reach: every field of out is null");
+    case CWH_REACH_N_STATES: return fail(CW_ERR_INVALID, "cw_reach: n_states = %d must be 0 .. %lld", n_states, (long long)CWH_REACH_MAX_ROWS);
+    case CWH_REACH_DEPTH: return fail(CW_ERR_INVALID, "cw_reach: max_depth = %d must be 1 .. %d", max_depth, CWH_REACH_MAX_DEPTH);
+    case CWH_REACH_PAIR: return fail(CW_ERR_INVALID, "cw_reach: hdr_in and slot_pos_in go together");
+    case CWH_REACH_ENV_OF: return fail(CW_ERR_INVALID, "cw_reach: env_of needs hdr_in and slot_pos_in");
+    case CWH_REACH_OWN_STATES: return fail(CW_ERR_INVALID, "cw_reach: n_states = %d must be num_envs = %d without records", n_states, e->n);
+    case CWH_REACH_ALIGN:
+        return fail(CW_ERR_INVALID, "cw_reach: hdr_in / slot_pos_in must be 16-byte aligned, env_of / out->distance / frontier / searched_depth 4-byte aligned");
+    default: return fail(CW_ERR_INVALID, "cw_reach: an output overlaps the records, env_of or another output");
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_reach called before cw_reset");
+    if (!e->seen) return fail(CW_ERR_STATE, "cw_reach: no set reserved (cw_seen_reserve)");
+    if (!e->reach) return fail(CW_ERR_STATE, "cw_reach: no workspace reserved (cw_reach_reserve)");
+    if (n_states > e->Rc.max_rows || max_depth > e->Rc.max_depth)
+        return fail(CW_ERR_STATE, "cw_reach: n_states = %d, max_depth = %d, the workspace holds %d rows and %d levels (cw_reach_reserve)", n_states, max_depth,
+                    e->Rc.max_rows, e->Rc.max_depth);
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    CwReachOut O;
+    O.distance = out->distance; O.plan = out->plan; O.first_action = out->first_action; O.frontier = out->frontier; O.searched_depth = out->searched_depth;
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    HIP_TRY(cwk_launch_reach(&e->P, &e->tune, &e->Sn, &e->Rc, env_of, h, p, n_states, max_depth, &O, (hipStream_t)stream));
     return in.done();
 }
 

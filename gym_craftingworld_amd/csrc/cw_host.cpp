@@ -278,6 +278,49 @@ int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_sta
     return CWH_SEEN_OK;
 }
 
+// ------------------------------------------------------------------------------ cw_reach: the rows of a level, the workspace's sections, the argument rules
+int64_t cwh_reach_rows_of(int64_t f) { return cwh_reach_rows(f); }
+int64_t cwh_reach_chunks_of(int64_t rows) { return cwh_reach_chunks(rows); }
+int64_t cwh_reach_grid_of(int64_t items, int32_t n_cu) { return cwh_reach_grid(items, n_cu); }
+
+int64_t cwh_reach_layout(int64_t max_rows, int32_t max_depth, uint64_t *offsets)
+{
+    if (max_rows < 1 || max_rows > CWH_REACH_MAX_ROWS || max_depth < 1 || max_depth > CWH_REACH_MAX_DEPTH) return -1;
+    const uint64_t R = (uint64_t)max_rows, D = (uint64_t)max_depth, rows = (uint64_t)cwh_reach_rows(max_rows), chunks = (uint64_t)cwh_reach_chunks((int64_t)rows);
+    const uint64_t bytes[CWH_REACH_SECTIONS] = {4 * (CWH_REACH_CTL_WORDS + D + 1 + chunks), 16 * R, 16 * R, 4 * R, 4 * R, 16 * R, 16 * R, 4 * R, 4 * R,
+                                                16 * rows, 16 * rows, 4 * rows, chunks * CWH_REACH_CHUNK, 4 * R * (D - 1), 4 * R, 4 * R, 4 * R, R};
+    uint64_t at = 0;
+    for (int i = 0; i < CWH_REACH_SECTIONS; i++) {
+        if (offsets) offsets[i] = at;
+        at += (bytes[i] + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
+    }
+    return (int64_t)at;
+}
+int64_t cwh_reach_bytes_of(int64_t max_rows, int32_t max_depth) { return cwh_reach_layout(max_rows, max_depth, nullptr); }
+
+int cwh_reach_args(int32_t num_envs, uint64_t env_of, uint64_t hdr_in, uint64_t slot_pos_in, int32_t n_states, int32_t max_depth, uint64_t distance,
+                   uint64_t plan, uint64_t first_action, uint64_t frontier, uint64_t searched_depth)
+{
+    if (!distance && !plan && !first_action && !frontier && !searched_depth) return CWH_REACH_NO_FIELD;
+    if (n_states < 0 || n_states > CWH_REACH_MAX_ROWS) return CWH_REACH_N_STATES;
+    if (max_depth < 1 || max_depth > CWH_REACH_MAX_DEPTH) return CWH_REACH_DEPTH;
+    if (!hdr_in != !slot_pos_in) return CWH_REACH_PAIR;
+    if (env_of && !hdr_in) return CWH_REACH_ENV_OF;
+    if (!hdr_in && n_states != num_envs) return CWH_REACH_OWN_STATES;
+    if ((hdr_in & 15u) || (slot_pos_in & 15u) || (env_of & 3u) || (distance & 3u) || (frontier & 3u) || (searched_depth & 3u)) return CWH_REACH_ALIGN;
+    const uint64_t m = (uint64_t)n_states, d = (uint64_t)max_depth;
+    const uint64_t outs[5][2] = {{distance, 4 * m}, {plan, d * m}, {first_action, m}, {frontier, 4 * d}, {searched_depth, 4}};
+    const uint64_t ins[3][2] = {{hdr_in, 16 * m}, {slot_pos_in, 16 * m}, {env_of, 4 * m}};
+    for (int o = 0; o < 5; o++) {
+        if (!outs[o][0]) continue;
+        for (int i = 0; i < 3; i++)
+            if (ins[i][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_REACH_OVERLAP;
+        for (int q = o + 1; q < 5; q++)
+            if (outs[q][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], outs[q][0], outs[q][1])) return CWH_REACH_OVERLAP;
+    }
+    return CWH_REACH_OK;
+}
+
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule
 static double period_ns(int32_t sweep_waves, double tb_per_s) { return (double)sweep_waves * 4096.0 / (tb_per_s * 1e12) * 1e9; }
 void cwh_sweep_periods(double rate, int32_t sweep_waves, double head_notch, double busy_notch, int32_t *period16, int32_t *period16_head, int32_t *period16_busy)

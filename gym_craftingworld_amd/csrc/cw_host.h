@@ -222,6 +222,48 @@ int64_t cwh_seen_slots_of(int64_t capacity);
 enum { CWH_SEEN_OK = 0, CWH_SEEN_NO_RECORDS = 1, CWH_SEEN_NO_FIELD = 2, CWH_SEEN_N_STATES = 3, CWH_SEEN_ALIGN = 4, CWH_SEEN_OVERLAP = 5 };
 int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_states, uint64_t fresh, uint64_t first);
 
+// ---- cw_reach: breadth-first search on the device (cw_reach_reserve / cw_reach).  THE ROWS of a level over a frontier of F states: row a * Fp + j is action a
+// on frontier state j, Fp = F rounded up to a wavefront, so that no wave straddles two actions; rows j >= F of an action take no part.  The order is the one
+// a * F + j gives.  The row is the row field of the visited set's bids: 6 * (max_rows + 63) < 2^CWH_SEEN_ROW_BITS is the cap on max_rows.
+// max_depth: 1 .. CWH_REACH_MAX_DEPTH = CWH_SIM_MAX_STEPS (a plan feeds cw_simulate); the workspace then stays below 2^43 bytes, far inside int64.
+#define CWH_REACH_CHUNK 4096        // rows a workgroup of 256 lanes compacts at a time: 16 flag bytes (one 16-byte load) a lane
+#define CWH_REACH_MAX_ROWS (((1ll << CWH_SEEN_ROW_BITS) - 1) / 6 - 63)
+#define CWH_REACH_MAX_DEPTH CWH_SIM_MAX_STEPS
+#define CWH_REACH_BLOCKS_PER_CU 8   // workgroups of 256 per CU at most: the grid-stride kernels of a level (the visited set's own shape)
+static inline CWH_HOST_DEVICE int64_t cwh_reach_padded(int64_t f) { return (f + CW_WAVE - 1) / CW_WAVE * CW_WAVE; }
+static inline CWH_HOST_DEVICE int64_t cwh_reach_rows(int64_t f) { return 6 * cwh_reach_padded(f); }                       // rows of a level over F states
+static inline CWH_HOST_DEVICE int64_t cwh_reach_chunks(int64_t rows) { return (rows + CWH_REACH_CHUNK - 1) / CWH_REACH_CHUNK; }
+// workgroups of 256 lanes for `items` items, one lane each, grid-stride: ceil(items / 256), 1 at least, n_cu * CWH_REACH_BLOCKS_PER_CU at most
+static inline int64_t cwh_reach_grid(int64_t items, int32_t n_cu)
+{
+    const int64_t want = (items + 255) / 256, most = (int64_t)n_cu * CWH_REACH_BLOCKS_PER_CU;
+    return want < most ? (want < 1 ? 1 : want) : most;
+}
+int64_t cwh_reach_rows_of(int64_t f);                  // (the same, exported for the CPU tests)
+int64_t cwh_reach_chunks_of(int64_t rows);
+int64_t cwh_reach_grid_of(int64_t items, int32_t n_cu);
+// THE WORKSPACE: one allocation, its sections in this order, each starting on a CWH_SNAP_ALIGN boundary.  ctl: CWH_REACH_CTL_WORDS int32 (the stop flag, the
+// searched depth), then the frontier's size per level [max_depth + 1] and the scan's scratch, one int32 per chunk of the largest level.  Two frontiers (record,
+// env, start row: 40 bytes a row), the successors of one level (record, group, fresh flag: 37 bytes for each of the 6 * padded(max_rows) rows, the flags padded
+// to whole chunks), the links of every level but the last (parent << 3 | action: 4 bytes a row and level), and per start row dist, the solving link, the bid
+// (the smallest solving row of the level in hand) and active: 13 bytes.  Writes CWH_REACH_SECTIONS offsets (may be null); -> the bytes, -1 outside the limits
+// (max_rows 1 .. CWH_REACH_MAX_ROWS, max_depth 1 .. CWH_REACH_MAX_DEPTH).
+#define CWH_REACH_CTL_WORDS 64
+enum { CWH_REACH_STOP = 0, CWH_REACH_SEARCHED = 1 };
+enum { CWH_REACH_S_CTL = 0, CWH_REACH_S_F_HDR0, CWH_REACH_S_F_POS0, CWH_REACH_S_F_ENV0, CWH_REACH_S_F_START0, CWH_REACH_S_F_HDR1, CWH_REACH_S_F_POS1,
+       CWH_REACH_S_F_ENV1, CWH_REACH_S_F_START1, CWH_REACH_S_HDR, CWH_REACH_S_POS, CWH_REACH_S_GRP, CWH_REACH_S_FRESH, CWH_REACH_S_LINKS, CWH_REACH_S_DIST,
+       CWH_REACH_S_SOL, CWH_REACH_S_BID, CWH_REACH_S_ACTIVE, CWH_REACH_SECTIONS };
+int64_t cwh_reach_layout(int64_t max_rows, int32_t max_depth, uint64_t *offsets);
+int64_t cwh_reach_bytes_of(int64_t max_rows, int32_t max_depth);
+// the argument rules of cw_reach, in the order they are tested; addresses as integers (0: null): some output (CWH_REACH_NO_FIELD), 0 <= n_states <=
+// CWH_REACH_MAX_ROWS (CWH_REACH_N_STATES), 1 <= max_depth <= CWH_REACH_MAX_DEPTH (CWH_REACH_DEPTH), hdr_in and slot_pos_in together (CWH_REACH_PAIR), env_of
+// only with them (CWH_REACH_ENV_OF), without them n_states = num_envs (CWH_REACH_OWN_STATES), hdr_in and slot_pos_in 16-byte aligned and env_of, distance,
+// frontier, searched_depth 4-byte aligned (CWH_REACH_ALIGN), no output sharing a byte with hdr_in, slot_pos_in, env_of or another output (CWH_REACH_OVERLAP)
+enum { CWH_REACH_OK = 0, CWH_REACH_NO_FIELD = 1, CWH_REACH_N_STATES = 2, CWH_REACH_DEPTH = 3, CWH_REACH_PAIR = 4, CWH_REACH_ENV_OF = 5, CWH_REACH_OWN_STATES = 6,
+       CWH_REACH_ALIGN = 7, CWH_REACH_OVERLAP = 8 };
+int cwh_reach_args(int32_t num_envs, uint64_t env_of, uint64_t hdr_in, uint64_t slot_pos_in, int32_t n_states, int32_t max_depth, uint64_t distance,
+                   uint64_t plan, uint64_t first_action, uint64_t frontier, uint64_t searched_depth);
+
 // ---- the GUARD of the sweep's clock as a pure state machine (cw_engine.cpp: sweep_guard_tick feeds it one timed sweep at a time; nothing here
 // touches HIP).  Rates in TB/s, times in ms.  DESIGN.md 4.3; the constants are the ones round 4/5 measured (profiles/r04_clock.txt, r05_experiments.txt).
 typedef struct cwh_guard {

@@ -24,6 +24,8 @@
 //                     integer mix (no action tensor), G lanes per state and a shuffle reduction; cw_shoot_actions_kernel decodes the draws.  Pure.
 //   cw_seen_claim_kernel / cw_seen_resolve_kernel  the visited set of such records: which of M rows brings a key the set has not held, and which is the first
 //                     of its key in the call -- an open-addressed table, one lane per row, atomics on the slot words and no wait; cw_seen_clear_kernel empties it.
+//   cw_reach_*_kernel  breadth-first search over such records without a host round trip: expansion, the set's two kernels, a stable compaction (count, scan,
+//                     scatter) and the bookkeeping of the start rows, level after level; the frontier's size lives in device memory and nothing waits.
 //   cw_render_pieces_kernel  render() of ray.py:442-520 (and the AltObs raster) for a whole frame ARRAY as a CLOCKED sweep of aligned 4-KiB
 //                     pieces: a zero fill plus the few lit bytes of the frames a piece overlaps, at a set rate.  The roofline kernel.
 //   cw_rollout_kernel persistent: T steps of every env in one launch (state-only mode).
@@ -1020,10 +1022,12 @@ __global__ __launch_bounds__(256) void cw_shoot_actions_kernel(int n_states, int
 //                           so a replayed graph tells "before this call" from "in this call" like a repeated call does.
 // Both are latency-bound random access: 8-byte atomics resolved in L2, no LDS, as many waves in flight as the card holds.  The repeated call (every key held)
 // issues no atomic at all: a tag or an earlier epoch's owner read by a device-scope load is final.  Neither kernel reads or writes anything of the engine.
-__device__ __forceinline__ bool seen_key_of_row(const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int j,
-                                                int n_envs, uint32_t key[CWH_SEEN_KEY_WORDS])
+// The group of row j is whatever `group_of(j)` says (negative: the row takes no part): cw_seen_insert's own array or default, or cw_reach's.
+template <typename GroupFn>
+__device__ __forceinline__ bool seen_key_of_row(GroupFn group_of, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int j,
+                                                uint32_t key[CWH_SEEN_KEY_WORDS])
 {
-    const int32_t g = group ? group[j] : (int32_t)((uint32_t)j % (uint32_t)n_envs);
+    const int32_t g = group_of(j);
     if (g < 0) return false;
     const uint4 h = hdr_in[j], p = pos_in[j];
     const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, pw[4] = {p.x, p.y, p.z, p.w};
@@ -1035,15 +1039,18 @@ __device__ __forceinline__ uint4 seen_key_a(const uint32_t key[CWH_SEEN_KEY_WORD
 __device__ __forceinline__ uint4 seen_key_b(const uint32_t key[CWH_SEEN_KEY_WORDS]) { return make_uint4(key[5], key[6], key[7], key[8]); }
 __device__ __forceinline__ bool same4(const uint4 &a, const uint4 &b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
 
-__global__ __launch_bounds__(256) void cw_seen_claim_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
-                                                            const uint4 *__restrict__ pos_in, int n_states, int n_envs)
+// The two kernels' bodies, over rows 0 .. n_rows - 1 of (group_of, hdr_in, pos_in): shared by cw_seen_insert's kernels and cw_reach's, whose row count and
+// groups live in device memory.  Every workgroup of the launch runs them to the end, whatever n_rows is: the ticket counts workgroups.
+template <typename GroupFn>
+__device__ __forceinline__ void seen_claim_rows(const CwSeen &S, GroupFn group_of, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in,
+                                                size_t n_rows)
 {
     const unsigned long long epoch = S.ctl[CW_SEEN_EPOCH];
-    if (epoch > CWH_SEEN_MAX_EPOCH) return;          // (the epochs are used up: cw_seen_resolve_kernel reports every row as overflow until the next clear)
-    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < (size_t)n_states; jj += (size_t)gridDim.x * blockDim.x) {
+    if (epoch > CWH_SEEN_MAX_EPOCH) return;          // (the epochs are used up: the resolve kernel reports every row as overflow until the next clear)
+    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < n_rows; jj += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)jj;
         uint32_t key[CWH_SEEN_KEY_WORDS];
-        if (!seen_key_of_row(group, hdr_in, pos_in, j, n_envs, key)) continue;
+        if (!seen_key_of_row(group_of, hdr_in, pos_in, j, key)) continue;
         const unsigned long long hash = cwh_seen_hash(key), tag = cwh_seen_tag(hash, S.tag_bits);
         const unsigned long long bid = (epoch << CWH_SEEN_ROW_BITS) | (unsigned long long)j;
         for (int p = 0; p < S.probes; p++) {
@@ -1061,17 +1068,17 @@ __global__ __launch_bounds__(256) void cw_seen_claim_kernel(CwSeen S, const int3
     }
 }
 
-__global__ __launch_bounds__(256) void cw_seen_resolve_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
-                                                              const uint4 *__restrict__ pos_in, int n_states, int n_envs, uint8_t *__restrict__ fresh,
-                                                              int32_t *__restrict__ first)
+template <typename GroupFn>
+__device__ __forceinline__ void seen_resolve_rows(const CwSeen &S, GroupFn group_of, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in,
+                                                  size_t n_rows, uint8_t *__restrict__ fresh, int32_t *__restrict__ first)
 {
     const unsigned long long epoch = S.ctl[CW_SEEN_EPOCH];
     const bool spent = epoch > CWH_SEEN_MAX_EPOCH;
     uint32_t n_won = 0, n_overflow = 0, n_collision = 0;
-    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < (size_t)n_states; jj += (size_t)gridDim.x * blockDim.x) {
+    for (size_t jj = (size_t)blockIdx.x * blockDim.x + threadIdx.x; jj < n_rows; jj += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)jj;
         uint32_t key[CWH_SEEN_KEY_WORDS];
-        if (!seen_key_of_row(group, hdr_in, pos_in, j, n_envs, key)) continue;
+        if (!seen_key_of_row(group_of, hdr_in, pos_in, j, key)) continue;
         const unsigned long long hash = cwh_seen_hash(key), tag = cwh_seen_tag(hash, S.tag_bits);
         int32_t found = -1;
         for (int p = 0; p < S.probes && !spent; p++) {
@@ -1096,7 +1103,7 @@ __global__ __launch_bounds__(256) void cw_seen_resolve_kernel(CwSeen S, const in
                     n_won++;
                 } else if (i >= 0 && i < j) {                                         // (i < j always: the owner is the smallest bidder)
                     uint32_t other[CWH_SEEN_KEY_WORDS];
-                    bool eq = seen_key_of_row(group, hdr_in, pos_in, i, n_envs, other);
+                    bool eq = seen_key_of_row(group_of, hdr_in, pos_in, i, other);
                     for (int k = 0; k < CWH_SEEN_KEY_WORDS; k++) eq = eq && other[k] == key[k];
                     if (eq) res = i; else n_collision++;
                 } else {
@@ -1129,6 +1136,19 @@ __global__ __launch_bounds__(256) void cw_seen_resolve_kernel(CwSeen S, const in
     }
 }
 
+__global__ __launch_bounds__(256) void cw_seen_claim_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
+                                                            const uint4 *__restrict__ pos_in, int n_states, int n_envs)
+{
+    seen_claim_rows(S, [=](int j) { return group ? group[j] : (int32_t)((uint32_t)j % (uint32_t)n_envs); }, hdr_in, pos_in, (size_t)n_states);
+}
+
+__global__ __launch_bounds__(256) void cw_seen_resolve_kernel(CwSeen S, const int32_t *__restrict__ group, const uint4 *__restrict__ hdr_in,
+                                                              const uint4 *__restrict__ pos_in, int n_states, int n_envs, uint8_t *__restrict__ fresh,
+                                                              int32_t *__restrict__ first)
+{
+    seen_resolve_rows(S, [=](int j) { return group ? group[j] : (int32_t)((uint32_t)j % (uint32_t)n_envs); }, hdr_in, pos_in, (size_t)n_states, fresh, first);
+}
+
 // cw_seen_clear: every slot empty (tag 0, owner all ones; the keys stay, unread), the counters, the epoch and the ticket 0
 __global__ __launch_bounds__(256) void cw_seen_clear_kernel(CwSeen S)
 {
@@ -1138,6 +1158,241 @@ __global__ __launch_bounds__(256) void cw_seen_clear_kernel(CwSeen S)
         S.owner[s] = ~0ull;
     }
     if (blockIdx.x == 0 && threadIdx.x < CW_SEEN_CTL_WORDS) S.ctl[threadIdx.x] = 0ull;
+}
+
+// ------------------------------------------------------------------------------------ reach: breadth-first search without a host round trip
+// cw_reach: VecEnv.reach()'s levels as kernels whose launch shapes do not depend on the frontier -- its size lives in the workspace (CwReach, cw_layout.h:
+// sizes[k], written by the scan that closes level k) and every kernel of a level reads it from there, so the host only enqueues.  A level d over frontier
+// d - 1 of F states (THE ROWS: cw_host.h):
+//   cw_reach_expand_kernel    step_env for the 6 * Fp rows, the action uniform across a wave and a literal (cw_expand_kernel's trick); writes the successor
+//                             record, its group (the start row; -1: done, or no part) and fresh = 0; a row whose reward is max_steps bids for its start
+//                             row with atomicMin(bid[start], row) while that start row is active
+//   cw_reach_claim_kernel / cw_reach_resolve_kernel   the visited set's own two kernels (seen_claim_rows, seen_resolve_rows) over those rows; a row of a
+//                             start row that has a BID takes no part -- the bids are complete when the expansion has ended and change no more inside the level
+//   cw_reach_count_kernel     fresh rows per chunk of CWH_REACH_CHUNK rows (16 flag bytes a lane, one load)
+//   cw_reach_scan_kernel      ONE workgroup: the chunk counts become what lies ahead of each chunk; their sum is the next frontier's size -- or, above
+//                             max_rows, the search stops: size 0, the stop flag, searched_depth = d
+//   cw_reach_scatter_kernel   each chunk again: a lane's place is its chunk's base plus the workgroup's prefix, so the fresh rows land in row order; record,
+//                             env, start row and the link (parent << 3 | action) go to the other frontier buffer
+//   cw_reach_settle_kernel    one lane per start row: a bid becomes dist = d, the solving link and inactive, and the bid is cleared for the next level
+// The last level runs its expansion and settles; nothing is inserted.  Before the first level cw_reach_start_kernel marks the participating start rows, the
+// set's kernels insert them (group = row) and count / scan / scatter compact them into frontier 0; after the last cw_reach_walk_kernel follows every solved
+// start row's links back, one lane per start row, and copies the sizes out.
+// NOTHING WAITS: no lane or workgroup waits for another anywhere, every loop's bound is a launch argument or one word read from the workspace, and a kernel
+// boundary is the only grid-wide ordering.  A level over an empty frontier -- the search has ended or stopped -- costs its launches and nothing else.
+
+// the rows of the kernels between two frontiers: the start rows ahead of level 1 (level 0), else THE ROWS of the level's frontier
+__device__ __forceinline__ int reach_rows(const CwReach &R, int level, int n_states)
+{
+    return level == 0 ? n_states : (int)cwh_reach_rows(min(max(R.sizes[level - 1], 0), R.max_rows));
+}
+// the group of a successor row as the set's kernels see it
+#define CW_REACH_GROUP(R) [=](int r) { int32_t g = (R).s_grp[r]; if (g >= 0 && (R).bid[g] != CW_REACH_NONE) g = -1; return g; }
+
+// exclusive prefix of v over the workgroup's lanes and their sum: a wave scan by shuffles, the waves' sums through LDS (lds: one int per wave)
+__device__ __forceinline__ int reach_block_scan(int v, int *lds, int &total)
+{
+    const int lane = (int)(threadIdx.x & (CW_WAVE - 1)), w = (int)(threadIdx.x / CW_WAVE), nw = (int)(blockDim.x / CW_WAVE);
+    int inc = v;
+    for (int d = 1; d < CW_WAVE; d <<= 1) {
+        const int o = __shfl_up(inc, d, CW_WAVE);
+        if (lane >= d) inc += o;
+    }
+    if (lane == CW_WAVE - 1) lds[w] = inc;
+    __syncthreads();
+    int base = 0, sum = 0;
+    for (int k = 0; k < nw; k++) {
+        const int x = lds[k];
+        base += k < w ? x : 0;
+        sum += x;
+    }
+    __syncthreads();                                 // (the next round writes lds again)
+    total = sum;
+    return base + inc - v;
+}
+// a lane's 16 flag bytes of chunk c (rows r0 .. r0 + 15, r0 = c * CWH_REACH_CHUNK + 16 * lane) as four words of 0 / 1 bytes, rows at or above n cleared
+__device__ __forceinline__ uint4 reach_flags(const CwReach &R, int c, int n, int &r0)
+{
+    r0 = c * CWH_REACH_CHUNK + 16 * (int)threadIdx.x;
+    const uint4 f = *(const uint4 *)(R.s_fresh + r0);
+    const int valid = min(max(n - r0, 0), 16);
+    auto keep = [&](uint32_t w, int k) { const int v = min(max(valid - 4 * k, 0), 4); return w & 0x01010101u & (v >= 4 ? 0xFFFFFFFFu : (1u << (8 * v)) - 1u); };
+    return make_uint4(keep(f.x, 0), keep(f.y, 1), keep(f.z, 2), keep(f.w, 3));
+}
+__device__ __forceinline__ int reach_flag_count(const uint4 &f) { return __popc(f.x) + __popc(f.y) + __popc(f.z) + __popc(f.w); }
+
+__global__ __launch_bounds__(256) void cw_reach_start_kernel(CwParams P, CwReach R, const int32_t *__restrict__ env_of, int n_states, int depth)
+{
+    for (int j = (int)(blockIdx.x * blockDim.x + threadIdx.x); j < n_states; j += (int)(gridDim.x * blockDim.x)) {
+        const int32_t env = env_of ? env_of[j] : (int32_t)((uint32_t)j % (uint32_t)P.n_envs);
+        const bool part = cwh_expand_env_ok(env, P.n_envs);
+        R.s_grp[j] = part ? j : -1;
+        R.s_fresh[j] = part ? 1 : 0;
+        R.dist[j] = -1;
+        R.sol[j] = 0;
+        R.bid[j] = CW_REACH_NONE;
+        R.active[j] = part ? 1 : 0;
+    }
+    if (blockIdx.x == 0) {
+        for (int k = (int)threadIdx.x; k <= depth; k += (int)blockDim.x) R.sizes[k] = 0;
+        if (threadIdx.x == 0) { R.ctl[CWH_REACH_STOP] = 0; R.ctl[CWH_REACH_SEARCHED] = depth; }
+    }
+}
+
+template <int A>
+__device__ __forceinline__ void reach_expand_one(const CwParams &P, const CwReach &R, int src, int j, int r)
+{
+    const int32_t env = R.f_env[src][j], start = R.f_start[src][j];
+    if (!cwh_expand_env_ok(env, P.n_envs) || (uint32_t)start >= (uint32_t)R.max_rows) { R.s_grp[r] = -1; return; }      // (cannot happen: the scatter wrote both)
+    uint4 h = R.f_hdr[src][j];
+    uint32_t sp[8];
+    unpack_pos(R.f_pos[src][j], sp);
+    const CwStepOut o = step_env(P, h, sp, A, [&]() { return P.init_pos[env]; });
+    R.s_hdr[r] = h;
+    R.s_pos[r] = pack_pos(sp);
+    R.s_grp[r] = o.done ? -1 : start;
+    if (o.reward == P.max_steps && R.active[start]) atomicMin(&R.bid[start], r);
+}
+
+__global__ __launch_bounds__(256) void cw_reach_expand_kernel(CwParams P, CwReach R, int level)
+{
+    const int F = min(max(R.sizes[level - 1], 0), R.max_rows), Fp = (int)cwh_reach_padded(F), n = 6 * Fp, src = (level - 1) & 1;
+    for (int r = (int)(blockIdx.x * blockDim.x + threadIdx.x); r < n; r += (int)(gridDim.x * blockDim.x)) {      // (whole waves: n and the stride are multiples of 64)
+        const int a = __builtin_amdgcn_readfirstlane(r / Fp), j = r - a * Fp;
+        R.s_fresh[r] = 0;
+        if (j >= F) { R.s_grp[r] = -1; continue; }
+        switch (a) {
+        case 0: reach_expand_one<0>(P, R, src, j, r); break;
+        case 1: reach_expand_one<1>(P, R, src, j, r); break;
+        case 2: reach_expand_one<2>(P, R, src, j, r); break;
+        case 3: reach_expand_one<3>(P, R, src, j, r); break;
+        case 4: reach_expand_one<4>(P, R, src, j, r); break;
+        default: reach_expand_one<5>(P, R, src, j, r); break;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cw_reach_claim_kernel(CwSeen S, CwReach R, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int level,
+                                                             int n_states)
+{
+    seen_claim_rows(S, CW_REACH_GROUP(R), hdr_in, pos_in, (size_t)reach_rows(R, level, n_states));
+}
+
+__global__ __launch_bounds__(256) void cw_reach_resolve_kernel(CwSeen S, CwReach R, const uint4 *__restrict__ hdr_in, const uint4 *__restrict__ pos_in, int level,
+                                                               int n_states)
+{
+    seen_resolve_rows(S, CW_REACH_GROUP(R), hdr_in, pos_in, (size_t)reach_rows(R, level, n_states), level == 0 ? nullptr : R.s_fresh, nullptr);
+}
+
+__global__ __launch_bounds__(256) void cw_reach_count_kernel(CwReach R, int level, int n_states)
+{
+    __shared__ int lds[256 / CW_WAVE];
+    const int n = reach_rows(R, level, n_states), n_chunks = (int)cwh_reach_chunks(n);
+    for (int c = (int)blockIdx.x; c < n_chunks; c += (int)gridDim.x) {                     // (uniform across the workgroup)
+        int r0, total;
+        (void)reach_block_scan(reach_flag_count(reach_flags(R, c, n, r0)), lds, total);
+        if (threadIdx.x == 0) R.chunk[c] = total;
+    }
+}
+
+__global__ __launch_bounds__(1024) void cw_reach_scan_kernel(CwReach R, int level, int n_states)
+{
+    __shared__ int lds[1024 / CW_WAVE];
+    const int n = reach_rows(R, level, n_states), n_chunks = (int)cwh_reach_chunks(n);
+    const int per = (n_chunks + (int)blockDim.x - 1) / (int)blockDim.x;
+    const int lo = min((int)threadIdx.x * per, n_chunks), hi = min(lo + per, n_chunks);
+    int sum = 0, total;
+    for (int k = lo; k < hi; k++) sum += R.chunk[k];
+    int ahead = reach_block_scan(sum, lds, total);
+    for (int k = lo; k < hi; k++) {
+        const int c = R.chunk[k];
+        R.chunk[k] = ahead;
+        ahead += c;
+    }
+    if (threadIdx.x == 0) {
+        const bool over = total > R.max_rows;
+        R.sizes[level] = over ? 0 : total;
+        if (over) { R.ctl[CWH_REACH_STOP] = 1; R.ctl[CWH_REACH_SEARCHED] = level; }
+    }
+}
+
+__global__ __launch_bounds__(256) void cw_reach_scatter_kernel(CwParams P, CwReach R, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                               const uint4 *__restrict__ pos_in, int level, int n_states)
+{
+    __shared__ int lds[256 / CW_WAVE];
+    const int n_next = R.sizes[level];
+    if (n_next <= 0 || n_next > R.max_rows) return;                                        // nothing fresh, or the search has stopped (uniform)
+    const int n = reach_rows(R, level, n_states), n_chunks = (int)cwh_reach_chunks(n), dst = level & 1, src = dst ^ 1;
+    const int Fp = level == 0 ? 1 : n / 6;
+    for (int c = (int)blockIdx.x; c < n_chunks; c += (int)gridDim.x) {
+        int r0, total;
+        const uint4 f = reach_flags(R, c, n, r0);
+        int at = R.chunk[c] + reach_block_scan(reach_flag_count(f), lds, total);
+        // the 16 flags as 16 bits (a word's bits 0, 8, 16, 24 gathered by one multiply: the partial products share no bit), then one round per fresh row
+        auto nibble = [](uint32_t w) { return ((w * 0x00204081u) >> 21) & 0xFu; };
+        uint32_t m = nibble(f.x) | nibble(f.y) << 4 | nibble(f.z) << 8 | nibble(f.w) << 12;
+        for (; m && at < n_next; m &= m - 1u) {                                            // (at < n_next always: the places are the scan's)
+            const int r = r0 + __builtin_ctz(m);
+            if (level == 0) {
+                R.f_hdr[0][at] = hdr_in[r];
+                R.f_pos[0][at] = pos_in[r];
+                R.f_env[0][at] = env_of ? env_of[r] : (int32_t)((uint32_t)r % (uint32_t)P.n_envs);
+                R.f_start[0][at] = r;
+            } else {
+                const int a = r / Fp, j = r - a * Fp;
+                R.f_hdr[dst][at] = R.s_hdr[r];
+                R.f_pos[dst][at] = R.s_pos[r];
+                R.f_env[dst][at] = R.f_env[src][j];
+                R.f_start[dst][at] = R.f_start[src][j];
+                R.links[(size_t)(level - 1) * (size_t)R.max_rows + (size_t)at] = (j << 3) | a;
+            }
+            at++;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cw_reach_settle_kernel(CwReach R, int level, int n_states)
+{
+    const int Fp = (int)cwh_reach_padded(min(max(R.sizes[level - 1], 0), R.max_rows));
+    for (int s = (int)(blockIdx.x * blockDim.x + threadIdx.x); s < n_states; s += (int)(gridDim.x * blockDim.x)) {
+        const int32_t b = R.bid[s];
+        if (b == CW_REACH_NONE || Fp == 0) continue;
+        const int a = b / Fp, j = b - a * Fp;
+        R.dist[s] = level;
+        R.sol[s] = (j << 3) | a;
+        R.active[s] = 0;
+        R.bid[s] = CW_REACH_NONE;
+    }
+}
+
+// the plans: start row s solved at level L took action sol & 7 from state sol >> 3 of frontier L - 1, which came by links[L - 2] from frontier L - 2, ...
+__global__ __launch_bounds__(256) void cw_reach_walk_kernel(CwReach R, int n_states, int depth, CwReachOut O)
+{
+    const size_t M = (size_t)n_states;
+    for (int s = (int)(blockIdx.x * blockDim.x + threadIdx.x); s < n_states; s += (int)(gridDim.x * blockDim.x)) {
+        const int32_t L = R.dist[s];
+        int32_t link = R.sol[s];
+        uint32_t first = 0;
+        for (int lvl = depth; lvl >= 1; lvl--) {
+            uint32_t a = 0;
+            if (lvl <= L) {
+                if (lvl < L) {
+                    const int32_t cur = link >> 3;
+                    link = (uint32_t)cur < (uint32_t)R.max_rows ? R.links[(size_t)(lvl - 1) * (size_t)R.max_rows + (size_t)cur] : 0;
+                }
+                a = (uint32_t)link & 7u;
+            }
+            if (O.plan) O.plan[(size_t)(lvl - 1) * M + (size_t)s] = (uint8_t)a;
+            first = a;
+        }
+        if (O.distance) O.distance[s] = L;
+        if (O.first_action) O.first_action[s] = (uint8_t)first;
+    }
+    if (blockIdx.x == 0) {
+        if (O.frontier)
+            for (int k = (int)threadIdx.x; k < depth; k += (int)blockDim.x) O.frontier[k] = R.sizes[k];
+        if (O.searched_depth && threadIdx.x == 0) O.searched_depth[0] = R.ctl[CWH_REACH_SEARCHED];
+    }
 }
 
 // ------------------------------------------------------------------------------------ reset
@@ -3022,6 +3277,34 @@ hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const Cw
 hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st)
 {
     hipLaunchKernelGGL(cw_seen_clear_kernel, dim3(cw_seen_grid(*T, (size_t)S->mask + 1)), dim3(256), 0, st, *S);
+    return hipGetLastError();
+}
+
+// cw_reach: the set's clear, six kernels for frontier 0, seven per level (two for the last) and the walk-back.  The launch shapes depend on the workspace's
+// max_rows and the card alone (cwh_reach_grid): the row kernels cover 6 * padded(max_rows) rows, the start-row kernels max_rows, count and scatter one
+// workgroup per chunk, each grid-stride beyond CWH_REACH_BLOCKS_PER_CU workgroups per CU; the scan is one workgroup of 1024.
+hipError_t cwk_launch_reach(const CwParams *P, const CwTuning *T, const CwSeen *S, const CwReach *R, const int32_t *env_of, const uint4 *hdr, const uint4 *pos,
+                            int n_states, int depth, const CwReachOut *O, hipStream_t st)
+{
+    const int64_t rows = cwh_reach_rows(R->max_rows);
+    const dim3 block(256), g_rows((unsigned)cwh_reach_grid(rows, T->n_cu)), g_start((unsigned)cwh_reach_grid(R->max_rows, T->n_cu)),
+        g_chunks((unsigned)cwh_reach_grid(256 * cwh_reach_chunks(rows), T->n_cu));
+    auto compact = [&](int level, const uint4 *h, const uint4 *p) {
+        hipLaunchKernelGGL(cw_reach_claim_kernel, level ? g_rows : g_start, block, 0, st, *S, *R, h, p, level, n_states);
+        hipLaunchKernelGGL(cw_reach_resolve_kernel, level ? g_rows : g_start, block, 0, st, *S, *R, h, p, level, n_states);
+        hipLaunchKernelGGL(cw_reach_count_kernel, g_chunks, block, 0, st, *R, level, n_states);
+        hipLaunchKernelGGL(cw_reach_scan_kernel, dim3(1), dim3(1024), 0, st, *R, level, n_states);
+        hipLaunchKernelGGL(cw_reach_scatter_kernel, g_chunks, block, 0, st, *P, *R, env_of, h, p, level, n_states);
+    };
+    hipLaunchKernelGGL(cw_seen_clear_kernel, dim3(cw_seen_grid(*T, (size_t)S->mask + 1)), block, 0, st, *S);
+    hipLaunchKernelGGL(cw_reach_start_kernel, g_start, block, 0, st, *P, *R, env_of, n_states, depth);
+    compact(0, hdr, pos);
+    for (int level = 1; level <= depth; level++) {
+        hipLaunchKernelGGL(cw_reach_expand_kernel, g_rows, block, 0, st, *P, *R, level);
+        if (level < depth) compact(level, R->s_hdr, R->s_pos);
+        hipLaunchKernelGGL(cw_reach_settle_kernel, g_start, block, 0, st, *R, level, n_states);
+    }
+    hipLaunchKernelGGL(cw_reach_walk_kernel, g_start, block, 0, st, *R, n_states, depth, *O);
     return hipGetLastError();
 }
 

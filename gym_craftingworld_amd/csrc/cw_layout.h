@@ -108,6 +108,36 @@ struct CwSeen {
     int32_t tag_bits;            // 0: the full hash
 };
 
+// The WORKSPACE of cw_reach (cw_reach_reserve): one allocation in device memory, its sections cw_host.cpp's (cwh_reach_layout).  Frontier k -- the states
+// level k + 1 expands, k = 0 the participating start rows -- lives in buffer k & 1; sizes[k] is its size, written ON THE DEVICE by the scan that closes
+// level k, and every kernel of a level reads it from there.  s_*: the successors of the level in hand, row a * Fp + j (cw_host.h: THE ROWS).  links: level k's
+// scatter leaves parent << 3 | action for every state of frontier k at links[(k - 1) * max_rows + i].  Per start row: dist (-1: unsolved), sol (the link of its
+// solving row), bid (the smallest solving row of the level in hand, CW_REACH_NONE: none) and active.
+#define CW_REACH_NONE 0x7FFFFFFF
+struct CwReach {
+    int32_t *ctl;                // [CWH_REACH_CTL_WORDS]: CWH_REACH_STOP, CWH_REACH_SEARCHED
+    int32_t *sizes;              // [max_depth + 1]
+    int32_t *chunk;              // [chunks of the largest level]: the count of every chunk, then (the scan) what lies ahead of it
+    uint4 *f_hdr[2], *f_pos[2];  // [max_rows]
+    int32_t *f_env[2], *f_start[2];
+    uint4 *s_hdr, *s_pos;        // [6 * padded(max_rows)]
+    int32_t *s_grp;              // ... the start row, -1 for a done successor and for a row that takes no part
+    uint8_t *s_fresh;            // ... 1: the row brings its key into the set (whole chunks: read 16 bytes at a time)
+    int32_t *links;              // [max_depth - 1][max_rows]
+    int32_t *dist, *sol, *bid;   // [max_rows]
+    uint8_t *active;             // [max_rows]
+    int32_t max_rows, max_depth;
+};
+
+// Where cw_reach leaves its results (the public cw_reach_out).  A null field is not written.
+struct CwReachOut {
+    int32_t *distance;           // [M]
+    uint8_t *plan;               // [D][M] step-major
+    uint8_t *first_action;       // [M]
+    int32_t *frontier;           // [D]
+    int32_t *searched_depth;     // [1]
+};
+
 // Where cw_expand_kernel leaves the six successors of M states (the public cw_expand_out with the records typed): every array ACTION-MAJOR, row a * M + j =
 // action a on input state j.  A null field is not written.
 struct CwExpandOut {

@@ -299,6 +299,8 @@ def plan_args(num_envs, depth, hdr, slot_pos, env_of):
 SHOOT_FIELDS = ('best_ret', 'best_sample', 'best_action', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'ret')
 SHOOT_MAX_SAMPLES, SHOOT_MAX_WORK = 65536, 2 ** 32
 SEEN_FIELDS = ('fresh', 'first')
+REACH_FIELDS = ('distance', 'plan', 'first_action', 'frontier', 'searched_depth')
+REACH_MAX_ROWS = (2 ** 28 - 1) // 6 - 63       # 6 * (max_rows + 63) < 2**28: the row field of the visited set's bids
 
 
 def _shoot_int(v, what, lo, hi):
@@ -1215,6 +1217,58 @@ class CraftingWorldVecEnv:
                 a, cur = torch.where(via, act[at], a), torch.where(via, par[at], cur)
             plan[lvl - 1] = a.to(torch.uint8)
         return {'distance': dist, 'plan': plan, 'first_action': plan[0].clone(), 'searched_depth': searched, 'states': self.seen_size, 'frontier': sizes}
+
+    def reach_reserve(self, max_rows, max_depth):
+        """Allocate (or re-allocate; max_rows = 0 frees it) the workspace of reach_async() for frontiers of at most `max_rows` states -- the cap on the
+        start rows of a call too -- and searches of at most `max_depth` levels (cw_reach_reserve; synchronises this engine's work): about
+        315 + 4 * (max_depth - 1) bytes a row in device memory (reach_bytes).  ValueError for max_rows outside 0 .. REACH_MAX_ROWS or max_depth outside
+        1 .. 32 767."""
+        max_rows, max_depth = _shoot_int(max_rows, 'max_rows', 0, REACH_MAX_ROWS), _shoot_int(max_depth, 'max_depth', 1, SIMULATE_MAX_STEPS)
+        self._settle()
+        self._reach_ws = None
+        L.check(self._lib.cw_reach_reserve(self._h, max_rows, max_depth), 'cw_reach_reserve', self._lib)
+        if max_rows:
+            self._reach_ws = (max_rows, max_depth)
+
+    @property
+    def reach_bytes(self):
+        """bytes of reach_async()'s workspace (0 without one)"""
+        return int(self._lib.cw_reach_bytes(self._h))
+
+    def reach_async(self, max_depth, hdr=None, slot_pos=None, env_of=None, *, max_rows=None, out=None):
+        """reach() as ONE library call that only enqueues kernels (cw_reach): no host round trip -- the frontier's size lives in device memory --, no
+        synchronisation, capturable with the steps.  Arguments and rules are reach()'s, and with the same start rows, the same max_rows and a set that
+        neither overflows nor collides every result equals reach()'s byte for byte, the choice among equally short plans included.
+        -> a dict of DEVICE tensors: 'distance' int32 [M0], 'plan' uint8 [max_depth, M0], 'first_action' uint8 [M0], 'frontier' int32 [max_depth] (the
+        states each level expanded, 0 for levels not run), 'searched_depth' int32 [1] and 'states' int64 [1] (a copy of seen_size made on the env's
+        stream).  out: a dict returned by an earlier call with the same max_depth and M0, written again ('states' is replaced).
+        The search needs the engine's visited set and a workspace (reach_reserve).  max_rows: the cap on a frontier; None: the workspace's, or 2**22
+        without one.  Without a set seen_reserve(4 * max_rows) is called; without a workspace, with one of ANOTHER max_rows or with one of fewer levels
+        reach_reserve(max_rows, max_depth) is.  Both reserves synchronise and allocate: RESERVE BEFORE CAPTURING, then call with max_rows=None."""
+        D = _shoot_int(max_depth, 'max_depth', 1, SIMULATE_MAX_STEPS)
+        ws = getattr(self, '_reach_ws', None)
+        if max_rows is None:
+            max_rows = ws[0] if ws else 2 ** 22
+        max_rows = _shoot_int(max_rows, 'max_rows', 1, REACH_MAX_ROWS)
+        m0, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        if m0 > max_rows:
+            raise ValueError('%d start rows: at most max_rows = %d' % (m0, max_rows))
+        if not self.seen_slots:
+            self.seen_reserve(4 * max_rows)
+        if ws is None or ws[0] != max_rows or ws[1] < D:
+            self.reach_reserve(max_rows, D)
+        spec = {'distance': ((m0,), torch.int32), 'plan': ((D, m0), torch.uint8), 'first_action': ((m0,), torch.uint8), 'frontier': ((D,), torch.int32),
+                'searched_depth': ((1,), torch.int32)}
+        if out is not None:
+            out = {f: t for f, t in out.items() if f != 'states'}
+        out = self._out_dict(out, REACH_FIELDS, spec)
+        if m0:
+            self._call('cw_reach', env_of, hdr, slot_pos, m0, D, C.byref(_out_struct(L.cw_reach_out, out)), keep=out)
+        else:                                       # (no start rows, and no address to hand over: what the call would leave)
+            self.seen_clear()
+            out['frontier'].zero_()
+            out['searched_depth'].fill_(D)
+        return dict(out, states=self._seen_ctl[0:1].clone())
 
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)

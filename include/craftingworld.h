@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -495,6 +495,49 @@ int cw_seen_clear(cw_engine *e, cw_stream_t stream);
 int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, const cw_seen_out *out, cw_stream_t stream);
 int cw_seen_counters(const cw_engine *e, const uint64_t **counters);   /* *counters = the DEVICE uint64[3]; CW_ERR_STATE (and NULL) without a set */
 size_t cw_seen_slots(const cw_engine *e);
+
+/* --- breadth-first search without a host round trip: the SHORTEST plan that ends in success from each of M start states, or "none within max_depth steps" --
+ * cw_expand's step, the visited set above and a stable compaction, level after level, in ONE call that only enqueues kernels: the frontier's size lives in
+ * device memory.  Capturable with the steps ("step, then label every env with its distance to the goal").  The reference has no counterpart.
+ * cw_reach_reserve: the WORKSPACE, one allocation per engine, or a new one; max_rows == 0 frees it.  max_rows is the cap on a frontier AND on the start rows of a
+ *   call; 1 <= max_rows with 6 * (max_rows + 63) < 2^28 (the row field of the set's bids), 1 <= max_depth <= 32 767, else CW_ERR_INVALID; CW_ERR_HIP when the
+ *   allocation fails -- the engine is then left WITHOUT a workspace.  Synchronous; waits for this engine's own work only, as cw_seen_reserve does.  It holds two
+ *   frontiers (record, env, start row: 80 bytes a row), the successors of one level (6 x 37 bytes a row), the links of every level but the last (parent and
+ *   action, 4 bytes a row and level), 13 bytes per start row and a control block (the frontier's size per level, a stop flag, the scan's scratch):
+ *   cw_reach_bytes (0 without one); about 315 + 4 * (max_depth - 1) bytes a row.  Not part of a checkpoint blob or of a snapshot row; freed by cw_destroy.
+ * cw_reach: the start states are cw_expand's: hdr_in / slot_pos_in NULL: the engine's own records (n_states = num_envs), else the caller's, only read; env_of
+ *   NULL: start row j belongs to env j % num_envs, else to env_of[j].  A start row whose entry is outside 0 .. num_envs - 1 takes no part: it reports -1 and is
+ *   NOT counted in counters[7].  Needs a visited set (cw_seen_reserve) and a workspace with max_rows >= n_states and max_depth >= the one asked for.
+ *   START: the set is CLEARED; the participating start rows are inserted with group = their row number -- two start rows are searched apart whatever they
+ *     share -- and form frontier 0 in row order.
+ *   LEVEL d = 1 .. max_depth over a frontier of F states: a successor row belongs to action a and parent j, in the order of a * F + j.  A successor whose
+ *     reward is max_steps bids for its start row; the smallest such row wins and sets distance = d.  A solved start row leaves the search at once: in the same
+ *     level its successors are not inserted.  A done successor is not inserted.  The rest go into the set with group = start row, and the fresh ones, in row
+ *     order, are the next frontier.  More than max_rows (the workspace's) of them: searched_depth = d and every later level is a no-op.  At d = max_depth
+ *     nothing is inserted.  An empty frontier ends the search with searched_depth = max_depth.
+ *   With a set that neither overflows nor collides (cw_seen_counters) the outputs are a function of the inputs alone -- which of several equally short plans
+ *     is returned included: the smallest solving row of the level, and behind it the smallest row of each key.  An overflow or a collision expands a state
+ *     again: the distances stay exact while the frontier stays within max_rows.  The set is left filled: its keys are the states searched.
+ * Enqueues the set's clear, 6 kernels for frontier 0, 7 per level (cw_reach_expand_kernel, cw_reach_claim_kernel, cw_reach_resolve_kernel, cw_reach_count_kernel,
+ *   cw_reach_scan_kernel, cw_reach_scatter_kernel, cw_reach_settle_kernel; the last level: expand and settle) and cw_reach_walk_kernel, which follows the links
+ *   back, one lane per start row.  Their launch shapes depend on the workspace's max_rows and the card alone; every kernel reads the frontier's size from the
+ *   workspace, so a level over an empty or stopped frontier costs its launches and nothing else.  No lane or workgroup waits for another anywhere: a kernel
+ *   boundary is the only grid-wide ordering.  No host synchronisation, no allocation.
+ *   CW_ERR_STATE before the first cw_reset / cw_checkpoint_load, without a set, without a workspace, for n_states above its max_rows or max_depth above its
+ *   max_depth.  CW_ERR_INVALID: a null engine or out, every field NULL, n_states < 0 or above the cap of max_rows, max_depth outside 1 .. 32 767, hdr_in without
+ *   slot_pos_in or the reverse, env_of without them, n_states != num_envs without records, misaligned records (env_of, distance, frontier, searched_depth:
+ *   4 bytes), an output overlapping the records, env_of or another output.  n_states == 0: frontier zeros, searched_depth = max_depth. */
+typedef struct cw_reach_out {          /* DEVICE pointers; a NULL field is not written; all NULL: CW_ERR_INVALID */
+    int32_t *distance;                 /* [n_states]  steps of a shortest plan that ends in success; -1: none within the searched depth, or no part */
+    uint8_t *plan;                     /* [max_depth][n_states]  that plan, step-major like cw_simulate's actions; 0 behind its end and for -1 rows */
+    uint8_t *first_action;             /* [n_states]  plan[0] */
+    int32_t *frontier;                 /* [max_depth]  states expanded per level, 0 for levels not run */
+    int32_t *searched_depth;           /* [1]  every plan of at most this many steps has been considered */
+} cw_reach_out;
+int cw_reach_reserve(cw_engine *e, int64_t max_rows, int32_t max_depth);
+size_t cw_reach_bytes(const cw_engine *e);
+int cw_reach(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t max_depth,
+             const cw_reach_out *out, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
