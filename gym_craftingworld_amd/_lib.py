@@ -178,6 +178,7 @@ CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
 CWH_SHOOT_MAX_SAMPLES, CWH_SHOOT_MAX_WORK = 65536, 1 << 32
 CWH_SEEN_OK, CWH_SEEN_NO_RECORDS, CWH_SEEN_NO_FIELD, CWH_SEEN_N_STATES, CWH_SEEN_ALIGN, CWH_SEEN_OVERLAP = range(6)
 CWH_SEEN_KEY_WORDS, CWH_SEEN_MAX_CAPACITY, CWH_SEEN_PROBES = 9, 1 << 28, 128
+CWH_SEEN_ROW_BITS, CWH_SEEN_MAX_EPOCH = 28, (1 << 36) - 2
 CWH_REACH_OK, CWH_REACH_NO_FIELD, CWH_REACH_N_STATES, CWH_REACH_DEPTH, CWH_REACH_PAIR, CWH_REACH_ENV_OF, CWH_REACH_OWN_STATES, CWH_REACH_ALIGN, \
     CWH_REACH_OVERLAP = range(9)
 CWH_REACH_CHUNK, CWH_REACH_MAX_ROWS, CWH_REACH_MAX_DEPTH, CWH_REACH_BLOCKS_PER_CU, CWH_REACH_SECTIONS = 4096, (2 ** 28 - 1) // 6 - 63, 32767, 8, 18

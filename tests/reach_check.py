@@ -12,7 +12,7 @@ from records_check import DENSE, encode, oracle_simulate
 from seen_check import SeenModel, key_of
 
 WAVE, CHUNK, NONE = 64, 4096, 2 ** 31 - 1
-FAULTS = ('swap_frontier', 'solved_row_stays', 'done_inserted', 'link_off_by_one', 'plan_tail')
+FAULTS = ('swap_frontier', 'solved_row_stays', 'done_inserted', 'link_off_by_one', 'plan_tail', 'chunk_round_lost')
 
 
 def padded(F):
@@ -29,16 +29,20 @@ def row_of(a, j, F):
     return a * padded(F) + j
 
 
-def compact(flags, chunk=CHUNK, lanes=256):
+def compact(flags, chunk=CHUNK, lanes=256, lost_from=None):
     """the kernels' stable compaction of the set flags: per chunk of `chunk` rows a count (every lane of `lanes` takes chunk // lanes consecutive flags), one
     scan over the chunk counts, and per chunk again the place of each set flag = what lies ahead of the chunk + the prefix of the lanes ahead + its rank in
-    its lane -> (places int64 [n]: places[k] is the row that lands at k, the chunk counts, what lies ahead of each chunk)"""
+    its lane -> (places int64 [n]: places[k] is the row that lands at k, the chunk counts, what lies ahead of each chunk).  lost_from (the fault
+    'chunk_round_lost'): the set flags of every chunk at or above that count are ignored -- count and scatter launched with lost_from workgroups whose
+    grid-stride loop never takes its second round"""
     flags = np.asarray(flags).astype(bool)
     n = len(flags)
     n_chunks = (n + chunk - 1) // chunk
     per = chunk // lanes
     grid = np.zeros(n_chunks * chunk, bool)
     grid[:n] = flags                                                   # (rows at or above n are cleared, whatever the buffer holds)
+    if lost_from is not None:
+        grid[int(lost_from) * chunk:] = False
     lane_counts = grid.reshape(n_chunks, lanes, per).sum(axis=2)
     counts = lane_counts.sum(axis=1)
     ahead = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if n_chunks else np.zeros(0, np.int64)
@@ -57,12 +61,13 @@ def compact(flags, chunk=CHUNK, lanes=256):
 class ReachModel:
     """one search.  part: bool [M0], which start rows take part.  start(keys) and then level(d, hit, done, keys) for d = 1, 2, ... return the next frontier as
     indices into the rows handed in (start rows; then successors in the order a * F + j), which the caller gathers; result() walks the plans back.
-    faults: names of FAULTS to plant."""
+    faults: names of FAULTS to plant.  chunk_grid: the workgroups count and scatter are launched with, which only 'chunk_round_lost' reads."""
 
-    def __init__(self, part, max_rows, max_depth, faults=(), chunk=CHUNK):
+    def __init__(self, part, max_rows, max_depth, faults=(), chunk=CHUNK, chunk_grid=1):
         self.part = np.asarray(part).astype(bool)
         self.M0, self.max_rows, self.D, self.faults, self.chunk = len(self.part), int(max_rows), int(max_depth), tuple(faults), chunk
         assert set(self.faults) <= set(FAULTS)
+        self.lost_from = int(chunk_grid) if 'chunk_round_lost' in self.faults else None
         self.seen = SeenModel()
         self.dist = np.full(self.M0, -1, np.int64)
         self.sol = np.zeros(self.M0, np.int64)
@@ -82,8 +87,8 @@ class ReachModel:
         self.seen.clear()
         rows = np.arange(self.M0, dtype=np.int64)
         self.seen.insert(self._keys(keys, rows), self.part)
-        places, _, _ = compact(self.part, self.chunk)
-        assert np.array_equal(places, np.flatnonzero(self.part))
+        places, _, _ = compact(self.part, self.chunk, lost_from=self.lost_from)
+        assert self.lost_from is not None or np.array_equal(places, np.flatnonzero(self.part))
         self.f_start = places
         self.sizes[0] = len(places)
         return places
@@ -118,8 +123,8 @@ class ReachModel:
             if F:
                 k[real] = np.asarray(keys).reshape(6 * F, -1)
             fresh, _ = self.seen.insert(self._keys(k, np.maximum(g, 0)), g >= 0)
-            places, counts_c, ahead = compact(fresh, self.chunk)
-            assert np.array_equal(places, np.flatnonzero(fresh)) and counts_c.sum() == len(places)
+            places, counts_c, ahead = compact(fresh, self.chunk, lost_from=self.lost_from)
+            assert (self.lost_from is not None or np.array_equal(places, np.flatnonzero(fresh))) and counts_c.sum() == len(places)
             if len(places) > self.max_rows:                            # the stop rule: searched_depth = d, every later level is a no-op
                 self.searched, self.stopped = d, True
                 places = places[:0]
@@ -159,10 +164,10 @@ class ReachModel:
                     states=len(self.seen))
 
 
-def run_model(part, start_keys, payload, successors, max_rows, max_depth, faults=(), chunk=CHUNK):
+def run_model(part, start_keys, payload, successors, max_rows, max_depth, faults=(), chunk=CHUNK, chunk_grid=1):
     """a whole search.  payload: anything indexable by an int array, one entry per start row; successors(payload of the frontier) -> (hit [6, F], done [6, F],
     keys [6 * F, words], payload of the 6 * F successors in the order a * F + j) -> ReachModel.result()"""
-    m = ReachModel(part, max_rows, max_depth, faults, chunk)
+    m = ReachModel(part, max_rows, max_depth, faults, chunk, chunk_grid)
     front = payload[m.start(start_keys)]
     for d in range(1, max_depth + 1):
         if len(m.f_start) == 0:                                        # (an empty or stopped frontier: the remaining levels are no-ops)

@@ -1,6 +1,7 @@
 """What the GPU tiers of the records calls (tests/test_{expand,simulate,plan,shoot}.py) share: sentinel-filled output buffers built from the layouts of the
-check modules, results as numpy, the env_of cases, goals within reach, records of the caller's, and the 70-env engine they hand in.  Imports torch: only
-`gpu` tests import it.  A plain module, not a fixture."""
+check modules, results as numpy, the env_of cases, goals within reach, records of the caller's, and the 70-env engine they hand in; and what the two GPU
+tiers of cw_reach (tests/test_reach_async.py, tests/test_reach_rounds.py) share: its sentinel-filled outputs and start rows tiled from an engine's envs.
+Imports torch: only `gpu` tests import it.  A plain module, not a fixture."""
 import numpy as np
 import torch
 
@@ -70,3 +71,19 @@ def walked_engine(seed, steps, goals=None):
     if goals:
         walk_goals(env, *goals)
     return env
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ cw_reach
+REACH_OUT = (('distance', torch.int32), ('plan', torch.uint8), ('first_action', torch.uint8), ('frontier', torch.int32), ('searched_depth', torch.int32))
+
+
+def reach_sentinel_out(D, M0):
+    """the five output buffers of reach_async(D, M0 start rows, out=...), every byte SENT"""
+    shapes = dict(distance=(M0,), plan=(D, M0), first_action=(M0,), frontier=(D,), searched_depth=(1,))
+    return {f: torch.full(shapes[f] + (dt.itemsize,), SENT, dtype=torch.uint8, device='cuda').view(dt).squeeze(-1) for f, dt in REACH_OUT}
+
+
+def tiled_rows(env, M0):
+    """M0 start rows tiled from the engine's envs: row j is env j % N's state"""
+    e = np.arange(M0) % env.num_envs
+    return dev(env.hdr.cpu().numpy()[e]).reshape(M0, 16), dev(env.slot_pos.cpu().numpy()[e], np.int16).reshape(M0, 8), dev(e, np.int32)

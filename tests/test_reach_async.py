@@ -12,13 +12,12 @@ from engines import ENGINES, K5, N1, n_cu
 from masked_check import spread, take
 from oracle_replay import make_env, np_states
 from reach_check import check_reach_call, rows_of
-from records_gpu import SENT, dev as _dev, walk_goals
+from records_gpu import REACH_OUT as OUT, SENT, dev as _dev, reach_sentinel_out as _sentinel_out, tiled_rows as _tiled, walk_goals
 from seen_check import REACH_MAX_STEPS, REACH_N, REACH_SEEDS, reach_reference, seed_states
 
 pytestmark = pytest.mark.gpu
 
 DEPTH = 10
-OUT = (('distance', torch.int32), ('plan', torch.uint8), ('first_action', torch.uint8), ('frontier', torch.int32), ('searched_depth', torch.int32))
 
 
 def _start_engine(size):
@@ -26,11 +25,6 @@ def _start_engine(size):
     env, _, _ = make_env(REACH_N, *seed_states(REACH_SEEDS[size]), obs_mode='state', auto_reset=False, size=(size, size), max_steps=REACH_MAX_STEPS)
     env.reset()
     return env
-
-
-def _sentinel_out(D, M0):
-    shapes = dict(distance=(M0,), plan=(D, M0), first_action=(M0,), frontier=(D,), searched_depth=(1,))
-    return {f: torch.full(shapes[f] + (dt.itemsize,), SENT, dtype=torch.uint8, device='cuda').view(dt).squeeze(-1) for f, dt in OUT}
 
 
 def _host(r):
@@ -69,12 +63,6 @@ def _plans_hold(env, got, hdr=None, pos=None, eo=None):
     assert done[solved].all() and np.array_equal(length[solved], dist[solved])
     assert np.array_equal(ret[solved], env.MAX_STEPS - (dist[solved] - 1))
     return dist
-
-
-def _tiled(env, M0):
-    """M0 start rows tiled from the engine's envs: row j is env j % N's state"""
-    e = np.arange(M0) % env.num_envs
-    return _dev(env.hdr.cpu().numpy()[e]).reshape(M0, 16), _dev(env.slot_pos.cpu().numpy()[e], np.int16).reshape(M0, 8), _dev(e, np.int32)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ 1. against reach()
@@ -225,6 +213,34 @@ def test_repeats_out_and_a_set_too_small(engine5):
     torch.cuda.synchronize()
     assert env.seen_overflow > 0 and r['frontier'].cpu().numpy().tolist()[0] == 12 and int(r['searched_depth'][0]) == 5
     assert np.array_equal(r['distance'].cpu().numpy(), np.where((ref['distance'] > 0) & (ref['distance'] <= 5), ref['distance'], -1))
+    env.seen_reserve(1 << 20)
+
+
+def test_a_spent_set_is_cleared_first(engine5):
+    """the set's epochs used up (the epoch word of its control block written past CWH_SEEN_MAX_EPOCH, and a seen_insert that shows it: held keys reported
+    fresh, every row counted as overflow, the epoch stuck): cw_reach clears the set before anything else, so the search that follows equals a fresh reach()
+    and leaves both counters at 0"""
+    from gym_craftingworld_amd import _lib as L
+    from gym_craftingworld_amd._wrap import tensor_view
+    env = engine5
+    env.seen_reserve(1 << 12)
+    p = C.c_void_p()
+    assert env._lib.cw_seen_counters(env._h, C.byref(p)) == L.CW_OK
+    ctl = tensor_view(p.value, (5,), torch.int64, env.device.index)                # size, overflow, collisions, EPOCH, ticket
+    assert env.seen_insert(env.hdr, env.slot_pos)['fresh'].all() and int(ctl[3].item()) == 1
+    ctl[3] = L.CWH_SEEN_MAX_EPOCH + 1
+    again = env.seen_insert(env.hdr, env.slot_pos)
+    assert again['fresh'].all() and (env.seen_size, env.seen_overflow, env.seen_collisions) == (REACH_N, REACH_N, 0)
+    assert int(ctl[3].item()) == L.CWH_SEEN_MAX_EPOCH + 1                          # spent, and stuck
+    out = _sentinel_out(3, REACH_N)
+    r = env.reach_async(3, max_rows=1 << 10, out=out)
+    torch.cuda.synchronize()
+    got = _host(r)
+    _clean(env)
+    assert int(ctl[3].item()) == 3                                                 # (cleared, then the start rows' insert and two levels')
+    check_reach_call(env.reach(3, max_rows=1 << 10), got, SENT)
+    _clean(env)
+    assert got['frontier'].tolist() == [12, 35, 55]
     env.seen_reserve(1 << 20)
 
 

@@ -83,7 +83,8 @@ def _table(seed=11):
     return nxt, pays, ends
 
 
-def _table_search(faults=(), max_rows=1 << 12):
+def _table_search(faults=(), max_rows=1 << 12, tile=1, **model_kw):
+    """tile: the nine start rows `tile` times over, row j is base row j % 9; model_kw: run_model's chunk and chunk_grid"""
     nxt, pays, ends = _table()
 
     def successors(front):
@@ -91,11 +92,11 @@ def _table_search(faults=(), max_rows=1 << 12):
         keys = np.zeros((6 * len(s), 2), np.uint32)
         keys[:, 1] = nxt[s].T.reshape(-1)
         return pays[s].T, ends[s].T | pays[s].T, keys, nxt[s].T.reshape(-1)
-    starts = np.arange(TABLE_STARTS) * 7
-    part = np.arange(TABLE_STARTS) != 4
-    keys = np.zeros((TABLE_STARTS, 2), np.uint32)
+    starts = np.tile(np.arange(TABLE_STARTS) * 7, tile)
+    part = np.tile(np.arange(TABLE_STARTS) != 4, tile)
+    keys = np.zeros((TABLE_STARTS * tile, 2), np.uint32)
     keys[:, 1] = starts
-    return run_model(part, keys, starts, successors, max_rows, TABLE_DEPTH, faults)
+    return run_model(part, keys, starts, successors, max_rows, TABLE_DEPTH, faults, **model_kw)
 
 
 def _buffers(r, **changed):
@@ -139,11 +140,14 @@ def test_a_correct_result_passes_and_is_the_breadth_first_one():
     check_reach_call(stopped, _buffers(stopped), SENT)
 
 
+FAULT_SHAPE = {'chunk_round_lost': dict(chunk=256, chunk_grid=2)}          # the launch a fault needs to show: chunks of 256 rows, two workgroups
+
+
 @pytest.mark.parametrize('fault', FAULTS)
 def test_a_planted_fault_is_caught(fault):
     """a swapped pair in the frontier order; a solved row that stays in the search, so that a later hit is accepted for it; a done row inserted; a link off by
-    one; a nonzero behind a plan's end"""
-    good, bad = _table_search(), _table_search(faults=(fault,))
+    one; a nonzero behind a plan's end; the chunks beyond the first grid-stride round of count and scatter lost"""
+    good, bad = _table_search(), _table_search(faults=(fault,), **FAULT_SHAPE.get(fault, {}))
     with pytest.raises(AssertionError):
         check_reach_call(good, _buffers(bad), SENT)
 
@@ -183,3 +187,45 @@ def test_what_else_the_checker_catches():
         check_reach_call(r, _buffers(r), SENT, engine, after)
     with pytest.raises(ValueError):
         check_reach_call(r, dict(_buffers(r), frontier=np.zeros(3, np.int32)), SENT)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ 4. tiled start rows
+TILE, TILE_CHUNK = 7, 256
+
+
+def _tiling_of(base, k):
+    """what a search over the base start rows k times over must give if start rows are searched apart and the order within a start row's own states is
+    kept: every per-row output repeats, every count is k times the base's (the comparison tests/test_reach_rounds.py makes on the card)"""
+    return dict(distance=np.tile(base['distance'], k), plan=np.tile(base['plan'], (1, k)), first_action=np.tile(base['first_action'], k),
+                frontier=k * base['frontier'], searched_depth=base['searched_depth'], states=k * base['states'])
+
+
+def test_tiled_start_rows_give_the_tiling_of_the_base_result():
+    """the table search once with its nine start rows and once with them seven times over, in chunks of 256 rows so that the tiled levels span many chunks:
+    distance, plan and first_action repeat (the tie of start row 0 included), frontier and states are seven times the base's"""
+    base, tiled = _table_search(chunk=TILE_CHUNK), _table_search(tile=TILE, chunk=TILE_CHUNK)
+    assert rows_of(int(tiled['frontier'].max())) > 8 * TILE_CHUNK and base['plan'][0, 0] == 0 and base['distance'][0] == 2      # (the tie: action 0 first)
+    want = _tiling_of(base, TILE)
+    for f in ('distance', 'plan', 'first_action', 'frontier'):
+        assert np.array_equal(tiled[f], want[f]), f
+    assert tiled['states'] == want['states'] and tiled['searched_depth'] == want['searched_depth'] == TABLE_DEPTH
+    check_reach_call(want, _buffers(tiled), SENT)
+    same_chunks = _table_search(tile=TILE)                                                                # the chunk size does not enter the result
+    check_reach_call(same_chunks, _buffers(tiled), SENT)
+
+
+def test_a_lost_chunk_round_breaks_the_tiling():
+    """'chunk_round_lost' with four workgroups: the fresh rows of every chunk from the fifth on never reach the next frontier.  The base search, whose levels
+    fit the four chunks' 1 024 rows or lose less, no longer tiles into the faulted search: the frontier is smaller than seven times the base's; and
+    check_reach_call against the unfaulted model names the frontier or the distance"""
+    base, good = _table_search(chunk=TILE_CHUNK), _table_search(tile=TILE, chunk=TILE_CHUNK)
+    bad = _table_search(tile=TILE, chunk=TILE_CHUNK, chunk_grid=4, faults=('chunk_round_lost',))
+    want = _tiling_of(base, TILE)
+    lvl = int(np.flatnonzero(bad['frontier'] != want['frontier'])[0])
+    assert lvl >= 1 and bad['frontier'][lvl] < want['frontier'][lvl] and (bad['frontier'][:lvl] == want['frontier'][:lvl]).all()
+    assert rows_of(int(want['frontier'][lvl - 1])) > 4 * TILE_CHUNK                                      # (the level whose compaction had a fifth chunk)
+    assert bad['states'] < want['states']
+    with pytest.raises(AssertionError, match='frontier|distance'):
+        check_reach_call(good, _buffers(bad), SENT)
+    unfaulted = _table_search(tile=TILE, chunk=TILE_CHUNK, chunk_grid=4)                                  # the grid alone changes nothing: the fault is opt-in
+    check_reach_call(good, _buffers(unfaulted), SENT)

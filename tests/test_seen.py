@@ -246,6 +246,50 @@ def test_collisions_are_counted_and_full_tags_are_exact_again(engine70):
     assert got['fresh'].sum() == 1000 == env.seen_size
 
 
+def test_the_last_usable_epoch_and_the_spent_one(engine70):
+    """The epoch is word 3 (CW_SEEN_EPOCH) of the control block cw_seen_counters names; the test writes it through a view of its own.  At the LAST USABLE
+    epoch, CWH_SEEN_MAX_EPOCH, a bid epoch << 28 | row fills the owner word up to bit 63: 300 new records (40 of them a second time, further down: first is
+    the smaller row) mixed with 300 held ones are exact against the model, and the epoch moves on to MAX_EPOCH + 1.  That epoch is SPENT: the same rows again
+    are all reported fresh with first = row and counted as overflow, row for row; the rows of a negative group keep the sentinel; keys held, collisions and
+    the epoch itself do not move -- a deviation in the safe direction, which check_seen_call(exact=False) accepts.  seen_clear() makes the set exact again."""
+    from gym_craftingworld_amd import _lib as L
+    from gym_craftingworld_amd._wrap import tensor_view
+    env = engine70
+    env.seen_reserve(4096)
+    p = C.c_void_p()
+    assert env._lib.cw_seen_counters(env._h, C.byref(p)) == L.CW_OK
+    ctl = tensor_view(p.value, (5,), torch.int64, env.device.index)                   # size, overflow, collisions, EPOCH, ticket
+    epoch = lambda: int(ctl[3].item())  # noqa: E731
+    hdr, pos = _random_records(600, 14)
+    model = SeenModel()
+    _insert(env, model, hdr[:300], pos[:300], np.zeros(300, np.int64))
+    assert epoch() == 1 and env.seen_size == 300
+    ctl[3] = L.CWH_SEEN_MAX_EPOCH
+    torch.cuda.synchronize()
+    rows = np.concatenate([np.random.RandomState(15).permutation(600), 300 + np.arange(40) * 7])      # 600 records, and 40 of the new ones again
+    group = np.zeros(640, np.int64)
+    group[[7, 311, 599, 639]] = [-1, -4, -1, -2]
+    part = group >= 0
+    got, _ = _insert(env, model, hdr[rows], pos[rows], group, engine=True)
+    want, met = np.full(640, -1, np.int64), {}
+    for j in np.flatnonzero(part & (rows >= 300)):                                   # a new record: the smallest participating row that brings it
+        want[j] = met.setdefault(int(rows[j]), int(j))
+    assert np.array_equal(got['first'][part], want[part]) and (got['first'][part] == -1).sum() >= 290
+    assert ((want[600:] >= 0) & (want[600:] < 600)).sum() >= 35
+    assert epoch() == L.CWH_SEEN_MAX_EPOCH + 1 and env.seen_size == len(model)
+    c0 = _counters(env)
+    got, n_off = _insert(env, model, hdr[rows], pos[rows], group, exact=False, engine=True)           # spent: the set neither looks nor learns
+    assert np.array_equal(got['first'][part], np.flatnonzero(part)) and (got['fresh'][part] == 1).all()
+    assert (got['fresh'][~part] == SENT).all() and (got['first'].view(np.uint8).reshape(-1, 4)[~part] == SENT).all()
+    assert (_counters(env) - c0).tolist() == [0, int(part.sum()), 0] and n_off == part.sum() and epoch() == L.CWH_SEEN_MAX_EPOCH + 1
+    assert int(ctl[4].item()) == 0                                                    # (the ticket is back at 0 for the next call)
+    env.seen_clear()
+    assert epoch() == 0 and _counters(env).tolist() == [0, 0, 0]
+    model = SeenModel()
+    got, _ = _insert(env, model, hdr[rows], pos[rows], group)
+    assert got['fresh'][part].sum() == len(model) == env.seen_size and epoch() == 1
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ 5. call order, engines, capture
 def test_clear_and_reserve_drop_the_keys(fresh_set):
     env, model = fresh_set

@@ -136,6 +136,25 @@ def test_seen_out_mirror_matches_the_header_and_the_abi_names_the_calls(lib, tmp
         assert SEEN_FIELDS == tuple(f for f, _ in L.cw_seen_out._fields_)
 
 
+def test_the_epoch_constants_are_the_headers(lib, tmp_path):
+    """CWH_SEEN_ROW_BITS and CWH_SEEN_MAX_EPOCH of the binding against cw_host.h as the C++ compiler reads it, what they promise -- the last usable epoch's
+    bid epoch << ROW_BITS | row fills the owner word and stays below the empty owner, all ones; MAX_EPOCH + 1, the spent epoch, still fits the shifted field --
+    and the epoch's place in the control block (cw_layout.h), which tests/test_seen.py writes"""
+    L, _ = lib
+    csrc = os.path.join(ROOT, 'gym_craftingworld_amd', 'csrc')
+    src, exe = tmp_path / 'epoch.cpp', tmp_path / 'epoch'
+    src.write_text('#include <cstdio>\n#include "cw_host.h"\nint main() { printf("%d %llu %lld\\n", CWH_SEEN_ROW_BITS, (unsigned long long)CWH_SEEN_MAX_EPOCH,'
+                   ' (long long)CWH_MAX_STATES); return 0; }\n')
+    subprocess.check_call(['g++', '-std=c++17', '-Wall', '-Werror', '-I', csrc, str(src), '-o', str(exe)])
+    bits, top, rows = (int(x) for x in subprocess.check_output([str(exe)]).decode().split())
+    assert (bits, top, rows) == (L.CWH_SEEN_ROW_BITS, L.CWH_SEEN_MAX_EPOCH, L.CWH_MAX_STATES)
+    assert rows <= 1 << bits and top + 1 < 1 << (64 - bits)
+    assert ((top << bits) | ((1 << bits) - 1)) < 2 ** 64 - 1 and ((top + 1) << bits) < 2 ** 64
+    layout = open(os.path.join(csrc, 'cw_layout.h')).read()
+    assert 'CW_SEEN_SIZE = 0, CW_SEEN_OVERFLOW = 1, CW_SEEN_COLLISIONS = 2, CW_SEEN_EPOCH = 3, CW_SEEN_TICKET = 4' in layout
+    assert '#define CW_SEEN_CTL_WORDS 8\n' in layout
+
+
 _ASAN_MAIN = r'''
 #include <cstdio>
 #include <cstdlib>
