@@ -205,6 +205,7 @@ HOST_HELPERS = {
     'cwh_reset_grid_of': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'cwh_masked_launch_of': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'cwh_envs_per_wave_of': (C.c_int, [C.c_int, C.c_int]),
+    'cwh_piece_chunks_of': (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'cwh_records_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int]),
     'cwh_plan_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
     'cwh_shoot_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),

@@ -179,6 +179,10 @@ uint32_t cwh_alt_pixel_offset_of(uint32_t size, uint32_t pos, uint32_t item) { r
 int cwh_reset_grid_of(int jobs, int n_cu, int reset_blocks_per_cu) { return cwh_reset_grid(jobs, n_cu, reset_blocks_per_cu); }
 int cwh_masked_launch_of(int n_envs, int n_cu, int reset_blocks_per_cu, int *blocks) { return cwh_masked_launch(n_envs, n_cu, reset_blocks_per_cu, blocks); }
 int cwh_envs_per_wave_of(int n, int most) { return cwh_envs_per_wave(n, most); }
+int cwh_piece_chunks_of(int n_envs, uint32_t frame_bytes, int n_cu, int render_chunk_rounds, int *per)
+{
+    return cwh_piece_chunks(n_envs, frame_bytes, n_cu, render_chunk_rounds, per);
+}
 
 // ------------------------------------------------------------------------------ the argument rules of a call that reads packed records
 int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields,

@@ -97,6 +97,42 @@ static inline int cwh_envs_per_wave(int n, int most)
     return epw;
 }
 int cwh_envs_per_wave_of(int n, int most);         // (the same, exported for the CPU tests)
+// THE CHUNKS of the sweep over one frame array [n_envs][frame_bytes] (cw_launch_sweep).  The sweep's waves are in step only at the start of a
+// launch; over thousands of rounds they drift apart (0.62-0.74 of the HBM peak at 2^20 envs in one launch against 0.86 in eight,
+// profiles/history/r03_other_configs.txt).  So a large batch is swept in chunks of consecutive envs, back-to-back launches on one stream of at most
+// render_chunk_rounds rounds of 3 KB per wave (~2.8 GB; 0: no limit of its own).  The kernels index a chunk with 32-bit offsets and round its bytes up to whole
+// 4-KiB pieces, so a chunk holds at most CWH_CHUNK_MAX_BYTES = 2^32 - 4096 bytes; and every chunk starts on a 4-KiB boundary of the array, so that every
+// wave of a chunk paints whole aligned pieces.  Chunks are whole multiples of 4 096 envs wherever that many frames fit a chunk -- every frame up to 147x147
+// (Ray, 48 S^2 bytes) or 196x196 (AltObs, 27 S (S + 1) bytes).  Larger frames take the smallest count of envs whose frames end on a 4-KiB boundary instead,
+// 4096 / gcd(frame_bytes, 4096): at most 256 envs (Ray frames are multiples of 16 bytes) or 2 048 (AltObs: of 2), under 2^32 bytes at every size up to 255.
+// A batch that needs no split -- one launch within the rounds, at most CWH_CHUNK_MAX_BYTES -- is one chunk of n_envs.
+// -> number of chunks; *per = envs per chunk (the last one may be shorter): chunk c covers envs [c * per, min(n_envs, (c + 1) * per))
+#define CWH_CHUNK_MAX_BYTES ((1ll << 32) - 4096)
+static inline int cwh_piece_chunks(int n_envs, uint32_t frame_bytes, int n_cu, int render_chunk_rounds, int *per)
+{
+    const long long waves = (long long)n_cu * (256 / CW_WAVE), fb = (long long)frame_bytes;
+    const long long cap = (long long)(render_chunk_rounds > 0 ? render_chunk_rounds : 1 << 20) * waves * 3072;
+    const long long bytes = (long long)n_envs * fb;
+    long long n = (bytes + cap - 1) / cap;
+    if (n < 1) n = 1;
+    long long p = (n_envs + n - 1) / n;
+    if (n > 1 || bytes > CWH_CHUNK_MAX_BYTES) {
+        p = (p + 4095) / 4096 * 4096;
+        while (p * fb > CWH_CHUNK_MAX_BYTES && p > 4096) p = (p / 2 + 4095) / 4096 * 4096;
+        if ((p < n_envs ? p : n_envs) * fb > CWH_CHUNK_MAX_BYTES) {      // 4 096 frames do not fit: as few equal chunks of whole granules as the limit allows
+            long long d = 4096;
+            while (fb % d) d >>= 1;                                      // gcd(frame_bytes, 4096)
+            const long long g = 4096 / d;
+            const long long most = CWH_CHUNK_MAX_BYTES / fb / g * g;     // (>= g for every frame the engine accepts; a frame beyond them goes one to a chunk)
+            long long k = most > 0 ? (n_envs + most - 1) / most : n_envs;
+            if (k < n) k = n;                                            // (... and no fewer than the rounds ask for)
+            p = most > 0 ? ((n_envs + k - 1) / k + g - 1) / g * g : 1;
+        }
+    }
+    *per = (int)p;
+    return (int)((n_envs + p - 1) / p);
+}
+int cwh_piece_chunks_of(int n_envs, uint32_t frame_bytes, int n_cu, int render_chunk_rounds, int *per);      // (the same, exported for the CPU tests)
 
 // ---- the argument rules of an entry point that reads PACKED RECORDS and needs no HIP to check them (cw_engine.cpp: cw_expand and cw_simulate turn the code
 // into their error texts), in the order they are tested: some output field, 0 <= n_states <= CWH_MAX_STATES (cw_export_onehot_states and cw_render_records,

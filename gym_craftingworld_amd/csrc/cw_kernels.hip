@@ -2499,7 +2499,7 @@ __global__ __launch_bounds__(256) void cw_render_records_kernel(CwParams P, cons
 // Records (agent, hold, codes, positions of the frames of a job) are fetched a batch of 64 / FPJ jobs ahead, one (job, frame) per lane, and
 // handed to the lanes that paint with ds_bpermute -- asked for before the fill's stores, used after them; no other LDS or memory round trip
 // and no branch in a job but the pace loops and the stores' own predicates.  `src` says which of an env's three states the array shows.
-// The sweep covers envs [env_lo, env_lo + env_n) (a chunk of the batch, cw_piece_chunks): offsets inside a chunk are 32-bit.
+// The sweep covers envs [env_lo, env_lo + env_n) (a chunk of the batch, cwh_piece_chunks): offsets inside a chunk are 32-bit.
 #define CW_PIECE 4096u             // (a sharp optimum: 2 / 8 / 16 KiB pieces are 79 / 18-24 / 20-27 % slower, profiles/history/r03_pieces.txt G)
 #define CW_PIECE_STORES 4          // 1-KiB stores per piece
 #ifndef CW_HEAD_JOBS
@@ -2526,7 +2526,7 @@ __device__ __forceinline__ void render_pieces(const CwParams &P, uint8_t *frames
     const int wave = (int)blockIdx.x * wpb + wave_in_block;                 // (four consecutive pieces per workgroup)
     const uint32_t S = (uint32_t)P.size, FB = P.frame_bytes, row_bytes = (RASTER == 1 ? 9u : 12u) * S;
     uint8_t *const dst_base = frames + (size_t)env_lo * FB;
-    const uint32_t total = (uint32_t)env_n * FB;                             // (cw_piece_chunks: < 2^32)
+    const uint32_t total = (uint32_t)env_n * FB;                             // (cwh_piece_chunks: <= 2^32 - 4096, so total + CW_PIECE - 1 and a0 + CW_PIECE do not wrap)
     const int n_jobs = (int)((total + CW_PIECE - 1u) / CW_PIECE);
     if (wave >= n_jobs) return;
     const int q_mine = (n_jobs + n_waves - 1) / n_waves;
@@ -3035,24 +3035,11 @@ static inline int cw_frames_per_job(uint32_t frame_bytes)
     while (fpj < most) fpj <<= 1;
     return fpj;                                  // <= 16: the smallest frame is 540 bytes (AltObs 4x4)
 }
-// The sweep's waves are in step only at the start of a launch; over thousands of rounds they drift apart (0.62-0.74 of the HBM peak at 2^20
-// envs in one launch against 0.86 in eight, profiles/history/r03_other_configs.txt).  So a large batch is swept in CHUNKS of consecutive envs, back-to-back
-// launches on one stream of at most render_chunk_rounds rounds of 3 KB per wave (~2.8 GB; 32-bit offsets inside a chunk).  Chunks are whole
-// multiples of 4 096 envs: every chunk then starts on a 4-KiB boundary of the array (frames are multiples of 16 bytes for the Ray raster, of
-// 2 for AltObs) and every wave of a chunk paints the same number of pieces.  -> number of chunks; *per = envs per chunk (the last one may be shorter)
+// A large batch is swept in CHUNKS of consecutive envs, back-to-back launches on one stream: the rule is cw_host.h's (cwh_piece_chunks: every chunk
+// at most 2^32 - 4096 bytes and starting on a 4-KiB boundary of the array).  -> number of chunks; *per = envs per chunk (the last one may be shorter)
 static inline int cw_piece_chunks(const CwParams &P, const CwTuning &tn, int *per)
 {
-    const long long waves = (long long)tn.n_cu * (256 / CW_WAVE);
-    const long long cap = (long long)(tn.render_chunk_rounds > 0 ? tn.render_chunk_rounds : 1 << 20) * waves * 3072;
-    const long long bytes = (long long)P.n_envs * P.frame_bytes;
-    int n = (int)((bytes + cap - 1) / cap);
-    if (n < 1) n = 1;
-    *per = (P.n_envs + n - 1) / n;
-    if (n > 1 || bytes >= (1ll << 32)) {
-        *per = (int)(((long long)*per + 4095) / 4096 * 4096);
-        while ((long long)*per * P.frame_bytes >= (1ll << 32) && *per > 4096) *per = (*per / 2 + 4095) / 4096 * 4096;
-    }
-    return (P.n_envs + *per - 1) / *per;
+    return cwh_piece_chunks(P.n_envs, P.frame_bytes, tn.n_cu, tn.render_chunk_rounds, per);
 }
 static inline int cw_render_grid(const CwTuning &tn, long long jobs)
 {
