@@ -533,6 +533,77 @@ void cwo_set_state(cwo_env *e, const uint8_t *grid, const uint8_t *init_grid, in
     else cwo_render(e->cfg.size, e->grid, agent_r, agent_c, hold, e->obs);
 }
 
+/* the three images from the env's records, by the env's own full-frame rasteriser (the persistent obs image equals it: render_edit_cell's
+ * 255 - COLORS_H[hold] is COLORS_N[hold]) */
+static void repaint(cwo_env *e)
+{
+    const int s = e->cfg.size;
+    void (*paint)(int32_t, const uint8_t *, int32_t, int32_t, int32_t, uint8_t *) = e->cfg.alt_obs ? cwo_render_alt : cwo_render;
+    paint(s, e->grid, e->agent_r, e->agent_c, e->hold, e->obs);
+    paint(s, e->init_grid, e->init_agent_r, e->init_agent_c, 0, e->init_img);
+    paint(s, e->goal_grid, e->goal_agent_r, e->goal_agent_c, 0, e->desired_img);
+}
+
+int cwo_set_full(cwo_env *e, const cwo_view *v)
+{
+    const int s = e->cfg.size;
+    const int32_t cells[6] = {v->agent_r, v->agent_c, v->init_agent_r, v->init_agent_c, v->goal_agent_r, v->goal_agent_c};
+    for (int k = 0; k < 6; k++)
+        if (cells[k] < 0 || cells[k] >= s) return -1;
+    if (v->hold < 0 || v->hold > 3 || v->step_num < 0 || !v->grid || !v->init_grid || !v->goal_grid) return -1;
+    const uint8_t *grids[3] = {v->grid, v->init_grid, v->goal_grid};
+    for (int g = 0; g < 3; g++)
+        for (int k = 0; k < e->ncell; k++)
+            if (grids[g][k] > WHEAT) return -1;
+    memmove(e->grid, v->grid, e->ncell);           /* (memmove: a view of this env itself may be handed back) */
+    memmove(e->init_grid, v->init_grid, e->ncell);
+    memmove(e->goal_grid, v->goal_grid, e->ncell);
+    e->agent_r = v->agent_r; e->agent_c = v->agent_c; e->hold = v->hold;
+    e->init_agent_r = v->init_agent_r; e->init_agent_c = v->init_agent_c;
+    e->goal_agent_r = v->goal_agent_r; e->goal_agent_c = v->goal_agent_c;
+    e->achieved = v->achieved; e->desired = v->desired;
+    e->step_num = v->step_num; e->ep_no = v->ep_no;
+    repaint(e);
+    return 0;
+}
+
+int cwo_copy(cwo_env *dst, const cwo_env *src, int32_t with_stream)
+{
+    const cwo_config *a = &dst->cfg, *b = &src->cfg;
+    if (a->size != b->size || a->max_steps != b->max_steps || a->n_task_list != b->n_task_list || a->alt_obs != b->alt_obs ||
+        a->fixed_init_state != b->fixed_init_state)
+        return -1;
+    if (dst == src) return 0;
+    const size_t img = image_bytes(a);
+    memcpy(dst->grid, src->grid, dst->ncell);
+    memcpy(dst->init_grid, src->init_grid, dst->ncell);
+    memcpy(dst->goal_grid, src->goal_grid, dst->ncell);
+    memcpy(dst->obs, src->obs, img);
+    memcpy(dst->desired_img, src->desired_img, img);
+    memcpy(dst->init_img, src->init_img, img);
+    dst->agent_r = src->agent_r; dst->agent_c = src->agent_c; dst->hold = src->hold;
+    dst->init_agent_r = src->init_agent_r; dst->init_agent_c = src->init_agent_c;
+    dst->goal_agent_r = src->goal_agent_r; dst->goal_agent_c = src->goal_agent_c;
+    dst->achieved = src->achieved; dst->desired = src->desired;
+    dst->step_num = src->step_num; dst->ep_no = src->ep_no;
+    dst->cfg.reward_subset = b->reward_subset;     /* the rule the episode is scored by is the episode's */
+    if (with_stream) {
+        memcpy(dst->mt, src->mt, sizeof(dst->mt));
+        dst->mti = src->mti;
+        if (a->fixed_init_state > 0) {
+            memcpy(dst->pool_grid, src->pool_grid, (size_t)a->fixed_init_state * dst->ncell);
+            memcpy(dst->pool_agent, src->pool_agent, (size_t)a->fixed_init_state * sizeof(int));
+        }
+        dst->cfg.stacking = b->stacking;
+        dst->cfg.n_selected = b->n_selected;
+        dst->cfg.number_of_tasks = b->number_of_tasks;
+        memcpy(dst->cfg.selected_bits, b->selected_bits, sizeof(b->selected_bits));
+    }
+    return 0;
+}
+
+void cwo_get_config(const cwo_env *e, cwo_config *cfg) { *cfg = e->cfg; }
+
 int64_t cwo_batch_rollout(cwo_env **envs, int32_t n, const int8_t *actions, int32_t T,
                           int32_t nthreads, int32_t *rewards, uint8_t *dones)
 {

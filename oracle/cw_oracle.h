@@ -82,6 +82,18 @@ void cwo_get_view(const cwo_env *e, cwo_view *v);
 void cwo_set_state(cwo_env *e, const uint8_t *grid, const uint8_t *init_grid, int32_t agent_r,
                    int32_t agent_c, int32_t hold, uint32_t achieved, uint32_t desired,
                    int32_t step_num);
+/* Overwrite an env COMPLETELY (the engine's set_state with every field given): the three grids, the three agent cells, hold, both masks,
+ * step_num and ep_no are taken from `v`; its three image pointers are not read -- obs, init_img and desired_img are repainted from the new
+ * records by the env's own rasteriser.  The stream, the pool and the config stay.  Returns 0, or -1 (env untouched) for a cell off the grid,
+ * a code above 8, a hold outside 0..3 or a null grid.  `v` may be a view of `e` itself with some fields changed. */
+int cwo_set_full(cwo_env *e, const cwo_view *v);
+/* dst <- src, what a snapshot row holds.  Always the EPISODE: the fields cwo_set_full takes, the three images, and the rule the episode is
+ * scored by (cfg.reward_subset).  with_stream != 0: also the MT19937 key and position, the fixed_init_state pool and the task menu
+ * (cfg.stacking, n_selected, number_of_tasks, selected_bits) -- dst is then an exact twin, its later resets included; with_stream == 0: those
+ * three stay dst's own, so dst plays the copied episode to its end and goes on with episodes of its own.  Returns 0, or -1 (dst untouched)
+ * when size, max_steps, n_task_list, alt_obs or fixed_init_state differ. */
+int cwo_copy(cwo_env *dst, const cwo_env *src, int32_t with_stream);
+void cwo_get_config(const cwo_env *e, cwo_config *cfg); /* the config as it stands now (cwo_copy changes the menu part) */
 /* craftingworld_altobs.py:489-595 render(state): out[(3s+3)*3s*3], values modulo 256 (the reference's int
  * image reaches 2 x colour when the agent holds sticks on a sticks cell) */
 void cwo_render_alt(int32_t size, const uint8_t *grid, int32_t agent_r, int32_t agent_c, int32_t hold,

@@ -75,6 +75,11 @@ def _lib():
         lib.cwo_set_state.argtypes = [vp, u8p, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                       C.c_uint32, C.c_int32]
         lib.cwo_render.argtypes = [C.c_int32, u8p, C.c_int32, C.c_int32, C.c_int32, u8p]
+        lib.cwo_set_full.restype = C.c_int
+        lib.cwo_set_full.argtypes = [vp, C.POINTER(_View)]
+        lib.cwo_copy.restype = C.c_int
+        lib.cwo_copy.argtypes = [vp, vp, C.c_int32]
+        lib.cwo_get_config.argtypes = [vp, C.POINTER(_Config)]
         lib.cwo_batch_rollout_full.restype = C.c_int64
         lib.cwo_batch_rollout_full.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_int32]
         lib.cwo_batch_rollout.restype = C.c_int64
@@ -215,6 +220,50 @@ class OracleEnv:
         u8p = C.POINTER(C.c_uint8)
         self._lib.cwo_set_state(self._h, g.ctypes.data_as(u8p), ig.ctypes.data_as(u8p), int(agent[0]),
                                 int(agent[1]), int(hold), int(achieved), int(desired), int(step_num))
+
+    def set_full(self, grid, init_grid, goal_grid, agent, init_agent, goal_agent, hold, achieved, desired, step_num, ep_no):
+        """every field of the env (CraftingWorldVecEnv.set_state with every field given); the three images are repainted"""
+        u8p = C.POINTER(C.c_uint8)
+        keep = [np.ascontiguousarray(g, dtype=np.uint8) for g in (grid, init_grid, goal_grid)]
+        if any(g.size != self.size * self.size for g in keep):
+            raise ValueError('grids must hold size * size codes')
+        v = _View(grid=keep[0].ctypes.data_as(u8p), init_grid=keep[1].ctypes.data_as(u8p), goal_grid=keep[2].ctypes.data_as(u8p),
+                  agent_r=int(agent[0]), agent_c=int(agent[1]), init_agent_r=int(init_agent[0]), init_agent_c=int(init_agent[1]),
+                  goal_agent_r=int(goal_agent[0]), goal_agent_c=int(goal_agent[1]), hold=int(hold), achieved=int(achieved), desired=int(desired),
+                  step_num=int(step_num), ep_no=int(ep_no))
+        if self._lib.cwo_set_full(self._h, C.byref(v)) != 0:
+            raise ValueError('cwo_set_full rejected the state')
+
+    def update(self, **fields):
+        """set_full with the env's own value for every field not named (names as state() gives them)"""
+        st = self.state()
+        names = ('grid', 'init_grid', 'goal_grid', 'agent', 'init_agent', 'goal_agent', 'hold', 'achieved', 'desired', 'step_num', 'ep_no')
+        if set(fields) - set(names):
+            raise ValueError('cannot set %s' % sorted(set(fields) - set(names)))
+        self.set_full(**{k: fields.get(k, st[k]) for k in names})
+
+    def copy_from(self, src, with_stream=True):
+        """self <- src, what a snapshot row holds (cwo_copy): the episode, and with_stream the stream, the pool and the task menu too"""
+        if self._lib.cwo_copy(self._h, src._h, 1 if with_stream else 0) != 0:
+            raise ValueError('cwo_copy: the two envs differ in size, max_steps, task_list, rasteriser or pool size')
+        self._lib.cwo_get_config(self._h, C.byref(self.cfg))
+
+    def clone(self):
+        """a new env that is an exact twin of this one"""
+        cfg = _Config()
+        self._lib.cwo_get_config(self._h, C.byref(cfg))
+        twin = OracleEnv.__new__(OracleEnv)
+        twin._lib, twin.cfg = self._lib, cfg
+        twin._h = self._lib.cwo_new(C.byref(cfg))
+        twin.size, twin.img_shape, twin.MAX_STEPS, twin.n_task_list = self.size, self.img_shape, self.MAX_STEPS, self.n_task_list
+        twin.copy_from(self, True)
+        return twin
+
+    def menu(self):
+        """the task-menu part of the config as it stands now: (stacking, number_of_tasks, the selected bits in order)"""
+        cfg = _Config()
+        self._lib.cwo_get_config(self._h, C.byref(cfg))
+        return (cfg.stacking, cfg.number_of_tasks, tuple(cfg.selected_bits[:cfg.n_selected]))
 
 
 def render(size, grid, agent, hold):

@@ -1,10 +1,8 @@
 """GPU tier of the device-resident snapshots: cw_snapshot_save_kernel / cw_snapshot_load_kernel through CraftingWorldVecEnv.snapshot_*.  Every load is
 checked env by env with snapshot_check.check_load (itself tested on the CPU, tests/test_snapshot_logic.py) -- restored envs against their saved source,
 all others byte for byte -- and the forked batch is then continued against the CPU oracle, which is brought to the same fork on the host from its OWN
-values (a replay of the source's lineage, or OracleEnv.set_state from the oracle's state at save time) and reads nothing of the engine but the actions.
+values (cwo_copy from a clone of the source taken at save time, with or without the stream) and reads nothing of the engine but the actions.
 Everything is bit-exact.  No timing."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -56,14 +54,8 @@ def _rows_of_test_1():
     return save, load
 
 
-def _frames_of(st, alt):
-    """the three frames of an oracle env's state() by the full-frame rasteriser -> {frame array of the engine: uint8 frame}"""
-    return {'observation': oracle_frame(st['grid'], st['agent'], st['hold'], alt), 'init_observation': oracle_frame(st['init_grid'], st['init_agent'], 0, alt),
-            'desired_goal': oracle_frame(st['goal_grid'], st['goal_agent'], 0, alt)}
-
-
 def _round_trip_and_fork(engine, with_stream, S):
-    from oracle import OracleBatch, OracleEnv
+    from oracle import OracleBatch
     ekw, KW = dict(SNAPSHOT_ENGINES[engine]), k_of(S)
     raster, pixels, K = ekw.get('raster', 'ray'), ekw['obs_mode'] != 'state', ekw.get('fixed_init_state', 0)
     env, keys, pos = make_env(N1, *np_states(N1, 31000), **ekw, **KW)
@@ -80,7 +72,7 @@ def _round_trip_and_fork(engine, with_stream, S):
     save_rows, load_rows = _rows_of_test_1()
     saved = take(env)
     pool_saved = env.fixed_states() if K else None
-    o_saved = [e.state() for e in ora.envs]                       # the oracle's own values at save time
+    o_saved = [e.clone() for e in ora.envs]                       # the oracle's own envs at save time
     env.snapshot_save(save_rows)                                  # (validated and packed on the host: vec_env.snapshot_rows)
     check_save(saved, take(env))
     a2 = spread(env, 11, 2)                                       # states move, episodes end
@@ -104,37 +96,19 @@ def _round_trip_and_fork(engine, with_stream, S):
         crossing = [j for j, s in zip(good, src) if ekw['env_menu'][j] != ekw['env_menu'][s]]
         assert len(crossing) >= 5                                 # (envs 0, 2, 4, ... continue from env 3, of the other menu)
         assert np.array_equal(after['hdr'][good, 3], ekw['env_menu'][src] if with_stream else ekw['env_menu'][good])
-    # ---- the oracle, brought to the same fork on the host
-    ep_shift = np.zeros(N1, np.int64)
+    # ---- the oracle, brought to the same fork on the host: every restored env from the clone taken of its source at save time (cwo_copy: the episode,
+    # and with the stream the stream, pool and menu too), so that whole states are compared at once, with and without the stream
     for j, s in zip(good.tolist(), src.tolist()):
-        if with_stream:                                           # an exact twin: the source's lineage, replayed up to the save
-            twin = OracleEnv(rng_state=(keys[s], int(pos[s])), **dict(okw, **per_env[s]))
-            twin.reset()
-            for a in a1[:, s]:
-                if twin.step(int(a))[2]:
-                    twin.reset()
-            ora.envs[j] = twin
-        else:                                                     # the saved episode on the env's own stream, menu and pool
-            st, e = o_saved[s], ora.envs[j]
-            ep_shift[j] = st['ep_no'] - e.view().ep_no
-            e.set_state(st['grid'], st['init_grid'], st['agent'], st['hold'], st['achieved'], st['desired'], st['step_num'])
-    ora._handles = (C.c_void_p * N1)(*[e._h for e in ora.envs])
-    if with_stream:
-        same_states(env, ora, frames=tuple(FRAMES) if pixels else (), tag='right after the load: ')
-    elif pixels:                                                  # the frames the load painted: the oracle's rasteriser on the oracle's saved states
-        want = [_frames_of(o_saved[s], raster == 'alt') for s in src]
-        for k in FRAMES:
-            same('right after the load: ' + k, good, after[k][good], np.stack([w[k] for w in want]))
+        ora.envs[j].copy_from(o_saved[s], with_stream)
+    same_states(env, ora, frames=tuple(FRAMES) if pixels else (), tag='right after the load: ')
     T = 2 * KW['max_steps'] + 3
     acts = torch.randint(0, 6, (T, N1), device='cuda', dtype=torch.uint8, generator=torch.Generator(device='cuda').manual_seed(3))
     r_host, d_host = _step_recorded(env, acts)
     _, o_rew, o_done = ora.rollout(acts.cpu().numpy().astype(np.int8), nthreads=16, record=True)
     same('reward of every step after the fork', 0, r_host.T, o_rew.T)
     same('done of every step after the fork', 0, d_host.T, o_done.astype(bool).T)
-    assert d_host.sum(axis=0).min() >= 2                          # every env has been reset since: the oracle's set_state leaves nothing undefined
-    snap = snapshot(env, frames=tuple(FRAMES) if pixels else ())
-    snap['ep_no'] = snap['ep_no'] - ep_shift                      # (set_state keeps the oracle env's own episode count: the row's differs by a constant)
-    same_states(snap, ora, frames=tuple(FRAMES) if pixels else (), tag='%d steps after the fork: ' % T)
+    assert d_host.sum(axis=0).min() >= 2                          # every env has been reset twice since, on whichever stream it continues
+    same_states(env, ora, frames=tuple(FRAMES) if pixels else (), tag='%d steps after the fork: ' % T)
     env.close()
 
 
