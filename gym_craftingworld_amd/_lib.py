@@ -126,6 +126,7 @@ ABI = {
     'cw_reach_reserve': (C.c_int, [_VP, C.c_int64, C.c_int32]),
     'cw_reach_bytes': (C.c_size_t, [_VP]),
     'cw_reach': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_reach_out), _VP]),
+    'cw_load_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
@@ -182,6 +183,8 @@ CWH_SEEN_ROW_BITS, CWH_SEEN_MAX_EPOCH = 28, (1 << 36) - 2
 CWH_REACH_OK, CWH_REACH_NO_FIELD, CWH_REACH_N_STATES, CWH_REACH_DEPTH, CWH_REACH_PAIR, CWH_REACH_ENV_OF, CWH_REACH_OWN_STATES, CWH_REACH_ALIGN, \
     CWH_REACH_OVERLAP = range(9)
 CWH_REACH_CHUNK, CWH_REACH_MAX_ROWS, CWH_REACH_MAX_DEPTH, CWH_REACH_BLOCKS_PER_CU, CWH_REACH_SECTIONS = 4096, (2 ** 28 - 1) // 6 - 63, 32767, 8, 18
+CWH_LOAD_OK, CWH_LOAD_NO_RECORDS, CWH_LOAD_N_RECORDS, CWH_LOAD_OWN_ORDER, CWH_LOAD_ALIGN, CWH_LOAD_ENGINE_OVERLAP, CWH_LOAD_STATUS_OVERLAP = range(7)
+CWH_LOAD_NO_PART, CWH_LOAD_LOADED, CWH_LOAD_BAD_INDEX, CWH_LOAD_REFUSED = range(4)
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -217,6 +220,9 @@ HOST_HELPERS = {
     'cwh_seen_hash_of': (C.c_uint64, [_VP]),
     'cwh_seen_slots_of': (C.c_int64, [C.c_int64]),
     'cwh_seen_args': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64]),
+    'cwh_record_ok_of': (C.c_int, [C.c_uint32, _VP, _VP]),
+    'cwh_load_record_index_in_range': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_load_records_args': (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64]),
     'cwh_reach_rows_of': (C.c_int64, [C.c_int64]),
     'cwh_reach_chunks_of': (C.c_int64, [C.c_int64]),
     'cwh_reach_grid_of': (C.c_int64, [C.c_int64, C.c_int32]),

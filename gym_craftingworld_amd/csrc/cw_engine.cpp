@@ -27,6 +27,8 @@ hipError_t cwk_launch_imagine_masked(const CwParams *P, const CwTuning *T, const
 hipError_t cwk_launch_sample_state_masked(const CwParams *P, const CwTuning *T, const uint8_t *mask, int pooled, uint16_t *out_cells, hipStream_t st);
 hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, hipStream_t st);
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st);
+hipError_t cwk_launch_load_records(const CwParams *P, const CwTuning *T, const int32_t *src, const uint4 *hdr, const uint4 *pos, int n_records, uint8_t *status,
+                                   int obs_mode, hipStream_t st);
 hipError_t cwk_launch_expand(const CwParams *P, const int32_t *env_of, const uint4 *hdr_in, const uint4 *pos_in, int n_states, const CwExpandOut *O, hipStream_t st);
 hipError_t cwk_launch_export_onehot_states(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, int n_states, uint8_t *out, hipStream_t st);
 hipError_t cwk_launch_render_records(const CwParams *P, const CwTuning *T, const uint4 *hdr, const uint4 *pos, const uint8_t *mask, int n_states, uint8_t *out,
@@ -229,7 +231,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_reach, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -1176,6 +1178,29 @@ int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const
     if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_seen_insert(&e->P, &e->tune, &e->Sn, group, (const uint4 *)hdr, (const uint4 *)slot_pos, n_states, out->fresh, out->first,
                                    (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ load records: packed records into envs
+// Checks (cwh_load_records_args, tested on the CPU), then ONE kernel: no wait, no allocation, the same call whether it runs or is captured.
+int cw_load_records(cw_engine *e, const int32_t *src, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_records, uint8_t *status, cw_stream_t stream)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_load_records: null engine");
+    switch (cwh_load_records_args(e->n, (uint64_t)(uintptr_t)src, (uint64_t)(uintptr_t)hdr, (uint64_t)(uintptr_t)slot_pos, n_records, (uint64_t)(uintptr_t)status,
+                                  (uint64_t)(uintptr_t)e->P.hdr, (uint64_t)(uintptr_t)e->P.pos)) {
+    case CWH_LOAD_OK: break;
+    case CWH_LOAD_NO_RECORDS: return fail(CW_ERR_INVALID, "cw_load_records: null %s", !hdr ? "hdr" : "slot_pos");
+    case CWH_LOAD_N_RECORDS: return fail(CW_ERR_INVALID, "cw_load_records: n_records = %d must be 0 .. %d", n_records, CWH_MAX_STATES);
+    case CWH_LOAD_OWN_ORDER: return fail(CW_ERR_INVALID, "cw_load_records: n_records = %d must be num_envs = %d without src", n_records, e->n);
+    case CWH_LOAD_ALIGN: return fail(CW_ERR_INVALID, "cw_load_records: hdr / slot_pos must be 16-byte aligned, src 4-byte aligned");
+    case CWH_LOAD_ENGINE_OVERLAP: return fail(CW_ERR_INVALID, "cw_load_records: the records overlap the engine's own hdr / slot_pos buffers (clone them first)");
+    default: return fail(CW_ERR_INVALID, "cw_load_records: status overlaps the records or src");
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_load_records called before cw_reset");
+    if (n_records == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_load_records(&e->P, &e->tune, src, (const uint4 *)hdr, (const uint4 *)slot_pos, n_records, status, e->obs_mode, (hipStream_t)stream));
     return in.done();
 }
 

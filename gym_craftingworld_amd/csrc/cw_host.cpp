@@ -282,6 +282,40 @@ int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_sta
     return CWH_SEEN_OK;
 }
 
+// ------------------------------------------------------------------------------ cw_load_records: the rule a record passes, the index check, the argument rules
+int cwh_record_ok_of(uint32_t size, const uint8_t *hdr, const uint16_t *slot_pos)
+{
+    uint32_t h[4], p[4];
+    for (int i = 0; i < 4; i++) {
+        h[i] = (uint32_t)hdr[4 * i] | (uint32_t)hdr[4 * i + 1] << 8 | (uint32_t)hdr[4 * i + 2] << 16 | (uint32_t)hdr[4 * i + 3] << 24;
+        uint16_t lo, hi;
+        memcpy(&lo, (const char *)slot_pos + 4 * i, 2);
+        memcpy(&hi, (const char *)slot_pos + 4 * i + 2, 2);
+        p[i] = (uint32_t)lo | (uint32_t)hi << 16;
+    }
+    return cwh_record_ok(size, h, p);
+}
+int cwh_load_record_index_in_range(int32_t index, int32_t n_records) { return cwh_load_record_index_ok(index, n_records); }
+
+int cwh_load_records_args(int32_t num_envs, uint64_t src, uint64_t hdr, uint64_t slot_pos, int32_t n_records, uint64_t status, uint64_t engine_hdr,
+                          uint64_t engine_slot_pos)
+{
+    if (!hdr || !slot_pos) return CWH_LOAD_NO_RECORDS;
+    if (n_records < 0 || n_records > CWH_MAX_STATES) return CWH_LOAD_N_RECORDS;
+    if (!src && n_records != num_envs) return CWH_LOAD_OWN_ORDER;
+    if ((hdr & 15u) || (slot_pos & 15u) || (src & 3u)) return CWH_LOAD_ALIGN;
+    const uint64_t r = 16ull * (uint64_t)n_records, n = num_envs > 0 ? (uint64_t)num_envs : 0;
+    const uint64_t recs[2] = {hdr, slot_pos}, own[2] = {engine_hdr, engine_slot_pos};
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++)
+            if (own[j] && cwh_ranges_overlap(recs[i], r, own[j], 16 * n)) return CWH_LOAD_ENGINE_OVERLAP;
+    if (status) {
+        if (cwh_ranges_overlap(status, n, hdr, r) || cwh_ranges_overlap(status, n, slot_pos, r)) return CWH_LOAD_STATUS_OVERLAP;
+        if (src && cwh_ranges_overlap(status, n, src, 4 * n)) return CWH_LOAD_STATUS_OVERLAP;
+    }
+    return CWH_LOAD_OK;
+}
+
 // ------------------------------------------------------------------------------ cw_reach: the rows of a level, the workspace's sections, the argument rules
 int64_t cwh_reach_rows_of(int64_t f) { return cwh_reach_rows(f); }
 int64_t cwh_reach_chunks_of(int64_t rows) { return cwh_reach_chunks(rows); }

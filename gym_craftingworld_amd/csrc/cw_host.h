@@ -258,6 +258,44 @@ int64_t cwh_seen_slots_of(int64_t capacity);
 enum { CWH_SEEN_OK = 0, CWH_SEEN_NO_RECORDS = 1, CWH_SEEN_NO_FIELD = 2, CWH_SEEN_N_STATES = 3, CWH_SEEN_ALIGN = 4, CWH_SEEN_OVERLAP = 5 };
 int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_states, uint64_t fresh, uint64_t first);
 
+// ---- cw_load_records: packed records INTO envs.  The pure calls above only compare a record's cells; a loaded record becomes engine state -- the dirty-cell
+// painter turns the agent's cell into an address, the colour tables are indexed by code -- so an env takes a record only after THE RULE, shared by the kernel
+// and the host.  hdr and slot_pos as the four little-endian dwords of a record each (the uint4 the kernels load), S the grid size.  A record passes iff the
+// agent's row and column are below S, hold <= 3, every slot code <= 8, every slot is one of gone (0xFFFF) with code 0 / held (0xFFFE) with code == hold != 0 /
+// on the grid (below S * S) with a code -- any other position or pairing fails --, exactly one slot is held if hold != 0 and none otherwise, and the
+// on-grid positions are pairwise different (the sparse layout's "one object per cell").  The masks, step_num, the flag word and the menu byte are free.
+static inline CWH_HOST_DEVICE int cwh_record_ok(uint32_t size, const uint32_t hdr[4], const uint32_t pos[4])
+{
+    const uint32_t hold = (hdr[0] >> 16) & 0xFFu, ncell = size * size;
+    int ok = (hdr[0] & 0xFFu) < size && ((hdr[0] >> 8) & 0xFFu) < size && hold <= 3u;
+    uint32_t p[8], held = 0;
+    for (int k = 0; k < 8; k++) {
+        const uint32_t code = (hdr[3] >> (4 * k)) & 15u;
+        p[k] = (pos[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+        const int gone = p[k] == 0xFFFFu && code == 0u, in_hand = p[k] == 0xFFFEu && code == hold && hold != 0u, on_grid = p[k] < ncell && code != 0u;
+        ok &= code <= 8u && (gone || in_hand || on_grid);
+        held += p[k] == 0xFFFEu;
+    }
+    ok &= held == (hold != 0u ? 1u : 0u);
+    for (int k = 1; k < 8; k++)
+        for (int j = 0; j < k; j++) ok &= p[k] >= 0xFFFEu || p[k] != p[j];
+    return ok;
+}
+int cwh_record_ok_of(uint32_t size, const uint8_t *hdr /* [16] */, const uint16_t *slot_pos /* [8] */);       // (exported for the CPU tests; any alignment)
+// THE index check of cw_load_records_kernel, shared by host and device: an entry of the caller's src array may index the records only if this says so
+static inline CWH_HOST_DEVICE int cwh_load_record_index_ok(int32_t index, int32_t n_records) { return index >= 0 && index < n_records; }
+int cwh_load_record_index_in_range(int32_t index, int32_t n_records);      // (the same, exported for the CPU tests)
+// what cw_load_records_kernel leaves in status[env]
+enum { CWH_LOAD_NO_PART = 0, CWH_LOAD_LOADED = 1, CWH_LOAD_BAD_INDEX = 2, CWH_LOAD_REFUSED = 3 };
+// the argument rules of cw_load_records, in the order they are tested; addresses as integers (0: null): records given (CWH_LOAD_NO_RECORDS), 0 <= n_records <=
+// CWH_MAX_STATES (CWH_LOAD_N_RECORDS), without src n_records = num_envs (CWH_LOAD_OWN_ORDER), hdr and slot_pos 16-byte aligned and src 4-byte aligned
+// (CWH_LOAD_ALIGN), the records sharing no byte with the engine's own hdr / slot_pos arrays -- engine_hdr, engine_slot_pos: 16 * num_envs bytes each; env i
+// would be written while env j reads it -- (CWH_LOAD_ENGINE_OVERLAP), status sharing no byte with the records or src (CWH_LOAD_STATUS_OVERLAP)
+enum { CWH_LOAD_OK = 0, CWH_LOAD_NO_RECORDS = 1, CWH_LOAD_N_RECORDS = 2, CWH_LOAD_OWN_ORDER = 3, CWH_LOAD_ALIGN = 4, CWH_LOAD_ENGINE_OVERLAP = 5,
+       CWH_LOAD_STATUS_OVERLAP = 6 };
+int cwh_load_records_args(int32_t num_envs, uint64_t src, uint64_t hdr, uint64_t slot_pos, int32_t n_records, uint64_t status, uint64_t engine_hdr,
+                          uint64_t engine_slot_pos);
+
 // ---- cw_reach: breadth-first search on the device (cw_reach_reserve / cw_reach).  THE ROWS of a level over a frontier of F states: row a * Fp + j is action a
 // on frontier state j, Fp = F rounded up to a wavefront, so that no wave straddles two actions; rows j >= F of an action take no part.  The order is the one
 // a * F + j gives.  The row is the row field of the visited set's bids: 6 * (max_rows + 63) < 2^CWH_SEEN_ROW_BITS is the cap on max_rows.

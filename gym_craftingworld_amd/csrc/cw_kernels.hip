@@ -13,6 +13,8 @@
 //                     cw_sample_state_masked_kernel: sample_state() / generate_fixed_initial_state() from the selected envs' streams.
 //   cw_snapshot_save_kernel / cw_snapshot_load_kernel  envs into rows of the engine's device-resident snapshot bank and back (restore, fork), dealt out the
 //                     same way by a device array of row numbers.
+//   cw_load_records_kernel  packed records of the caller's INTO envs (the other direction of the record family below), dealt out the same way by a device
+//                     array of record indices; a record is loaded only after the rule of cw_host.h (cwh_record_ok), and its obs frame painted on the spot.
 //   cw_expand_kernel  the successors of all six actions of M states (the engine's own or packed records of the caller's), one lane per (action, state) pair with
 //                     the action uniform across a wave; writes nothing of the engine.  cw_export_onehot_states_kernel: the one-hot view of such records.
 //   cw_render_records_kernel  the frames of such records in the engine's raster, one wave per state (paint_state_frame); writes nothing of the engine.
@@ -1903,7 +1905,7 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_imagine_masked_ker
 }
 
 // ------------------------------------------------------------------------------------ the dealer
-// THE DEALER of cw_reset_masked_kernel (above), written once for cw_sample_state_masked_kernel and the two snapshot kernels: a workgroup scans `epb`
+// THE DEALER of cw_reset_masked_kernel (above), written once for cw_sample_state_masked_kernel, the two snapshot kernels and cw_load_records_kernel: a workgroup scans `epb`
 // consecutive envs per round, grid-stride over the chunks; all four waves evaluate the same selection, one env per lane, and hold the same ballot: the
 // selected env of rank k goes to wave k mod 4.
 // cw_reset_masked_kernel and cw_imagine_masked_kernel KEEP THEIR OWN COPY of this loop: as bodies of deal_envs their code moved, and the calls that paint
@@ -2072,6 +2074,51 @@ __global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_snapshot_load_kern
             paint_state_frame(P, P.init_img + off, jp, CW_CODES_INITIAL, __builtin_amdgcn_readfirstlane(ia), 0u, lane);
             unpack_uniform(gp, jp);
             paint_state_frame(P, P.desired_img + off, jp, __builtin_amdgcn_readfirstlane(gc), __builtin_amdgcn_readfirstlane(ga), 0u, lane);
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------ records into envs
+// cw_load_records: env i <- the caller's packed record src[i] (src null: record i; negative: env i takes no part); any number of envs may name one record.
+// Dealt out by deal_envs like the bank kernels.  The pick, one env per lane: the index becomes an address only behind cwh_load_record_index_ok, the lane then
+// loads its record and puts it to THE RULE (cwh_record_ok) -- a loaded record becomes engine state, which the painters turn into addresses.  An env whose index
+// is out of range or whose record is refused is left exactly as it is and counted in counters[6], once: by wave 0 of the workgroup that balloted it, which
+// also writes every env's status byte.  The ticket of an env that loads is its record's index, and the wave it is dealt to loads that record again, uniformly.
+// The env receives the record's hdr but byte 3 (it keeps its own menu id), its slot_pos, the mask outputs (store_env_state) and -- PAINT, the pixel modes --
+// its obs frame, held item included.  The episode's start and goal states and their frames, ep_no, the stream, the ring, the pool, reward, done, the episode
+// outputs, terminal_obs and every other counter are not written: a load is not a step and not a finished episode.  No LDS.
+template <bool PAINT>
+__global__ __launch_bounds__(CW_RESET_WAVES *CW_WAVE) void cw_load_records_kernel(CwParams P, const int32_t *__restrict__ src, const uint4 *__restrict__ hdr,
+                                                                                    const uint4 *__restrict__ pos, int n_records, uint8_t *__restrict__ status,
+                                                                                    int epb)
+{
+    deal_envs(P, epb, [&](int mine, bool in_chunk, int wave_in_block, int lane) {
+        const int32_t v_idx = in_chunk ? (src ? src[mine] : mine) : -1;
+        const bool v_in = cwh_load_record_index_ok(v_idx, n_records) != 0;
+        bool v_ok = false;
+        if (v_in) {                                                               // (an address only behind the check)
+            const uint4 h = hdr[v_idx], p = pos[v_idx];
+            const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, pw[4] = {p.x, p.y, p.z, p.w};
+            v_ok = cwh_record_ok((uint32_t)P.size, hw, pw) != 0;
+        }
+        const unsigned long long skipped = CW_BALLOT(v_idx >= 0 && !v_ok);
+        if (wave_in_block == 0) {
+            if (skipped && lane == 0) atomicAdd(&P.counters[6], (unsigned long long)__builtin_popcountll(skipped));
+            if (status && in_chunk)
+                status[mine] = (uint8_t)(v_idx < 0 ? CWH_LOAD_NO_PART : v_ok ? CWH_LOAD_LOADED : v_in ? CWH_LOAD_REFUSED : CWH_LOAD_BAD_INDEX);
+        }
+        return v_ok ? v_idx : -1;
+    },
+              [&](int env, int32_t ticket, int, int lane) {
+        uint4 h = hdr[ticket];
+        const uint4 ps = pos[ticket];
+        h.x = (h.x & 0x00FFFFFFu) | (P.hdr[env].x & 0xFF000000u);                 // (the env's own menu id)
+        if (lane == 0) store_env_state(P, env, h, ps);
+        if constexpr (PAINT) {
+            const uint32_t hx = __builtin_amdgcn_readfirstlane(h.x);
+            uint32_t jp[8];
+            unpack_uniform(ps, jp);
+            paint_state_frame(P, P.obs + (size_t)env * P.frame_bytes, jp, __builtin_amdgcn_readfirstlane(h.w), agent_cell_of(P, hx), hold_of(hx), lane);
         }
     });
 }
@@ -3208,6 +3255,13 @@ hipError_t cwk_launch_snapshot_save(const CwParams *P, const CwTuning *T, const 
 hipError_t cwk_launch_snapshot_load(const CwParams *P, const CwTuning *T, const CwBank *B, const int32_t *rows, int with_stream, int obs_mode, hipStream_t st)
 {
     return cw_launch_dealt(obs_mode != 0 ? cw_snapshot_load_kernel<true> : cw_snapshot_load_kernel<false>, P, T, st, *B, rows, with_stream);
+}
+
+// cw_load_records: one launch, in the masked kernels' shape
+hipError_t cwk_launch_load_records(const CwParams *P, const CwTuning *T, const int32_t *src, const uint4 *hdr, const uint4 *pos, int n_records, uint8_t *status,
+                                   int obs_mode, hipStream_t st)
+{
+    return cw_launch_dealt(obs_mode != 0 ? cw_load_records_kernel<true> : cw_load_records_kernel<false>, P, T, st, src, hdr, pos, n_records, status);
 }
 
 // cw_plan: one launch, grid = (ceil(n_states / 256), 6 first actions)

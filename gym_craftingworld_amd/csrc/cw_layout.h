@@ -231,8 +231,8 @@ struct CwParams {
                                        // adapts its refill period to it without ever waiting for the card (cw_engine.cpp: cw_step)
     unsigned long long *counters; // [4] public: steps, finished, successes, invalid actions; [4] PRIVATE: the finished count the last sweep of the
                                   // observation array saw (cw_render_pieces_kernel: what kind of step does it follow?), [5] PRIVATE: resets of
-                                  // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot save / load
-                                  // skipped for a bad row number (cw_snapshot_save_kernel, cw_snapshot_load_kernel); [7] public: states cw_expand_kernel,
+                                  // look-ahead engines that found no record and were taken the slow way; [6] public: envs a snapshot or record load
+                                  // skipped (cw_snapshot_save_kernel, cw_snapshot_load_kernel: a bad row number; cw_load_records_kernel: an index out of range, a refused record); [7] public: states cw_expand_kernel,
                                   // cw_simulate_kernel or cw_plan_kernel skipped for an env index at or above n_envs; 8 words allocated
     const CwMenuDev *menus;
     // constants

@@ -182,6 +182,69 @@ def snapshot_rows(num_envs, capacity, rows, envs=None, fork=False):
     return np.ascontiguousarray(out, dtype=np.int32)
 
 
+LOAD_NO_PART, LOAD_LOADED, LOAD_BAD_INDEX, LOAD_REFUSED = range(4)     # the status bytes of load_records(status=True)
+
+
+def load_records_src(num_envs, n_records, src=None, envs=None):
+    """The record indices cw_load_records takes, built and validated on the host: -> np.int32 [num_envs], entry i = the record env i takes, -1 = env i takes
+    no part.  Neither `src` nor `envs`: record i for env i (n_records must be num_envs).  `src` alone: one entry per env (a negative entry = no part).  With
+    `envs`: envs[j] is paired with src[j] (env ids in -num_envs .. num_envs - 1; src None: with record j), every env not listed takes no part; any number
+    of envs may name one record.  ValueError for lengths that differ, an env listed twice, anything that is not a flat integer list; IndexError for an env
+    outside the batch or an index outside the records."""
+    num_envs, n_records = int(num_envs), int(n_records)
+    if src is None:
+        r = np.arange(n_records if envs is None else len(np.asarray(envs).reshape(-1)), dtype=np.int64)
+    else:
+        r = np.asarray(src)
+        if r.ndim != 1 or (r.size and (r.dtype == np.bool_ or not np.issubdtype(r.dtype, np.integer))):
+            raise ValueError('src must be a flat list of integer record indices')
+        r = r.astype(np.int64)
+    if envs is None:
+        if len(r) != num_envs:
+            raise ValueError('%s must hold one entry per env (%d), got %d' % ('the records' if src is None else 'src', num_envs, len(r)))
+        out = np.where(r < 0, -1, r)
+    else:
+        e = np.asarray(envs)
+        if e.ndim != 1 or (e.size and not np.issubdtype(e.dtype, np.integer)):
+            raise ValueError('envs must be a flat list of integer env ids')
+        e = e.astype(np.int64)
+        if len(e) != len(r):
+            raise ValueError('%d envs but %d record indices' % (len(e), len(r)))
+        bad = e[(e < -num_envs) | (e >= num_envs)]
+        if bad.size:
+            raise IndexError('env index %d outside a batch of %d envs' % (int(bad[0]), num_envs))
+        e = np.where(e < 0, e + num_envs, e)
+        if len(np.unique(e)) != len(e):
+            raise ValueError('an env is listed twice')
+        out = np.full(num_envs, -1, np.int64)
+        out[e] = np.where(r < 0, -1, r)
+    if out.size and out.max() >= n_records:
+        raise IndexError('record index %d outside %d records' % (int(out[out >= n_records][0]), n_records))
+    return np.ascontiguousarray(out, dtype=np.int32)
+
+
+def load_records_args(num_envs, size, hdr, slot_pos, src=None, envs=None, record_ok=None):
+    """What cw_load_records is handed, validated and packed on the host (numpy inputs): -> (hdr uint8 [R, 16], slot_pos uint16 [R, 8], src int32 [num_envs]),
+    all contiguous.  hdr uint8 [..., 16] and slot_pos int16 / uint16 [..., 8] under expand_args' rules (both required, flattened to R records); src / envs
+    as load_records_src takes them.  Every record some env takes is put to THE RULE the kernel applies -- record_ok(size, hdr16, slot_pos8) -> bool, by
+    default the library's own cwh_record_ok_of (include/craftingworld.h states the rule) -- and ValueError names the first one that fails it."""
+    if hdr is None or slot_pos is None:
+        raise ValueError('load_records needs hdr and slot_pos')
+    hdr, slot_pos = np.asarray(hdr), np.asarray(slot_pos)
+    r = _expand_m(1, (hdr.shape, hdr.dtype), (slot_pos.shape, slot_pos.dtype), None)
+    idx = load_records_src(num_envs, r, src, envs)
+    hdr = np.ascontiguousarray(hdr).reshape(r, 16)
+    slot_pos = np.ascontiguousarray(slot_pos).reshape(r, 8).view(np.uint16)
+    if record_ok is None:
+        lib = L.load()
+        record_ok = lambda s, h, p: lib.cwh_record_ok_of(s, h.ctypes.data, p.ctypes.data) != 0  # noqa: E731
+    for j in np.unique(idx[idx >= 0]).tolist():
+        if not record_ok(int(size), hdr[j], slot_pos[j]):
+            raise ValueError('record %d cannot be loaded into an env of size %d: hdr %s, slot_pos %s (include/craftingworld.h: cw_load_records states the rule)'
+                             % (j, int(size), hdr[j].tolist(), slot_pos[j].tolist()))
+    return hdr, slot_pos, idx
+
+
 EXPAND_FIELDS = ('reward', 'done', 'changed', 'achieved_mask', 'hdr', 'slot_pos')
 
 
@@ -789,7 +852,8 @@ class CraftingWorldVecEnv:
 
     @property
     def snapshot_skipped(self):
-        """how many envs snapshot_save / snapshot_load have skipped so far for a bad row number (counters[6]; reading it synchronises)"""
+        """how many envs snapshot_save / snapshot_load have skipped so far for a bad row number, and load_records for an index outside its records or a
+        record an env cannot take (counters[6]; reading it synchronises)"""
         return int(self._counters_raw[6].item())
 
     def _snapshot_rows(self, rows, envs, fork):
@@ -815,6 +879,43 @@ class CraftingWorldVecEnv:
         restored state at once.  -> the observation dict (live views, as reset_envs returns)."""
         self._call('cw_snapshot_load', self._snapshot_rows(rows, envs, True), 1 if with_stream else 0)
         return self._observation()
+
+    def load_records(self, hdr, slot_pos, src=None, *, envs=None, status=False):
+        """Put packed records back INTO envs, which go on stepping from them (cw_load_records: one kernel, no host round trip, capturable): env i takes
+        record src[i] of hdr [..., 16] / slot_pos [..., 8] (flattened to R records) -- env.hdr / env.slot_pos cloned earlier, a row of expand()'s, simulate()'s,
+        plan()'s, shoot()'s or reach's result, an archive cell.  src None: R = num_envs and env i takes record i; a negative entry = env i takes no part; any
+        number of envs may name one record; `envs=[3, 5], src=[0, 1]` pairs envs with records.  The records may not be env.hdr / env.slot_pos themselves.
+        A loaded env receives the record's header (but keeps its own task menu) and slots; achieved_mask / desired_mask and, in the pixel modes, its
+        observation frame show the record at once.  Its episode -- the start and goal states and their frames, the RNG stream, the look-ahead records -- reward,
+        done, the episode statistics and counters[0..5] are not touched: the env supplies the episode, a load is not a step.  A terminal record may be loaded:
+        the next step is done again (and resets, on an auto_reset engine).
+        Contiguous tensors on the env's device (hdr uint8, slot_pos int16, src int32 [num_envs]) go over in place -- no copy, no synchronisation -- and are
+        checked on the device: an index >= R or a record an env cannot take (include/craftingworld.h states the rule) is skipped, the env left exactly as it
+        is and counted (snapshot_skipped).  Anything else is validated on the host through the same rule and packed (load_records_args: ValueError names the
+        first bad record, IndexError an index outside the records).
+        -> the observation dict (live views, as snapshot_load returns); with status=True (that, a uint8 tensor [num_envs]): 0 no part, 1 loaded, 2 index
+        out of range, 3 record refused."""
+        if hdr is None or slot_pos is None:
+            raise ValueError('load_records needs hdr and slot_pos')
+        h_dev, p_dev = self._in_place(hdr, (torch.uint8,)), self._in_place(slot_pos, (torch.int16,))
+        if h_dev and p_dev:
+            r = _expand_m(1, _shape_dtype(hdr), _shape_dtype(slot_pos), None)
+            if envs is None and (src is None or self._in_place(src, (torch.int32,), (self.num_envs,))):
+                if src is None and r != self.num_envs:
+                    raise ValueError('the records must hold one entry per env (%d), got %d' % (self.num_envs, r))
+            else:
+                src = torch.as_tensor(load_records_src(self.num_envs, r, as_numpy(src), as_numpy(envs))).to(self.device)
+        else:
+            h, p, idx = load_records_args(self.num_envs, self.size, as_numpy(hdr), as_numpy(slot_pos), as_numpy(src), as_numpy(envs))
+            r = len(h)
+            hdr, slot_pos, src = (torch.as_tensor(a).to(self.device) for a in (h, p.view(np.int16), idx))
+        st = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device) if status else None
+        if r:
+            self._call('cw_load_records', src, hdr, slot_pos, r, st)
+        elif status:
+            st.zero_()
+        obs = self._observation()
+        return (obs, st.cpu() if self.host_outputs else st) if status else obs
 
     # ------------------------------------------------------------------ looking one step ahead
     @property

@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -126,8 +126,8 @@ typedef struct cw_buffer_table {
     uint64_t *counters;      /* [4]  {env-steps, episodes finished, successes (reward==max_steps), invalid actions}; the allocation holds
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
-                              *      found no record waiting (performance diagnostics), [6] counts the envs a cw_snapshot_save / cw_snapshot_load skipped
-                              *      for a bad row number, [7] counts the states skipped by cw_expand, cw_simulate, cw_plan or cw_shoot for an env index at or above num_envs.
+                              *      found no record waiting (performance diagnostics), [6] counts the envs a snapshot or record load skipped
+                              *      (cw_snapshot_save / cw_snapshot_load: a bad row number; cw_load_records: an index out of range or a refused record), [7] counts the states skipped by cw_expand, cw_simulate, cw_plan or cw_shoot for an env index at or above num_envs.
                               *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
@@ -538,6 +538,43 @@ int cw_reach_reserve(cw_engine *e, int64_t max_rows, int32_t max_depth);
 size_t cw_reach_bytes(const cw_engine *e);
 int cw_reach(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, int32_t max_depth,
              const cw_reach_out *out, cw_stream_t stream);
+
+/* --- packed records INTO envs: the other direction of the record family.  cw_expand, cw_simulate, cw_plan, cw_shoot, cw_seen_insert, cw_reach and
+ * cw_render_records read records and write records; this call puts one back into an env, which then goes on stepping from it: an archive of 32-byte cells
+ * ("return, then explore"), committing the chosen child of a tree search -- the terminal successor cw_expand exposes included --, starting episodes k steps
+ * from the goal out of cw_reach's states, restarting from demonstration states.
+ * hdr [R][16] and slot_pos [R][8], R = n_records: taken exactly as cw_expand takes records (device memory, 16-byte aligned, only read -- and not written by
+ *   anyone while the call runs).  They must NOT overlap the engine's own hdr / slot_pos buffers (CW_ERR_INVALID): env i would be written while env j reads
+ *   it; a caller who wants that clones them first.
+ * src: DEVICE int32[num_envs], only read: env i takes record src[i].  A negative entry: env i takes no part.  An entry >= n_records is SKIPPED.  No entry
+ *   becomes an address without that check (cw_host.h: cwh_load_record_index_ok).  Any number of envs may name the same record.  src == NULL: n_records must
+ *   equal num_envs, and env i takes record i.
+ * THE RULE (cw_host.h: cwh_record_ok, written once for the kernel and the host).  Unlike the pure calls, which only compare a record's cells, a loaded
+ *   record becomes engine state: the dirty-cell painter turns the agent's cell into an address, the colour tables are indexed by code.  A record is loaded
+ *   iff agent row < S and agent col < S; hold <= 3; every slot code <= 8; every slot is gone (0xFFFF) with code 0, or held (0xFFFE) with code == hold and
+ *   hold != 0, or on the grid (position < S*S) with code != 0 -- any other position value or pairing fails --; exactly one slot is held if hold != 0 and
+ *   none otherwise; the on-grid positions are pairwise different (one object per cell: what cw_export_grid can show).  Everything else in hdr is free: the
+ *   masks, step_num, the flag word, the menu byte.  Every record cw_step, cw_expand, cw_simulate, cw_plan, cw_shoot or cw_reach produced from a state of the
+ *   engine passes.  A REFUSED record is skipped like an index out of range.
+ * status (or NULL): DEVICE uint8[num_envs], written once for EVERY env: 0 no part, 1 loaded, 2 index out of range, 3 record refused.  It must not overlap
+ *   the records or src.
+ * A LOADED env receives the record's hdr except byte 3 (it keeps its own menu id) and the record's slot_pos; cw_buffer_table.achieved / .desired take the
+ *   record's masks, as after cw_snapshot_load; in the pixel modes its obs frame is repainted at once, held item included.
+ *   NOT written: the episode's start and goal states and their two frames (init_obs, desired_goal), ep_no, the RNG stream, the look-ahead ring, the pool,
+ *   reward, done, episode_length, episode_return, terminal_obs, counters[0..5] and counters[7].  A load is not a step and not a finished episode.
+ * An env with status 2 or 3 is left exactly as it is and counted once in counters[6].
+ * A RECORD DOES NOT HOLD ITS EPISODE: the env supplies the start positions (the Move tasks compare with them) and the goal state.  Loading a record that grew
+ *   out of another episode is the caller's affair; it is legal after a with_stream == 0 fork (cw_snapshot_load), which gives envs one episode.  The record's
+ *   desired mask is taken as it is: if it differs from the episode's, the goal state and frame stay the episode's -- cw_imagine_masked(commit) draws a
+ *   matching goal.  A TERMINAL record may be loaded (step_num >= max_steps, or achieved == desired): the next step is then what the reference does with a
+ *   finished env (ray.py:367) -- done again, and on auto_reset engines reset.
+ * Enqueues ONE kernel (cw_load_records_kernel, dealt out like the snapshot kernels) on `stream` -- no host synchronisation, no allocation -- and can be
+ *   captured into a HIP graph with cw_expand / cw_plan / cw_step.  Every obs_mode, with and without auto_reset, host_outputs engines included (the resident
+ *   stepper is parked first; host_onehot is rewritten by the next cw_step_resident).  n_records == 0: CW_OK, nothing enqueued.  CW_ERR_STATE before the first
+ *   cw_reset / cw_checkpoint_load.  CW_ERR_INVALID: a null engine, hdr or slot_pos, n_records < 0 or above 2^27, src == NULL with n_records != num_envs, a
+ *   misaligned hdr / slot_pos (16 bytes) or src (4 bytes), the overlaps above.  (65 536 envs at 21x21: 20 us state-only, 0.33 ms with the dirty-cell frames repainted; 13 us for 219 selected envs:
+ *   tools/measure_load_records.py, profiles/r13_load_records.txt.) */
+int cw_load_records(cw_engine *e, const int32_t *src, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_records, uint8_t *status, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
