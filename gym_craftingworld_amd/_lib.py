@@ -75,6 +75,10 @@ class cw_shoot_out(C.Structure):
                 ('achieved', C.c_void_p), ('hdr', C.c_void_p), ('slot_pos', C.c_void_p), ('plan', C.c_void_p), ('ret', C.c_void_p)]
 
 
+class cw_refit_out(C.Structure):
+    _fields_ = [('elites', C.c_void_p), ('weights', C.c_void_p), ('elite_min', C.c_void_p)]
+
+
 class cw_seen_out(C.Structure):
     _fields_ = [('fresh', C.c_void_p), ('first', C.c_void_p)]
 
@@ -118,6 +122,8 @@ ABI = {
     'cw_plan': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_plan_out), _VP]),
     'cw_shoot': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, C.POINTER(cw_shoot_out), _VP]),
     'cw_shoot_actions': (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    'cw_shoot_refit': (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, C.c_uint32, C.c_uint32,
+                                C.POINTER(cw_refit_out), _VP]),
     'cw_seen_reserve': (C.c_int, [_VP, C.c_int64, C.c_int32]),
     'cw_seen_clear': (C.c_int, [_VP, _VP]),
     'cw_seen_insert': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_seen_out), _VP]),
@@ -177,6 +183,9 @@ CWH_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_PLAN_MAX_DEPTH, CWH_PLAN_MAX_LEAVES = 8, 1 << 32
 CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
 CWH_SHOOT_MAX_SAMPLES, CWH_SHOOT_MAX_WORK = 65536, 1 << 32
+(CWH_REFIT_OK, CWH_REFIT_NULL, CWH_REFIT_N_STATES, CWH_REFIT_N_STEPS, CWH_REFIT_N_SAMPLES, CWH_REFIT_N_ELITES, CWH_REFIT_WORK, CWH_REFIT_SMOOTH, CWH_REFIT_GAIN,
+ CWH_REFIT_ALIGN, CWH_REFIT_OVERLAP) = range(11)
+CWH_REFIT_BLOCKS_PER_CU = 8
 CWH_SEEN_OK, CWH_SEEN_NO_RECORDS, CWH_SEEN_NO_FIELD, CWH_SEEN_N_STATES, CWH_SEEN_ALIGN, CWH_SEEN_OVERLAP = range(6)
 CWH_SEEN_KEY_WORDS, CWH_SEEN_MAX_CAPACITY, CWH_SEEN_PROBES = 9, 1 << 28, 128
 CWH_SEEN_ROW_BITS, CWH_SEEN_MAX_EPOCH = 28, (1 << 36) - 2
@@ -216,6 +225,10 @@ HOST_HELPERS = {
     'cwh_shoot_draw_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     'cwh_shoot_action_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     'cwh_shoot_lanes_of': (C.c_int, [C.c_int32, C.c_int32]),
+    'cwh_refit_weight_of': (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    'cwh_refit_grid_of': (C.c_int64, [C.c_int64, C.c_int32]),
+    'cwh_refit_args': (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                 C.c_uint64]),
     'cwh_seen_key_of': (None, [C.c_int32, _VP, _VP, _VP]),
     'cwh_seen_hash_of': (C.c_uint64, [_VP]),
     'cwh_seen_slots_of': (C.c_int64, [C.c_int64]),

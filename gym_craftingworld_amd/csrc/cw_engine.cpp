@@ -45,6 +45,9 @@ hipError_t cwk_launch_shoot(const CwParams *P, const int32_t *env_of, const uint
                             unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights, const CwShootOut *O, hipStream_t st);
 hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsigned long long seed, const unsigned long long *seed_dev,
                                     const uint16_t *weights, const int32_t *samples, uint8_t *out, hipStream_t st);
+hipError_t cwk_launch_refit(const CwParams *P, const CwTuning *T, const int32_t *env_of, int n_states, int n_steps, int n_samples, int n_elites,
+                            unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights_in, const int32_t *ret, uint32_t smooth,
+                            uint32_t gain, int32_t *elites, uint16_t *weights, int32_t *elite_min, hipStream_t st);
 hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const CwSeen *S, const int32_t *group, const uint4 *hdr, const uint4 *pos, int n_states,
                                   uint8_t *fresh, int32_t *first, hipStream_t st);
 hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st);
@@ -231,7 +234,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_shoot_refit, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -1082,6 +1085,40 @@ int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t s
     if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_shoot_actions(n_states, n_steps, n_rows, (unsigned long long)seed, (const unsigned long long *)seed_dev, weights, samples, out,
                                      (hipStream_t)stream));
+    return in.done();
+}
+
+// ... and the refit, the other half of a CEM iteration: checks (cwh_refit_args), then the selection kernel and -- when weights are asked for -- the count
+// kernel.  The engine contributes its stream bookkeeping and the has_reset rule; the kernels read num_envs for the env_of test and nothing else of it.
+int cw_shoot_refit(cw_engine *e, const int32_t *env_of, int32_t n_states, int32_t n_steps, int32_t n_samples, int32_t n_elites, uint64_t seed,
+                   const uint64_t *seed_dev, const uint16_t *weights_in, const int32_t *ret, uint32_t smooth, uint32_t gain, const cw_refit_out *out,
+                   cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_shoot_refit: null %s", !e ? "engine" : "out");
+    const auto at = [](const void *p) { return (uint64_t)(uintptr_t)p; };
+    switch (cwh_refit_args(at(env_of), n_states, n_steps, n_samples, n_elites, at(weights_in), at(ret), smooth, gain, at(out->elites), at(out->weights),
+                           at(out->elite_min))) {
+    case CWH_REFIT_OK: break;
+    case CWH_REFIT_NULL: return fail(CW_ERR_INVALID, "cw_shoot_refit: null %s", !ret ? "ret" : "out->elites");
+    case CWH_REFIT_N_STATES: return fail(CW_ERR_INVALID, "cw_shoot_refit: n_states = %d must be 0 .. %d", n_states, CWH_MAX_STATES);
+    case CWH_REFIT_N_STEPS: return fail(CW_ERR_INVALID, "cw_shoot_refit: n_steps = %d must be 1 .. %d", n_steps, CWH_SIM_MAX_STEPS);
+    case CWH_REFIT_N_SAMPLES: return fail(CW_ERR_INVALID, "cw_shoot_refit: n_samples = %d must be 1 .. %d", n_samples, CWH_SHOOT_MAX_SAMPLES);
+    case CWH_REFIT_N_ELITES: return fail(CW_ERR_INVALID, "cw_shoot_refit: n_elites = %d must be 1 .. n_samples = %d", n_elites, n_samples);
+    case CWH_REFIT_WORK:
+        return fail(CW_ERR_INVALID, "cw_shoot_refit: n_states = %d times n_samples = %d times n_steps = %d is above 2^32 steps in one call", n_states, n_samples,
+                    n_steps);
+    case CWH_REFIT_SMOOTH: return fail(CW_ERR_INVALID, "cw_shoot_refit: smooth = %u must be 0 .. 65535", smooth);
+    case CWH_REFIT_GAIN: return fail(CW_ERR_INVALID, "cw_shoot_refit: gain = %u must be 1 .. 65535", gain);
+    case CWH_REFIT_ALIGN: return fail(CW_ERR_INVALID, "cw_shoot_refit: env_of, ret, out->elites and out->elite_min must be 4-byte, the weights 2-byte aligned");
+    default:
+        return fail(CW_ERR_INVALID, "cw_shoot_refit: an output overlaps ret, env_of, another output or weights_in (out->weights == weights_in, in place, is legal)");
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_shoot_refit called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_refit(&e->P, &e->tune, env_of, n_states, n_steps, n_samples, n_elites, (unsigned long long)seed, (const unsigned long long *)seed_dev,
+                             weights_in, ret, smooth, gain, out->elites, out->weights, out->elite_min, (hipStream_t)stream));
     return in.done();
 }
 

@@ -241,6 +241,37 @@ int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_byte
     return a < b_end && b < a_end;
 }
 
+// ------------------------------------------------------------------------------ cw_shoot_refit: the weight, the grid, the argument rules
+uint32_t cwh_refit_weight_of(uint32_t smooth, uint32_t gain, uint32_t count) { return cwh_refit_weight(smooth, gain, count); }
+int64_t cwh_refit_grid_of(int64_t items, int32_t n_cu) { return cwh_refit_grid(items, n_cu); }
+
+int cwh_refit_args(uint64_t env_of, int32_t n_states, int32_t n_steps, int32_t n_samples, int32_t n_elites, uint64_t weights_in, uint64_t ret, uint32_t smooth,
+                   uint32_t gain, uint64_t elites, uint64_t weights, uint64_t elite_min)
+{
+    if (!ret || !elites) return CWH_REFIT_NULL;
+    if (n_states < 0 || n_states > CWH_MAX_STATES) return CWH_REFIT_N_STATES;
+    if (n_steps < 1 || n_steps > CWH_SIM_MAX_STEPS) return CWH_REFIT_N_STEPS;
+    if (n_samples < 1 || n_samples > CWH_SHOOT_MAX_SAMPLES) return CWH_REFIT_N_SAMPLES;
+    if (n_elites < 1 || n_elites > n_samples) return CWH_REFIT_N_ELITES;
+    if ((uint64_t)n_states * (uint64_t)n_samples * (uint64_t)n_steps > CWH_SHOOT_MAX_WORK) return CWH_REFIT_WORK;       // (<= 2^27 * 2^16 * 2^15)
+    if (smooth > 65535u) return CWH_REFIT_SMOOTH;
+    if (gain < 1u || gain > 65535u) return CWH_REFIT_GAIN;
+    if ((env_of & 3u) || (ret & 3u) || (elites & 3u) || (elite_min & 3u) || (weights_in & 1u) || (weights & 1u)) return CWH_REFIT_ALIGN;
+    const uint64_t m = (uint64_t)n_states, w_bytes = 12 * (uint64_t)n_steps * m;
+    const uint64_t outs[3][2] = {{elites, 4 * (uint64_t)n_elites * m}, {weights, w_bytes}, {elite_min, 4 * m}};
+    const uint64_t ins[3][2] = {{ret, 4 * (uint64_t)n_samples * m}, {env_of, 4 * m}, {weights_in, w_bytes}};
+    for (int o = 0; o < 3; o++) {
+        if (!outs[o][0]) continue;
+        for (int i = 0; i < 3; i++) {
+            if (!ins[i][0] || (o == 1 && i == 2 && weights == weights_in)) continue;                                      // (in place: the one overlap allowed)
+            if (cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_REFIT_OVERLAP;
+        }
+        for (int q = o + 1; q < 3; q++)
+            if (outs[q][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], outs[q][0], outs[q][1])) return CWH_REFIT_OVERLAP;
+    }
+    return CWH_REFIT_OK;
+}
+
 // ------------------------------------------------------------------------------ the visited set's key, size and argument rules
 void cwh_seen_key_of(int32_t group, const uint8_t *hdr, const uint16_t *slot_pos, uint32_t *key)
 {

@@ -212,6 +212,34 @@ int cwh_shoot_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slo
 // 1 <= n_steps <= CWH_SIM_MAX_STEPS (CWH_REC_N_STEPS), n_rows * n_states * n_steps <= CWH_SHOOT_MAX_WORK (CWH_REC_SHOOT_WORK)
 int cwh_shoot_actions_args(int32_t n_states, int32_t n_steps, int32_t n_rows);
 
+// ---- cw_shoot_refit: the other half of a CEM iteration (include/craftingworld.h states it).  THE WEIGHT an action gets that `count` of the elites drew:
+// min(65 535, smooth + gain * count) in uint32 arithmetic -- smooth and gain <= 65 535 and count <= 65 536 (CWH_SHOOT_MAX_SAMPLES), so the sum is at most
+// 2^32 - 1 and never wraps.  Shared by the kernel and the host.
+static inline CWH_HOST_DEVICE uint32_t cwh_refit_weight(uint32_t smooth, uint32_t gain, uint32_t count)
+{
+    const uint32_t w = smooth + gain * count;
+    return w < 65535u ? w : 65535u;
+}
+uint32_t cwh_refit_weight_of(uint32_t smooth, uint32_t gain, uint32_t count);       // (the same, exported for the CPU tests)
+// workgroups of 256 lanes of the two refit kernels, grid-stride over `items` lanes: ceil(items / 256), 1 at least, n_cu * CWH_REFIT_BLOCKS_PER_CU at most
+#define CWH_REFIT_BLOCKS_PER_CU 8
+static inline int64_t cwh_refit_grid(int64_t items, int32_t n_cu)
+{
+    const int64_t want = (items + 255) / 256, most = (int64_t)n_cu * CWH_REFIT_BLOCKS_PER_CU;
+    return want < most ? (want < 1 ? 1 : want) : most;
+}
+int64_t cwh_refit_grid_of(int64_t items, int32_t n_cu);                             // (the same, exported for the CPU tests)
+// the argument rules of cw_shoot_refit, in the order they are tested; addresses as integers (0: null), so the rules need no HIP: ret and elites given
+// (CWH_REFIT_NULL), 0 <= n_states <= CWH_MAX_STATES (CWH_REFIT_N_STATES), 1 <= n_steps <= CWH_SIM_MAX_STEPS (CWH_REFIT_N_STEPS), 1 <= n_samples <=
+// CWH_SHOOT_MAX_SAMPLES (CWH_REFIT_N_SAMPLES), 1 <= n_elites <= n_samples (CWH_REFIT_N_ELITES), n_states * n_samples * n_steps <= CWH_SHOOT_MAX_WORK
+// (CWH_REFIT_WORK: cw_shoot's cap; the refit draws n_states * n_elites * n_steps times at most), smooth <= 65 535 (CWH_REFIT_SMOOTH), 1 <= gain <= 65 535
+// (CWH_REFIT_GAIN), env_of, ret, elites, elite_min 4-byte and weights_in, weights 2-byte aligned (CWH_REFIT_ALIGN), no output sharing a byte with ret,
+// env_of, another output or weights_in -- except weights == weights_in, the SAME address: the refit in place (CWH_REFIT_OVERLAP).
+enum { CWH_REFIT_OK = 0, CWH_REFIT_NULL = 1, CWH_REFIT_N_STATES = 2, CWH_REFIT_N_STEPS = 3, CWH_REFIT_N_SAMPLES = 4, CWH_REFIT_N_ELITES = 5, CWH_REFIT_WORK = 6,
+       CWH_REFIT_SMOOTH = 7, CWH_REFIT_GAIN = 8, CWH_REFIT_ALIGN = 9, CWH_REFIT_OVERLAP = 10 };
+int cwh_refit_args(uint64_t env_of, int32_t n_states, int32_t n_steps, int32_t n_samples, int32_t n_elites, uint64_t weights_in, uint64_t ret, uint32_t smooth,
+                   uint32_t gain, uint64_t elites, uint64_t weights, uint64_t elite_min);
+
 // ---- cw_seen_*: the visited set of packed records.  THE KEY of a record (include/craftingworld.h states it): everything step_env reads of a state but the two
 // step counters, and the group that says which records may be merged at all -- group, hdr bytes 0-2, 4-7, bit 1 of byte 10, 12-15 and the 16 bytes of slot_pos:
 // 36 bytes as nine dwords.  hdr and slot_pos as the four little-endian dwords of a record each (the uint4 the kernels load).  Shared by the kernels and the host.

@@ -24,6 +24,8 @@
 //                     state) pair, a depth-first search with its stack in registers and a wave-uniform action at every level; writes nothing of the engine.
 //   cw_shoot_kernel   random shooting: the best of K sampled T-step plans of M such states, the actions drawn where they are used by a counter-based
 //                     integer mix (no action tensor), G lanes per state and a shuffle reduction; cw_shoot_actions_kernel decodes the draws.  Pure.
+//   cw_refit_select_kernel / cw_refit_count_kernel  the other half of a CEM iteration: the exact top E of every column of ret [K][M] (a binary search on the
+//                     value, then a compaction in sample order, cw_shoot_kernel's lanes), and the next weights from the elites' regenerated draws.  Pure.
 //   cw_seen_claim_kernel / cw_seen_resolve_kernel  the visited set of such records: which of M rows brings a key the set has not held, and which is the first
 //                     of its key in the call -- an open-addressed table, one lane per row, atomics on the slot words and no wait; cw_seen_clear_kernel empties it.
 //   cw_reach_*_kernel  breadth-first search over such records without a host round trip: expansion, the set's two kernels, a stable compaction (count, scan,
@@ -1005,6 +1007,114 @@ __global__ __launch_bounds__(256) void cw_shoot_actions_kernel(int n_states, int
             else a = cwh_shoot_mulhi(x, 6u);
             out[(size_t)t * columns + c] = (uint8_t)a;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------ refit: the other half of a CEM iteration
+// cw_shoot_refit: from ret [K][M] to the next weights [T][6][M], in TWO kernels that read nothing of the engine.  No atomics, no LDS, and no lane waits for
+// another beyond the shuffles and ballots of its own wave.  Does state j take part?  refit_takes_part, the one place either kernel asks: env_of null, or an
+// entry behind cwh_expand_env_ok -- the states whose ret column cw_shoot wrote.  The entry is compared and never becomes an index; nothing is counted.
+//   cw_refit_select_kernel  the E elites of every column, EXACT: the first E in the order (return descending, sample ascending).  cw_shoot_kernel's lanes: a
+//                           state has G = 1 << lg lanes (cwh_shoot_lanes), lane (j, g) at global lane j * G + g, lane g visiting samples g, g + G, ...; G = 1
+//                           at large M, where the lanes of a wave are 64 consecutive states and every load of a row of ret is one contiguous run.  Every loop
+//                           over the samples is uniform within the G lanes (a lane past K carries neutral values), so the shuffles and ballots of a group
+//                           always find all of its lanes.  Pass 1: the column's min and max.  Then a binary search on the VALUE for v, the E-th largest: the
+//                           smallest v with fewer than E samples above it -- each pass counts ret > mid, the midpoint in 64 bits; at most 32 passes for
+//                           arbitrary int32, at most 17 for cw_shoot's returns.  Last pass: the elites are every sample above v and the first E - (samples above
+//                           v) holders of v; the samples are visited in rounds, within a round in lane order, so a running offset plus the prefix over the
+//                           group's bits of a ballot is the ascending sample order.  Grid-stride over the n_states << lg lanes, a whole group at a time.
+//   cw_refit_count_kernel   one lane per (t, j), j fastest, grid-stride: the six weights_in of (t, j) are loaded FIRST (the weighted instance; the uniform one
+//                           carries no weight loads), then every elite's draw of step t is regenerated -- one prefix and one step mix -- and counted in six
+//                           registers by compares, then the six new weights (cwh_refit_weight) are stored.  The lane that writes the weights of a (t, j) is
+//                           the only one that reads them, and it reads before it writes: weights == weights_in is legal, so neither pointer is __restrict__.
+__device__ __forceinline__ bool refit_takes_part(const int32_t *__restrict__ env_of, size_t j, int n_envs)
+{
+    return !env_of || cwh_expand_env_ok(env_of[j], n_envs);
+}
+
+__global__ __launch_bounds__(256) void cw_refit_select_kernel(const int32_t *__restrict__ env_of, int n_envs, int n_states, int K, int E, int lg,
+                                                              const int32_t *__restrict__ ret, int32_t *__restrict__ elites, int32_t *__restrict__ elite_min)
+{
+    const int G = 1 << lg;
+    const size_t M = (size_t)n_states, lanes = M << lg;                   // (n_states << lg < 2^28: cwh_shoot_lanes)
+    const int first = (int)(threadIdx.x & (CW_WAVE - 1)) & ~(G - 1);      // the wave lane of the group's lane 0
+    const unsigned long long group_bits = G == CW_WAVE ? ~0ull : (1ull << G) - 1ull;
+    for (size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x; lane < lanes; lane += (size_t)gridDim.x * blockDim.x) {      // (256 % G == 0: whole groups)
+        const size_t j = lane >> lg;
+        const int g = (int)(lane & (size_t)(G - 1));
+        if (!refit_takes_part(env_of, j, n_envs)) continue;               // (all G lanes of the state alike)
+        const int32_t *const col = ret + j;
+        int32_t mn = INT32_MAX, mx = INT32_MIN;
+        for (int k = g; k < K; k += G) {
+            const int32_t r = col[(size_t)k * M];
+            mn = r < mn ? r : mn;
+            mx = r > mx ? r : mx;
+        }
+        for (int off = 1; off < G; off <<= 1) {
+            const int32_t o_mn = __shfl_xor(mn, off), o_mx = __shfl_xor(mx, off);
+            mn = o_mn < mn ? o_mn : mn;
+            mx = o_mx > mx ? o_mx : mx;
+        }
+        auto above = [&](int32_t v) -> int {                              // how many samples of the column lie above v (every lane of the group gets the sum)
+            int n = 0;
+            for (int k = g; k < K; k += G) n += col[(size_t)k * M] > v ? 1 : 0;
+            for (int off = 1; off < G; off <<= 1) n += __shfl_xor(n, off);
+            return n;
+        };
+        long long lo = mn, hi = mx;                                       // v lies in [lo, hi]: nothing is above the max, and E >= 1
+        while (lo < hi) {                                                 // (the same in every lane of the group)
+            const long long mid = (lo + hi) >> 1;                         // floor, in 64 bits
+            if (above((int32_t)mid) < E) hi = mid; else lo = mid + 1;
+        }
+        const int32_t v = (int32_t)lo;
+        const int ties = E - above(v);                                    // holders of v to take: 1 at least
+        int taken = 0, written = 0;                                       // holders of v seen, elites written: in the rounds before this one
+        for (int k0 = 0; k0 < K && written < E; k0 += G) {
+            const int k = k0 + g;
+            const int32_t r = k < K ? col[(size_t)k * M] : INT32_MIN;
+            const bool holds = k < K && r == v;
+            const unsigned long long m_holds = (CW_BALLOT(holds) >> first) & group_bits, before = (1ull << g) - 1ull;
+            const bool elite = (k < K && r > v) || (holds && taken + __popcll(m_holds & before) < ties);
+            const unsigned long long m_elite = (CW_BALLOT(elite) >> first) & group_bits;
+            if (elite) elites[(size_t)(written + __popcll(m_elite & before)) * M + j] = k;
+            taken += __popcll(m_holds);
+            written += __popcll(m_elite);
+        }
+        if (elite_min && g == 0) elite_min[j] = v;
+    }
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void cw_refit_count_kernel(const int32_t *__restrict__ env_of, int n_envs, int n_states, int T, int E, unsigned long long seed,
+                                                             const unsigned long long *__restrict__ seed_dev, const uint16_t *weights_in,
+                                                             const int32_t *__restrict__ elites, uint32_t smooth, uint32_t gain, uint16_t *weights)
+{
+    const size_t M = (size_t)n_states, items = (size_t)T * M;
+    const unsigned long long s = seed + (seed_dev ? *seed_dev : 0ull);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t t = i / M, j = i - t * M;
+        if (!refit_takes_part(env_of, j, n_envs)) continue;
+        const size_t at = t * 6 * M + j;
+        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0;
+        if constexpr (WEIGHTED) {                                         // read before anything of (t, j) is written: the refit in place
+            w0 = weights_in[at]; w1 = weights_in[at + M]; w2 = weights_in[at + 2 * M]; w3 = weights_in[at + 3 * M]; w4 = weights_in[at + 4 * M];
+            w5 = weights_in[at + 5 * M];
+        }
+        uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
+        for (int e = 0; e < E; e++) {
+            const uint32_t k = (uint32_t)elites[(size_t)e * M + j];       // (a number that is mixed, never an address)
+            const uint32_t r = cwh_shoot_step(cwh_shoot_prefix(s, (uint32_t)j, k), (uint32_t)t);
+            uint32_t a;
+            if constexpr (WEIGHTED) a = cwh_shoot_action_w(r, w0, w1, w2, w3, w4, w5);
+            else a = cwh_shoot_mulhi(r, 6u);
+            c0 += a == 0u; c1 += a == 1u; c2 += a == 2u; c3 += a == 3u; c4 += a == 4u; c5 += a == 5u;
+        }
+        weights[at] = (uint16_t)cwh_refit_weight(smooth, gain, c0);
+        weights[at + M] = (uint16_t)cwh_refit_weight(smooth, gain, c1);
+        weights[at + 2 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c2);
+        weights[at + 3 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c3);
+        weights[at + 4 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c4);
+        weights[at + 5 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c5);
     }
 }
 
@@ -3296,6 +3406,28 @@ hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsig
         hipLaunchKernelGGL(cw_shoot_actions_kernel<true>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
     else
         hipLaunchKernelGGL(cw_shoot_actions_kernel<false>, grid, block, 0, st, n_states, n_steps, n_rows, seed, seed_dev, weights, samples, out);
+    return hipGetLastError();
+}
+
+// cw_shoot_refit: the selection over n_states * G lanes (G = cwh_shoot_lanes), then -- only when weights are asked for -- the counts over n_steps * n_states
+// lanes, its weighted draw an instance of its own; both grid-stride, cwh_refit_grid workgroups
+hipError_t cwk_launch_refit(const CwParams *P, const CwTuning *T, const int32_t *env_of, int n_states, int n_steps, int n_samples, int n_elites,
+                            unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights_in, const int32_t *ret, uint32_t smooth,
+                            uint32_t gain, int32_t *elites, uint16_t *weights, int32_t *elite_min, hipStream_t st)
+{
+    int lg = 0;
+    while ((1 << lg) < cwh_shoot_lanes(n_states, n_samples)) lg++;
+    const dim3 block(256), g_select((unsigned)cwh_refit_grid((int64_t)n_states << lg, T->n_cu));
+    hipLaunchKernelGGL(cw_refit_select_kernel, g_select, block, 0, st, env_of, P->n_envs, n_states, n_samples, n_elites, lg, ret, elites, elite_min);
+    hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess || !weights) return rc;
+    const dim3 g_count((unsigned)cwh_refit_grid((int64_t)n_steps * (int64_t)n_states, T->n_cu));
+    if (weights_in)
+        hipLaunchKernelGGL(cw_refit_count_kernel<true>, g_count, block, 0, st, env_of, P->n_envs, n_states, n_steps, n_elites, seed, seed_dev, weights_in, elites,
+                           smooth, gain, weights);
+    else
+        hipLaunchKernelGGL(cw_refit_count_kernel<false>, g_count, block, 0, st, env_of, P->n_envs, n_states, n_steps, n_elites, seed, seed_dev, weights_in, elites,
+                           smooth, gain, weights);
     return hipGetLastError();
 }
 

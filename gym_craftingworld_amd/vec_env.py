@@ -415,6 +415,33 @@ def shoot_weights(weights, horizon, m):
     return np.ascontiguousarray(w, dtype=np.uint16)
 
 
+REFIT_FIELDS = ('elites', 'weights', 'elite_min')
+
+
+def refit_args(ret, elites, horizon, smooth=1, gain=1, env_of=None, num_envs=None):
+    """What cw_shoot_refit is handed, validated on the host: -> (T, K, E, M).  ret: the (shape, numpy dtype) of the returns -- int32 [K, M] with K 1 .. 65 536
+    and M <= 2**27; elites: an integer 1 .. K; horizon: an integer 1 .. 32 767 with M * K * horizon <= 2**32 (shoot()'s cap: the refit draws at most that often);
+    smooth: an integer 0 .. 65 535; gain: an integer 1 .. 65 535; env_of: None or a flat integer list of M env ids (a negative entry = the state takes no
+    part; IndexError for an entry >= num_envs, where num_envs is given).  ValueError for everything else."""
+    shape, dtype = ret
+    if len(shape) != 2 or np.dtype(dtype) != np.int32:
+        raise ValueError('ret must be int32 [K, M] (shoot()\'s \'ret\' field), got %s %s' % (np.dtype(dtype), tuple(shape)))
+    K, m = int(shape[0]), int(shape[1])
+    if m > 2 ** 27:
+        raise ValueError('%d states: at most 2**27 in one call' % m)
+    T, K = _shoot_tk(horizon, K, m)
+    E = _shoot_int(elites, 'elites', 1, K)
+    _shoot_int(smooth, 'smooth', 0, 65535)
+    _shoot_int(gain, 'gain', 1, 65535)
+    if env_of is not None:
+        e = np.asarray(env_of)
+        if e.ndim != 1 or e.shape[0] != m or e.size and not np.issubdtype(e.dtype, np.integer):
+            raise ValueError('env_of must be a flat integer list with one entry per state (%d), got %s %s' % (m, e.dtype, e.shape))
+        if num_envs is not None and e.size and int(e.max()) >= int(num_envs):
+            raise IndexError('env index %d outside a batch of %d envs' % (int(e.max()), int(num_envs)))
+    return T, K, E, m
+
+
 def _render_records_m(frame_shape, lead, mask, out):
     """render_records_args on the records' leading shape and the (shape, numpy dtype) of mask and out (None: not given)"""
     lead, frame_shape = tuple(int(x) for x in lead), tuple(int(x) for x in frame_shape)
@@ -1048,7 +1075,9 @@ class CraftingWorldVecEnv:
 
     # ------------------------------------------------------------------ shooting plans
     def _shoot_seed(self, seed):
-        """seed as shoot() takes it -> (the scalar, the device word or None)"""
+        """seed as shoot() takes it -> (the scalar, the device word or None); a pair (int, tensor) is both at once -- the kernel adds them: cem()'s form"""
+        if type(seed) is tuple and len(seed) == 2 and type(seed[1]) is torch.Tensor:
+            return shoot_seed(seed[0]), self._shoot_seed(seed[1])[1]
         if type(seed) is torch.Tensor:
             if seed.numel() != 1 or seed.dtype not in (torch.int64, torch.uint64) or seed.device != self.device or not seed.is_contiguous():
                 raise ValueError('a seed tensor must hold one int64 / uint64 element on %s, got %s %s on %s' % (self.device, seed.dtype, tuple(seed.shape), seed.device))
@@ -1070,7 +1099,8 @@ class CraftingWorldVecEnv:
         a counter-based integer function of (seed, state, sample, step), stated in include/craftingworld.h and reproduced by shoot_actions() -- so no
         [T, K, M] action tensor exists; no host round trip, capturable; no env is touched.)  horizon: 1 .. 32 767, samples: 1 .. 65 536, with
         M * samples * horizon <= 2**32.  seed: an int 0 .. 2**64 - 1, or a one-element int64 / uint64 tensor on the env's device, which the KERNEL reads:
-        a captured graph draws new plans on every replay once the caller has changed the word.  The states are plan()'s: without records the envs' current
+        a captured graph draws new plans on every replay once the caller has changed the word (a pair (int, tensor) is both: the kernel adds them -- cem()'s
+        form).  The states are plan()'s: without records the envs' current
         ones (M = num_envs), else hdr [..., 16] / slot_pos [..., 8] / env_of under expand()'s rules (a negative env_of entry takes no part and none of its
         rows is written, an entry >= num_envs handed over on the device is skipped and counted once in expand_skipped).  weights: None (uniform actions)
         or integers 0 .. 65 535 of shape [T, 6, M] -- weights[t, a, j] is the weight of action a at step t of state j, 0 forbids it, six zeros mean
@@ -1128,6 +1158,94 @@ class CraftingWorldVecEnv:
         if R and m:
             self._call('cw_shoot_actions', m, T, seed, seed_dev, weights, samples, R, out)
         return out
+
+    # ------------------------------------------------------------------ refitting plans
+    def shoot_refit(self, ret, elites, horizon, seed=0, *, weights=None, env_of=None, smooth=1, gain=1, fields=None, out=None):
+        """The other half of a CEM iteration: from shoot()'s 'ret' to the next weights (cw_shoot_refit: two kernels, exact integer arithmetic, no host round
+        trip, capturable; no env is touched).  ret: int32 [K, M], a contiguous tensor on the env's device, which goes over in place -- shoot()'s, or any
+        int32 values.  elites: E, 1 .. K.  The ELITES of state j are the first E samples in the order (return descending, sample ascending): ties go to the
+        smaller sample, best_sample's rule, so two runs never differ.  horizon, seed and weights as the shoot() call that produced ret took them (the same
+        seed and weights give the same draws): the actions of the elites are regenerated from the draw, ALL `horizon` of them -- the steps behind a
+        sample's done step included, as 'plan' holds them -- and no [T, E, M] tensor exists.  The new weight of action a at step t of state j is
+        min(65535, smooth + gain * (the number of elites that drew a there)): smooth 0 .. 65 535 is a pseudo-count (0: an action no elite drew becomes
+        forbidden), gain 1 .. 65 535.  env_of: None, or shoot()'s env_of (int32 [M]; an int32 tensor on the env's device goes over in place): a negative
+        entry or one >= num_envs takes no part -- the states whose 'ret' column shoot() did not write -- and nothing of it is written; expand_skipped does
+        not move.
+        -> a dict of device tensors: 'elites' int32 [E, M], the elite samples in ascending order; 'weights' uint16 [T, 6, M], as shoot() takes them;
+        'elite_min' int32 [M], the smallest return among the elites.  fields: a subset of REFIT_FIELDS (default all).  out: a dict returned by an earlier
+        call with the same shapes and fields, written again; out={'weights': w, ...} with w the very tensor passed as weights= is the refit IN PLACE (any
+        other overlap of the two raises)."""
+        names = _field_names(fields, REFIT_FIELDS, REFIT_FIELDS)
+        if type(ret) is not torch.Tensor or ret.device != self.device or not ret.is_contiguous():
+            raise ValueError('ret must be a contiguous int32 tensor [K, M] on %s (shoot()\'s \'ret\' field)' % (self.device,))
+        e_dev = env_of is None or self._in_place(env_of, (torch.int32,))
+        if not e_dev:
+            env_of = as_numpy(env_of)
+            if not env_of.size:
+                env_of = env_of.astype(np.int32)        # (an empty list is an empty list of ints)
+        T, K, E, m = refit_args(_shape_dtype(ret), elites, horizon, smooth, gain, None if e_dev else env_of, self.num_envs)
+        if env_of is not None and e_dev and tuple(env_of.shape) != (m,):
+            raise ValueError('env_of must hold one entry per state (%d), got %s' % (m, tuple(env_of.shape)))
+        if not e_dev:
+            env_of = torch.as_tensor(np.ascontiguousarray(np.maximum(env_of.astype(np.int64), -1), dtype=np.int32)).to(self.device)
+        seed, seed_dev = self._shoot_seed(seed)
+        spec = {'elites': ((E, m), torch.int32), 'weights': ((T, 6, m), torch.uint16), 'elite_min': ((m,), torch.int32)}
+        in_place = weights is not None and out is not None and out.get('weights') is weights
+        out = self._out_dict(out, names, spec)
+        weights = out['weights'] if in_place else self._shoot_weights(weights, T, m)
+        kernel = out if 'elites' in out else dict(out, elites=torch.empty((E, m), dtype=torch.int32, device=self.device))   # (the selection is always written)
+        if m:
+            self._call('cw_shoot_refit', env_of, m, T, K, E, seed, seed_dev, weights, ret, int(smooth), int(gain),
+                       C.byref(_out_struct(L.cw_refit_out, kernel)), keep=kernel)
+        return out
+
+    def _cem_scratch(self, K, E, m):
+        """what a cem() call needs and does not return, per shape and kept by the env (a captured graph goes on using it): the elites, and the returns
+        where the caller did not name 'ret'"""
+        held = self.__dict__.setdefault('_cem_held', {})
+        if (K, E, m) not in held:
+            held[(K, E, m)] = {'elites': torch.empty((E, m), dtype=torch.int32, device=self.device),
+                               'ret': torch.empty((K, m), dtype=torch.int32, device=self.device)}
+        return held[(K, E, m)]
+
+    def cem(self, horizon, samples, elites, iters, seed=0, hdr=None, slot_pos=None, env_of=None, *, weights=None, smooth=1, gain=1, fields=None, out=None):
+        """`iters` iterations of the cross-entropy method on the device: shoot(), then shoot_refit() of its returns into ONE weights buffer, again and
+        again -- a plain loop over the two public calls with NO synchronisation and no host round trip.  Iteration i = 0 .. iters - 1 shoots with the
+        current weights and the effective seed (seed + i) mod 2**64 -- a seed tensor goes over as the device word with the scalar i, so a captured graph
+        draws new plans on every replay once the caller has bumped the word -- and refits with the same seed and weights, in place.  weights=None starts
+        uniform and the first refit fills the buffer; other weights are COPIED into the buffer first: a caller's tensor is never written unless it is
+        handed in through out= (weights=r['weights'], out=r of an earlier result r is the warm start without a copy).  horizon, samples, hdr / slot_pos /
+        env_of and fields as shoot() takes them; elites, smooth and gain as shoot_refit() does.
+        -> shoot()'s dict of the LAST iteration plus 'weights' uint16 [T, 6, M] (after the last refit: the warm start of the next MPC step) and
+        'elite_min' int32 [M] (of the last refit).  THE RESULT IS THE LAST ITERATION'S BEST, NOT THE BEST OVER ALL ITERATIONS: 'best_ret' may lie below
+        what an earlier iteration found.  out: the dict an earlier call with the same shapes and fields returned -- every buffer is used again, the
+        env's own scratch included, and nothing is allocated, so the whole call can be captured into a graph together with the steps."""
+        iters = _shoot_int(iters, 'iters', 1, 2 ** 31 - 1)
+        names = _field_names(fields, SHOOT_FIELDS, tuple(f for f in SHOOT_FIELDS if f not in ('hdr', 'slot_pos', 'ret')))
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        T, K = _shoot_tk(horizon, samples, m)
+        E = _shoot_int(elites, 'elites', 1, K)
+        smooth, gain = _shoot_int(smooth, 'smooth', 0, 65535), _shoot_int(gain, 'gain', 1, 65535)
+        scalar, word = self._shoot_seed(seed)
+        own = ('weights', 'elite_min')
+        if out is not None and set(out) != set(names + own):
+            raise ValueError('out holds %s, asked for %s' % (sorted(out), sorted(names + own)))
+        fit = self._out_dict(None if out is None else {f: out[f] for f in own}, own, {'weights': ((T, 6, m), torch.uint16), 'elite_min': ((m,), torch.int32)})
+        scratch = self._cem_scratch(K, E, m)
+        fit['elites'] = scratch['elites']
+        inner = names if 'ret' in names else names + ('ret',)
+        shot = None if out is None else dict({f: out[f] for f in names}, **({} if 'ret' in names else {'ret': scratch['ret']}))
+        current = None
+        if weights is not None:
+            if weights is not fit['weights']:
+                fit['weights'].copy_(self._shoot_weights(weights, T, m))
+            current = fit['weights']
+        for i in range(iters):
+            s = (scalar + i) % 2 ** 64 if word is None else (i, word)
+            shot = self.shoot(T, K, s, hdr, slot_pos, env_of, weights=current, fields=inner, out=shot)
+            self.shoot_refit(shot['ret'], E, T, s, weights=current, env_of=env_of, smooth=smooth, gain=gain, out=fit)
+            current = fit['weights']
+        return dict({f: shot[f] for f in names}, weights=fit['weights'], elite_min=fit['elite_min'])
 
     def one_hot_states(self, hdr, slot_pos, out=None):
         """obs_one_hot (ray.py:119) of caller-supplied packed records hdr [..., 16] / slot_pos [..., 8] (as expand() takes and returns them):

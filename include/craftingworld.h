@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; then cw_refit_out, cw_shoot_refit; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -445,6 +445,41 @@ int cw_shoot(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const u
  * CW_ERR_INVALID, as for a null engine or out; n_states == 0 or n_rows == 0: CW_OK, nothing enqueued. */
 int cw_shoot_actions(cw_engine *e, int32_t n_states, int32_t n_steps, uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights,
                      const int32_t *samples, int32_t n_rows, uint8_t *out /* [T][n_rows][M] */, cw_stream_t stream);
+/* THE REFIT: the other half of a CEM iteration -- from cw_shoot's ret [K][M] to the next weights [T][6][M], exact, integer and deterministic, with no [T][E][M]
+ * action tensor: the elites' actions are regenerated from THE DRAW.  M = n_states, T = n_steps, K = n_samples, E = n_elites.
+ * ret is DEVICE int32 [K][M], only read: cw_shoot's, or any int32 values at all (INT32_MIN and INT32_MAX order as integers do).
+ * THE ELITES of state j: order its K samples by (ret[k][j] DESCENDING, k ASCENDING) and take the first E -- a tie goes to the smaller sample, best_sample's
+ *   rule.  Equivalently: v = the E-th largest value of the column, counted with multiplicity; the elites are every sample above v and the smallest-indexed samples
+ *   equal to v until E is reached.  elites[0..E-1][j] holds them in ASCENDING sample order; elite_min[j] = v.  A function of the inputs alone, never of scheduling.
+ * THE COUNTS: c[t][a][j] = how many elites k of state j have action(draw(s, j, k, t), weights_in ? the six uint16 weights_in[(t * 6 + a') * M + j], a' = 0..5 : NULL)
+ *   == a, with s = seed + (seed_dev ? *seed_dev : 0) mod 2^64 -- cw_shoot's draw with cw_shoot's seed and weights.  ALL T drawn actions of an elite count, as
+ *   cw_shoot's `plan` holds all T: the steps BEHIND a sample's done step, which cw_shoot never played, are included.  The six counts of a (t, j) sum to E.
+ * THE NEW WEIGHTS: weights[(t * 6 + a) * M + j] = min(65535, smooth + gain * c[t][a][j]) in uint32 arithmetic (no wrap: at most 65535 + 65535 * 65536).  smooth,
+ *   0 .. 65 535, is a pseudo-count: 0 lets an action no elite drew become FORBIDDEN at that step of that state.  gain is 1 .. 65 535.  The six new weights are
+ *   never all zero (E >= 1 and gain >= 1).
+ * IN PLACE: out->weights == weights_in, the same address, is legal -- the six weights of a (t, j) are read by the one lane that writes them, before it writes;
+ *   a CEM loop keeps one weights buffer.  Any other overlap of the two is CW_ERR_INVALID.
+ * STATES THAT TAKE NO PART: env_of is NULL (every state takes part) or DEVICE int32 [M], cw_shoot's; a negative entry or an entry >= num_envs takes no part --
+ *   exactly the states whose ret column cw_shoot did not write -- and NOTHING of such a state is written in any output.  It is not counted in counters[7]:
+ *   cw_shoot counted it already.  No entry becomes an address. */
+typedef struct cw_refit_out {      /* DEVICE pointers; elites is REQUIRED, the others may be NULL */
+    int32_t  *elites;     /* [E][M]     the E elite samples of state j, in ASCENDING sample order; 4-byte aligned */
+    uint16_t *weights;    /* [T][6][M]  the refitted weights, cw_shoot's layout; NULL: selection only              */
+    int32_t  *elite_min;  /* [M]        the smallest return among the elites (the E-th largest of the column)      */
+} cw_refit_out;
+/* PURE: nothing of the engine is read but num_envs (the env_of test) and nothing written; the engine contributes its stream bookkeeping and the has_reset rule.
+ * Enqueues TWO kernels on `stream` (cw_refit_select_kernel: cw_shoot's G lanes per state, the column's min and max, a binary search on the value for v -- at most
+ *   32 passes over the column, 17 for cw_shoot's returns -- and one pass that compacts in sample order by ballots; cw_refit_count_kernel: one lane per (t, j), E
+ *   regenerated draws, six coalesced stores; not enqueued when out->weights is NULL) -- no atomics, no host synchronisation, no allocation -- and can be captured
+ *   into a HIP graph with cw_shoot / cw_step.  Every obs_mode, host_outputs engines included.  n_states == 0: CW_OK, nothing enqueued.  CW_ERR_STATE before the
+ *   first cw_reset / cw_checkpoint_load.  CW_ERR_INVALID, tested in this order: a null engine or out; a null ret or out->elites; n_states < 0 or above 2^27;
+ *   n_steps outside 1 .. 32 767; n_samples outside 1 .. 65 536; n_elites outside 1 .. n_samples; n_states * n_samples * n_steps above 2^32 (cw_shoot's cap: the
+ *   refit does at most that many draws); smooth above 65 535; gain outside 1 .. 65 535; env_of, ret, out->elites or out->elite_min not 4-byte or weights_in,
+ *   out->weights not 2-byte aligned; an output sharing a byte with ret, env_of, another output, or weights_in other than the exact in-place case.
+ *   (21x21, launch included, (K, T, E) = (16, 8, 4) / (1 024, 64, 64): 4 096 envs 20 / 131 us, 65 536 envs 32 us / 2.69 ms, against 70 / 622 us and 439 us / 8.77 ms for torch.topk + cw_shoot_actions + a scatter_add histogram + clamp and cast in torch; a whole iteration behind cw_shoot 42 us / 4.38 ms and 176 us / 66.5 ms against 92 us / 4.89 ms and 584 us / 72.6 ms: tools/measure_refit.py, profiles/r14_refit.txt.) */
+int cw_shoot_refit(cw_engine *e, const int32_t *env_of, int32_t n_states, int32_t n_steps, int32_t n_samples, int32_t n_elites,
+                   uint64_t seed, const uint64_t *seed_dev, const uint16_t *weights_in, const int32_t *ret,
+                   uint32_t smooth, uint32_t gain, const cw_refit_out *out, cw_stream_t stream);
 
 /* --- searching deep: "have I seen this state before?" -- a device-resident VISITED SET of packed records, filled by kernels (breadth-first search with duplicate
  * detection, distance-to-goal labels, the "solvable within D steps" filter of a curriculum).  6^D action strings reach far fewer than 6^D states; cw_expand plus
