@@ -79,6 +79,16 @@ class cw_refit_out(C.Structure):
     _fields_ = [('elites', C.c_void_p), ('weights', C.c_void_p), ('elite_min', C.c_void_p)]
 
 
+class cw_replay_table(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ('hdr', 'slot_pos', 'next_hdr', 'next_slot_pos', 'goal_hdr', 'goal_slot_pos', 'action', 'flags', 'reward', 'episode',
+                                          'env_episode', 'n')] + [('steps', C.c_int32), ('num_envs', C.c_int32)]
+
+
+class cw_replay_out(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ('hdr', 'slot_pos', 'next_hdr', 'next_slot_pos', 'goal_hdr', 'goal_slot_pos', 'action', 'reward', 'done', 'desired',
+                                          'env', 'slot', 'future')]
+
+
 class cw_seen_out(C.Structure):
     _fields_ = [('fresh', C.c_void_p), ('first', C.c_void_p)]
 
@@ -134,6 +144,12 @@ ABI = {
     'cw_reach': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_reach_out), _VP]),
     'cw_load_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_render_records': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    'cw_replay_reserve': (C.c_int, [_VP, C.c_int32]),
+    'cw_replay_bytes': (C.c_size_t, [_VP]),
+    'cw_replay_buffers': (C.c_int, [_VP, C.POINTER(cw_replay_table)]),
+    'cw_replay_clear': (C.c_int, [_VP, _VP]),
+    'cw_replay_push': (C.c_int, [_VP, _VP, C.c_int, _VP]),
+    'cw_replay_sample': (C.c_int, [_VP, C.c_int32, C.c_uint64, _VP, C.c_uint32, C.c_int32, C.POINTER(cw_replay_out), _VP]),
     'cw_step': (C.c_int, [_VP, _VP, C.c_int, _VP]),
     'cw_step_many': (C.c_int, [_VP, _VP, C.c_int, C.c_int32, _VP]),
     'cw_rollout': (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
@@ -194,6 +210,8 @@ CWH_REACH_OK, CWH_REACH_NO_FIELD, CWH_REACH_N_STATES, CWH_REACH_DEPTH, CWH_REACH
 CWH_REACH_CHUNK, CWH_REACH_MAX_ROWS, CWH_REACH_MAX_DEPTH, CWH_REACH_BLOCKS_PER_CU, CWH_REACH_SECTIONS = 4096, (2 ** 28 - 1) // 6 - 63, 32767, 8, 18
 CWH_LOAD_OK, CWH_LOAD_NO_RECORDS, CWH_LOAD_N_RECORDS, CWH_LOAD_OWN_ORDER, CWH_LOAD_ALIGN, CWH_LOAD_ENGINE_OVERLAP, CWH_LOAD_STATUS_OVERLAP = range(7)
 CWH_LOAD_NO_PART, CWH_LOAD_LOADED, CWH_LOAD_BAD_INDEX, CWH_LOAD_REFUSED = range(4)
+CWH_REPLAY_OK, CWH_REPLAY_N_ROWS, CWH_REPLAY_HER, CWH_REPLAY_STRATEGY, CWH_REPLAY_NO_FIELD, CWH_REPLAY_ALIGN, CWH_REPLAY_OVERLAP = range(7)
+CWH_REPLAY_FIELDS, CWH_REPLAY_SECTIONS, CWH_REPLAY_MAX_STEPS, CWH_REPLAY_CTL_BYTES = 13, 12, 1 << 24, 256
 CWH_CKPT_SECTIONS = 22
 CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN = 16, 256
 CWH_ALT_NO_PIXEL = 0xFFFFFFFF
@@ -236,6 +254,11 @@ HOST_HELPERS = {
     'cwh_record_ok_of': (C.c_int, [C.c_uint32, _VP, _VP]),
     'cwh_load_record_index_in_range': (C.c_int, [C.c_int32, C.c_int32]),
     'cwh_load_records_args': (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64]),
+    'cwh_replay_reward_of': (C.c_int32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int32]),
+    'cwh_replay_layout': (C.c_int64, [C.c_int32, C.c_int32, _VP]),
+    'cwh_replay_bytes_of': (C.c_int64, [C.c_int32, C.c_int32]),
+    'cwh_replay_sample_args': (C.c_int, [C.c_int32, C.c_uint32, C.c_int32, _VP]),
+    'cwh_replay_field_bytes_of': (C.c_int, [C.c_int]),
     'cwh_reach_rows_of': (C.c_int64, [C.c_int64]),
     'cwh_reach_chunks_of': (C.c_int64, [C.c_int64]),
     'cwh_reach_grid_of': (C.c_int64, [C.c_int64, C.c_int32]),

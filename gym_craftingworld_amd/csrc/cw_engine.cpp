@@ -48,6 +48,10 @@ hipError_t cwk_launch_shoot_actions(int n_states, int n_steps, int n_rows, unsig
 hipError_t cwk_launch_refit(const CwParams *P, const CwTuning *T, const int32_t *env_of, int n_states, int n_steps, int n_samples, int n_elites,
                             unsigned long long seed, const unsigned long long *seed_dev, const uint16_t *weights_in, const int32_t *ret, uint32_t smooth,
                             uint32_t gain, int32_t *elites, uint16_t *weights, int32_t *elite_min, hipStream_t st);
+hipError_t cwk_launch_replay_push(const CwParams *P, const CwReplay *R, const void *actions, int act_dtype, hipStream_t st);
+hipError_t cwk_launch_replay_clear(const CwParams *P, const CwTuning *T, const CwReplay *R, hipStream_t st);
+hipError_t cwk_launch_replay_sample(const CwParams *P, const CwTuning *T, const CwReplay *R, int n_rows, unsigned long long seed,
+                                    const unsigned long long *seed_dev, uint32_t her, int strategy, const CwReplayOut *O, hipStream_t st);
 hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const CwSeen *S, const int32_t *group, const uint4 *hdr, const uint4 *pos, int n_states,
                                   uint8_t *fresh, int32_t *first, hipStream_t st);
 hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st);
@@ -119,6 +123,9 @@ struct cw_engine {
     void *reach = nullptr;             // cw_reach's workspace, one allocation (cw_reach_reserve), or null: none reserved
     CwReach Rc{};                      // ... its sections (cw_host.cpp: cwh_reach_layout)
     size_t reach_bytes = 0;
+    void *replay = nullptr;            // the replay buffer's one allocation (cw_replay_reserve), or null: none reserved
+    CwReplay Rp{};                     // ... its sections (cw_host.cpp: cwh_replay_layout)
+    size_t replay_bytes = 0;
     int n = 0, S = 0, ncell = 0, K = 0;
     // resident stepper of the single-env loop (cw_step_resident; cw_kernels.hip: cw_resident_kernel)
     CwResident *res = nullptr;         // pinned coherent host memory, or null (engine not eligible)
@@ -234,7 +241,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_shoot_refit, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_shoot_refit, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_replay_clear, cw_replay_push, cw_replay_sample, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -678,6 +685,7 @@ int cw_destroy(cw_engine *e)
     if (e->bank) (void)hipFree(e->bank);
     if (e->seen) (void)hipFree(e->seen);
     if (e->reach) (void)hipFree(e->reach);
+    if (e->replay) (void)hipFree(e->replay);
     for (void *p : e->host_allocs) (void)hipHostFree(p);
     delete e;
     return CW_OK;
@@ -1119,6 +1127,146 @@ int cw_shoot_refit(cw_engine *e, const int32_t *env_of, int32_t n_states, int32_
     if (in.rc != CW_OK) return in.rc;
     HIP_TRY(cwk_launch_refit(&e->P, &e->tune, env_of, n_states, n_steps, n_samples, n_elites, (unsigned long long)seed, (const unsigned long long *)seed_dev,
                              weights_in, ret, smooth, gain, out->elites, out->weights, out->elite_min, (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ replay: transitions as packed records, relabelled minibatches
+// One allocation of the engine's, like the snapshot bank and the visited set and as far from every checkpoint blob and snapshot row; its sections are
+// cw_host.cpp's (cwh_replay_layout).  A reserve drops everything stored: the new buffer is zero-filled and cleared before the call returns.
+static void replay_free(cw_engine *e)
+{
+    if (e->replay) (void)hipFree(e->replay);
+    e->replay = nullptr;
+    e->Rp = CwReplay{};
+    e->replay_bytes = 0;
+}
+
+int cw_replay_reserve(cw_engine *e, int32_t steps)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_replay_reserve: null engine");
+    uint64_t at[CWH_REPLAY_SECTIONS];
+    const int64_t bytes = steps == 0 ? 0 : cwh_replay_layout(steps, e->n, at);
+    if (bytes < 0)
+        return fail(CW_ERR_INVALID, "cw_replay_reserve: steps = %d must be 0 .. %d with steps * num_envs (%d) below 2^31", steps, CWH_REPLAY_MAX_STEPS, e->n);
+    SyncEntry in(e);                                 // (the engine's own work: a push or a sample in flight uses the buffer about to go)
+    if (in.rc != CW_OK) return in.rc;
+    replay_free(e);
+    if (steps == 0) return CW_OK;
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CW_ERR_HIP, "cw_replay_reserve: no device memory for %d steps of %d envs (%lld bytes)", steps, e->n, (long long)bytes);
+    }
+    char *const b = (char *)p;
+    CwReplay R{};
+    R.ctl = (unsigned long long *)(b + at[CWH_REPLAY_S_CTL]);
+    R.env_episode = (uint32_t *)(b + at[CWH_REPLAY_S_ENV_EPISODE]);
+    R.hdr = (uint4 *)(b + at[CWH_REPLAY_S_HDR]);
+    R.pos = (uint4 *)(b + at[CWH_REPLAY_S_POS]);
+    R.next_hdr = (uint4 *)(b + at[CWH_REPLAY_S_NEXT_HDR]);
+    R.next_pos = (uint4 *)(b + at[CWH_REPLAY_S_NEXT_POS]);
+    R.goal_hdr = (uint4 *)(b + at[CWH_REPLAY_S_GOAL_HDR]);
+    R.goal_pos = (uint4 *)(b + at[CWH_REPLAY_S_GOAL_POS]);
+    R.reward = (int32_t *)(b + at[CWH_REPLAY_S_REWARD]);
+    R.episode = (uint32_t *)(b + at[CWH_REPLAY_S_EPISODE]);
+    R.action = (uint8_t *)(b + at[CWH_REPLAY_S_ACTION]);
+    R.flags = (uint8_t *)(b + at[CWH_REPLAY_S_FLAGS]);
+    R.steps = steps;
+    if (hipMemsetAsync(p, 0, (size_t)bytes, e->aux) != hipSuccess || cwk_launch_replay_clear(&e->P, &e->tune, &R, e->aux) != hipSuccess ||
+        hipStreamSynchronize(e->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(p);
+        return fail(CW_ERR_HIP, "cw_replay_reserve: clearing the buffer failed");
+    }
+    e->replay = p;
+    e->Rp = R;
+    e->replay_bytes = (size_t)bytes;
+    return CW_OK;
+}
+
+size_t cw_replay_bytes(const cw_engine *e)
+{
+    if (!e) { (void)fail(CW_ERR_INVALID, "cw_replay_bytes: null engine"); return 0; }
+    return e->replay ? e->replay_bytes : 0;
+}
+
+int cw_replay_buffers(cw_engine *e, cw_replay_table *out)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_replay_buffers: null %s", !e ? "engine" : "out");
+    if (!e->replay) return fail(CW_ERR_STATE, "cw_replay_buffers: no buffer reserved (cw_replay_reserve)");
+    const CwReplay &R = e->Rp;
+    out->hdr = (const uint8_t *)R.hdr;
+    out->slot_pos = (const uint16_t *)R.pos;
+    out->next_hdr = (const uint8_t *)R.next_hdr;
+    out->next_slot_pos = (const uint16_t *)R.next_pos;
+    out->goal_hdr = (const uint8_t *)R.goal_hdr;
+    out->goal_slot_pos = (const uint16_t *)R.goal_pos;
+    out->action = R.action;
+    out->flags = R.flags;
+    out->reward = R.reward;
+    out->episode = R.episode;
+    out->env_episode = R.env_episode;
+    out->n = (const uint64_t *)R.ctl;
+    out->steps = R.steps;
+    out->num_envs = e->n;
+    return CW_OK;
+}
+
+// Only enqueues ONE kernel: no wait, no allocation, the same call whether it runs or is captured.
+int cw_replay_clear(cw_engine *e, cw_stream_t stream)
+{
+    if (!e) return fail(CW_ERR_INVALID, "cw_replay_clear: null engine");
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_replay_clear called before cw_reset");
+    if (!e->replay) return fail(CW_ERR_STATE, "cw_replay_clear: no buffer reserved (cw_replay_reserve)");
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_replay_clear(&e->P, &e->tune, &e->Rp, (hipStream_t)stream));
+    return in.done();
+}
+
+// cw_step's argument rules, then the push and the one-lane launch that advances n.  Of the engine only the buffer is written.
+int cw_replay_push(cw_engine *e, const void *actions, int action_dtype, cw_stream_t stream)
+{
+    if (!e || !actions) return fail(CW_ERR_INVALID, "cw_replay_push: null argument");
+    if (action_dtype < CW_ACT_I32 || action_dtype > CW_ACT_U8) return fail(CW_ERR_INVALID, "cw_replay_push: bad action dtype %d", action_dtype);
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_replay_push called before cw_reset");
+    if (!e->replay) return fail(CW_ERR_STATE, "cw_replay_push: no buffer reserved (cw_replay_reserve)");
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    HIP_TRY(cwk_launch_replay_push(&e->P, &e->Rp, actions, action_dtype, (hipStream_t)stream));
+    return in.done();
+}
+
+// Checks (cwh_replay_sample_args, tested on the CPU), then ONE kernel.  Nothing of the engine is written.
+int cw_replay_sample(cw_engine *e, int32_t n_rows, uint64_t seed, const uint64_t *seed_dev, uint32_t her, int32_t strategy, const cw_replay_out *out,
+                     cw_stream_t stream)
+{
+    if (!e || !out) return fail(CW_ERR_INVALID, "cw_replay_sample: null %s", !e ? "engine" : "out");
+    const auto at = [](const void *p) { return (uint64_t)(uintptr_t)p; };
+    const uint64_t fields[CWH_REPLAY_FIELDS] = {at(out->hdr), at(out->slot_pos), at(out->next_hdr), at(out->next_slot_pos), at(out->goal_hdr),
+                                                at(out->goal_slot_pos), at(out->action), at(out->reward), at(out->done), at(out->desired), at(out->env),
+                                                at(out->slot), at(out->future)};
+    switch (cwh_replay_sample_args(n_rows, her, strategy, fields)) {
+    case CWH_REPLAY_OK: break;
+    case CWH_REPLAY_N_ROWS: return fail(CW_ERR_INVALID, "cw_replay_sample: n_rows = %d must be 0 .. %d", n_rows, CWH_MAX_STATES);
+    case CWH_REPLAY_HER: return fail(CW_ERR_INVALID, "cw_replay_sample: her = %u must be 0 .. 65536", her);
+    case CWH_REPLAY_STRATEGY: return fail(CW_ERR_INVALID, "cw_replay_sample: strategy = %d must be 0 (future) or 1 (final)", strategy);
+    case CWH_REPLAY_NO_FIELD: return fail(CW_ERR_INVALID, "cw_replay_sample: every field of out is null");
+    case CWH_REPLAY_ALIGN:
+        return fail(CW_ERR_INVALID, "cw_replay_sample: the record fields must be 16-byte, reward / env / slot / future 4-byte and desired 2-byte aligned");
+    default: return fail(CW_ERR_INVALID, "cw_replay_sample: two fields of out overlap");
+    }
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_replay_sample called before cw_reset");
+    if (!e->replay) return fail(CW_ERR_STATE, "cw_replay_sample: no buffer reserved (cw_replay_reserve)");
+    if (n_rows == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    CwReplayOut O{};
+    O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.next_hdr = (uint4 *)out->next_hdr; O.next_pos = (uint4 *)out->next_slot_pos;
+    O.goal_hdr = (uint4 *)out->goal_hdr; O.goal_pos = (uint4 *)out->goal_slot_pos; O.action = out->action; O.reward = out->reward; O.done = out->done;
+    O.desired = out->desired; O.env = out->env; O.slot = out->slot; O.future = out->future;
+    HIP_TRY(cwk_launch_replay_sample(&e->P, &e->tune, &e->Rp, n_rows, (unsigned long long)seed, (const unsigned long long *)seed_dev, her, strategy, &O,
+                                     (hipStream_t)stream));
     return in.done();
 }
 

@@ -347,6 +347,48 @@ int cwh_load_records_args(int32_t num_envs, uint64_t src, uint64_t hdr, uint64_t
     return CWH_LOAD_OK;
 }
 
+// ------------------------------------------------------------------------------ cw_replay_*: the relabelled reward, the buffer's sections, the argument rules
+int32_t cwh_replay_reward_of(uint32_t achieved, uint32_t goal, uint32_t task_mask, int subset, int changed, int32_t max_steps)
+{
+    return cwh_replay_reward(achieved, goal, task_mask, subset, changed, max_steps);
+}
+
+int64_t cwh_replay_layout(int32_t steps, int32_t num_envs, uint64_t *offsets)
+{
+    if (steps < 1 || steps > CWH_REPLAY_MAX_STEPS || num_envs < 1 || (int64_t)steps * (int64_t)num_envs >= (1ll << 31)) return -1;
+    const uint64_t N = (uint64_t)num_envs, T = (uint64_t)steps * N;
+    const uint64_t bytes[CWH_REPLAY_SECTIONS] = {CWH_REPLAY_CTL_BYTES, 4 * N, 16 * T, 16 * T, 16 * T, 16 * T, 16 * T, 16 * T, 4 * T, 4 * T, T, T};
+    uint64_t at = 0;
+    for (int i = 0; i < CWH_REPLAY_SECTIONS; i++) {
+        if (offsets) offsets[i] = at;
+        at += (bytes[i] + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
+    }
+    return (int64_t)at;
+}
+int64_t cwh_replay_bytes_of(int32_t steps, int32_t num_envs) { return cwh_replay_layout(steps, num_envs, nullptr); }
+
+// cw_replay_out's fields in its order: hdr, slot_pos, next_hdr, next_slot_pos, goal_hdr, goal_slot_pos, action, reward, done, desired, env, slot, future
+static const int kReplayFieldBytes[CWH_REPLAY_FIELDS] = {16, 16, 16, 16, 16, 16, 1, 4, 1, 2, 4, 4, 4};
+int cwh_replay_field_bytes_of(int field) { return field >= 0 && field < CWH_REPLAY_FIELDS ? kReplayFieldBytes[field] : 0; }
+
+int cwh_replay_sample_args(int32_t n_rows, uint32_t her, int32_t strategy, const uint64_t *fields)
+{
+    if (n_rows < 0 || n_rows > CWH_MAX_STATES) return CWH_REPLAY_N_ROWS;
+    if (her > 65536u) return CWH_REPLAY_HER;
+    if (strategy != 0 && strategy != 1) return CWH_REPLAY_STRATEGY;
+    int any = 0;
+    for (int f = 0; f < CWH_REPLAY_FIELDS; f++) any |= fields[f] != 0;
+    if (!any) return CWH_REPLAY_NO_FIELD;
+    for (int f = 0; f < CWH_REPLAY_FIELDS; f++)
+        if (fields[f] & (uint64_t)(kReplayFieldBytes[f] - 1)) return CWH_REPLAY_ALIGN;
+    for (int f = 0; f < CWH_REPLAY_FIELDS; f++)
+        for (int g = f + 1; g < CWH_REPLAY_FIELDS; g++)
+            if (fields[f] && fields[g] &&
+                cwh_ranges_overlap(fields[f], (uint64_t)kReplayFieldBytes[f] * (uint64_t)n_rows, fields[g], (uint64_t)kReplayFieldBytes[g] * (uint64_t)n_rows))
+                return CWH_REPLAY_OVERLAP;
+    return CWH_REPLAY_OK;
+}
+
 // ------------------------------------------------------------------------------ cw_reach: the rows of a level, the workspace's sections, the argument rules
 int64_t cwh_reach_rows_of(int64_t f) { return cwh_reach_rows(f); }
 int64_t cwh_reach_chunks_of(int64_t rows) { return cwh_reach_chunks(rows); }

@@ -324,6 +324,37 @@ enum { CWH_LOAD_OK = 0, CWH_LOAD_NO_RECORDS = 1, CWH_LOAD_N_RECORDS = 2, CWH_LOA
 int cwh_load_records_args(int32_t num_envs, uint64_t src, uint64_t hdr, uint64_t slot_pos, int32_t n_records, uint64_t status, uint64_t engine_hdr,
                           uint64_t engine_slot_pos);
 
+// ---- cw_replay_*: the replay buffer of packed records (include/craftingworld.h states it).  THE REWARD of a relabelled row, shared by the sample kernel and
+// the host: -1 unless the stored transition changed the state; then max_steps iff the goal g holds of the successor's achieved mask a under the task mask --
+// subset == 0: a == g; else (g & ~a) == 0 and some position equal -- the expressions of step_env and of compute_reward_batch.
+static inline CWH_HOST_DEVICE int32_t cwh_replay_reward(uint32_t achieved, uint32_t goal, uint32_t task_mask, int subset, int changed, int32_t max_steps)
+{
+    if (!changed) return -1;
+    const uint32_t am = achieved & task_mask, dm = goal & task_mask;
+    const int hit = subset ? ((dm & ~am) == 0u && ((~(dm ^ am)) & task_mask) != 0u) : am == dm;
+    return hit ? max_steps : -1;
+}
+int32_t cwh_replay_reward_of(uint32_t achieved, uint32_t goal, uint32_t task_mask, int subset, int changed, int32_t max_steps);   // (exported for the CPU tests)
+// the buffer of `steps` slots of `num_envs` transitions: CWH_REPLAY_SECTIONS sections, each a multiple of CWH_SNAP_ALIGN bytes, in this order -- the control
+// block (CWH_REPLAY_CTL_BYTES), env_episode (4 bytes an env), the six record arrays (16 bytes a transition each), reward and episode (4 each), action and
+// flags (1 each): 106 bytes a transition.  Writes the sections' offsets (may be null); -> the bytes, -1 outside the limits: steps 1 .. CWH_REPLAY_MAX_STEPS,
+// num_envs >= 1, steps * num_envs < 2^31 (the total then stays below 2^38).
+#define CWH_REPLAY_MAX_STEPS (1 << 24)
+#define CWH_REPLAY_CTL_BYTES 256
+enum { CWH_REPLAY_S_CTL = 0, CWH_REPLAY_S_ENV_EPISODE, CWH_REPLAY_S_HDR, CWH_REPLAY_S_POS, CWH_REPLAY_S_NEXT_HDR, CWH_REPLAY_S_NEXT_POS, CWH_REPLAY_S_GOAL_HDR,
+       CWH_REPLAY_S_GOAL_POS, CWH_REPLAY_S_REWARD, CWH_REPLAY_S_EPISODE, CWH_REPLAY_S_ACTION, CWH_REPLAY_S_FLAGS, CWH_REPLAY_SECTIONS };
+int64_t cwh_replay_layout(int32_t steps, int32_t num_envs, uint64_t *offsets);
+int64_t cwh_replay_bytes_of(int32_t steps, int32_t num_envs);
+// the argument rules of cw_replay_sample, in the order they are tested; fields: the CWH_REPLAY_FIELDS addresses of cw_replay_out in its order, as integers
+// (0: null): 0 <= n_rows <= CWH_MAX_STATES (CWH_REPLAY_N_ROWS), her <= 65 536 (CWH_REPLAY_HER), strategy 0 or 1 (CWH_REPLAY_STRATEGY), some field given
+// (CWH_REPLAY_NO_FIELD), the six record fields 16-byte, reward / env / slot / future 4-byte and desired 2-byte aligned (CWH_REPLAY_ALIGN), no two fields
+// sharing a byte of their n_rows rows (CWH_REPLAY_OVERLAP).
+#define CWH_REPLAY_FIELDS 13
+enum { CWH_REPLAY_OK = 0, CWH_REPLAY_N_ROWS = 1, CWH_REPLAY_HER = 2, CWH_REPLAY_STRATEGY = 3, CWH_REPLAY_NO_FIELD = 4, CWH_REPLAY_ALIGN = 5,
+       CWH_REPLAY_OVERLAP = 6 };
+int cwh_replay_sample_args(int32_t n_rows, uint32_t her, int32_t strategy, const uint64_t *fields);
+int cwh_replay_field_bytes_of(int field);          // bytes a row of field 0 .. CWH_REPLAY_FIELDS - 1 takes (16, 1, 4 or 2); 0 for any other number
+
 // ---- cw_reach: breadth-first search on the device (cw_reach_reserve / cw_reach).  THE ROWS of a level over a frontier of F states: row a * Fp + j is action a
 // on frontier state j, Fp = F rounded up to a wavefront, so that no wave straddles two actions; rows j >= F of an action take no part.  The order is the one
 // a * F + j gives.  The row is the row field of the visited set's bids: 6 * (max_rows + 63) < 2^CWH_SEEN_ROW_BITS is the cap on max_rows.

@@ -26,6 +26,8 @@
 //                     integer mix (no action tensor), G lanes per state and a shuffle reduction; cw_shoot_actions_kernel decodes the draws.  Pure.
 //   cw_refit_select_kernel / cw_refit_count_kernel  the other half of a CEM iteration: the exact top E of every column of ret [K][M] (a binary search on the
 //                     value, then a compaction in sample order, cw_shoot_kernel's lanes), and the next weights from the elites' regenerated draws.  Pure.
+//   cw_replay_push_kernel / cw_replay_sample_kernel  the replay buffer of such records: a transition (s, s', the goal as a record) per env and push, one lane
+//                     per env, and minibatches of rows relabelled in hindsight, one lane per row; n advances by a one-lane launch, cw_replay_clear_kernel zeroes it.
 //   cw_seen_claim_kernel / cw_seen_resolve_kernel  the visited set of such records: which of M rows brings a key the set has not held, and which is the first
 //                     of its key in the call -- an open-addressed table, one lane per row, atomics on the slot words and no wait; cw_seen_clear_kernel empties it.
 //   cw_reach_*_kernel  breadth-first search over such records without a host round trip: expansion, the set's two kernels, a stable compaction (count, scan,
@@ -1115,6 +1117,139 @@ __global__ __launch_bounds__(256) void cw_refit_count_kernel(const int32_t *__re
         weights[at + 3 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c3);
         weights[at + 4 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c4);
         weights[at + 5 * M] = (uint16_t)cwh_refit_weight(smooth, gain, c5);
+    }
+}
+
+// ------------------------------------------------------------------------------------ replay: transitions kept as packed records, minibatches relabelled in hindsight
+// The buffer (CwReplay, cw_layout.h) is time-major, so every array a push writes is one contiguous run per wave.  Three kernels and a one-lane launch; no
+// atomics, no LDS, and no lane or workgroup ever waits for another: n, the number of pushes, advances by a KERNEL BOUNDARY (cw_replay_advance_kernel behind
+// every push), which is also what makes a replayed graph push into the next slot each time.
+//   cw_replay_push_kernel    one lane per env: the env's record s, step_env as the pure function it is (cw_expand_kernel's use of it, with the env's own
+//                            init_pos) for s', reward, done and changed, the goal record from the env's goal state, THE EPISODE RULE against the predecessor slot
+//                            -- read before the slot is written, so steps == 1 is legal -- and the stores into slot n % steps.  Of the engine nothing is written.
+//   cw_replay_sample_kernel  one lane per row, grid-stride: the three draws, for a relabelled row the binary search for the episode's last position (episode
+//                            numbers are only ever COMPARED) and the draw of f, then the record gathers and the relabel.  Reads the buffer, writes the outputs.
+//   cw_replay_clear_kernel   n = 0 and every env's running episode 0.
+__device__ __forceinline__ bool same_record(const uint4 &a, const uint4 &b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+
+__global__ __launch_bounds__(256) void cw_replay_push_kernel(CwParams P, CwReplay R, const void *actions, int act_dtype)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= P.n_envs) return;
+    const unsigned long long n = R.ctl[0], L = (unsigned long long)R.steps;
+    const size_t N = (size_t)P.n_envs;
+    const size_t at = (size_t)(n % L) * N + (size_t)i;                    // (a slot below steps and an env below n_envs: inside every [steps][n_envs] array)
+    const int a = load_action(actions, act_dtype, i);
+    const uint4 h0 = P.hdr[i], p0 = P.pos[i];
+    const uint4 gp = P.goal_pos[i];
+    const uint32_t gc = P.goal_codes[i], ga = P.goal_agent[i];
+    uint32_t ep = 0;                                                      // the first push after a clear starts episode 0
+    if (n) {                                                              // THE EPISODE RULE: the predecessor, read before this push's stores
+        const size_t prev = (size_t)((n - 1ull) % L) * N + (size_t)i;
+        const uint4 ph = R.next_hdr[prev], pp = R.next_pos[prev];
+        const bool goes_on = !(R.flags[prev] & CW_REPLAY_DONE) && same_record(ph, h0) && same_record(pp, p0);
+        ep = R.env_episode[i] + (goes_on ? 0u : 1u);
+    }
+    uint4 h = h0;
+    uint32_t sp[8];
+    unpack_pos(p0, sp);
+    const CwStepOut o = step_env(P, h, sp, a, [&]() { return P.init_pos[i]; });
+    const uint32_t desired = h0.y >> 16;
+    const uint32_t gr = __umulhi(ga, P.div_magic), gcol = ga - gr * (uint32_t)P.size;
+    uint4 gh;
+    gh.x = (gr & 0xFFu) | ((gcol & 0xFFu) << 8) | (h0.x & 0xFF000000u);  // hold 0, the env's menu id
+    gh.y = desired | (desired << 16);
+    gh.z = 0u;
+    gh.w = gc;
+    R.hdr[at] = h0;
+    R.pos[at] = p0;
+    R.next_hdr[at] = h;
+    R.next_pos[at] = pack_pos(sp);
+    R.goal_hdr[at] = gh;
+    R.goal_pos[at] = gp;
+    R.reward[at] = o.reward;
+    R.episode[at] = ep;
+    R.action[at] = o.invalid ? (uint8_t)255 : (uint8_t)a;
+    R.flags[at] = (uint8_t)((o.changed ? CW_REPLAY_CHANGED : 0u) | (o.done ? CW_REPLAY_DONE : 0u));
+    R.env_episode[i] = ep;
+}
+
+__global__ __launch_bounds__(64) void cw_replay_advance_kernel(CwReplay R)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) R.ctl[0] = R.ctl[0] + 1ull;
+}
+
+__global__ __launch_bounds__(256) void cw_replay_clear_kernel(CwReplay R, int n_envs)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x, first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (first < CW_REPLAY_CTL_WORDS) R.ctl[first] = 0ull;
+    for (size_t i = first; i < (size_t)n_envs; i += stride) R.env_episode[i] = 0u;
+}
+
+__global__ __launch_bounds__(256) void cw_replay_sample_kernel(CwReplay R, int n_envs, uint32_t task_mask, int max_steps, int n_rows, unsigned long long seed,
+                                                               const unsigned long long *__restrict__ seed_dev, uint32_t her, int strategy, CwReplayOut O)
+{
+    const unsigned long long n = R.ctl[0];
+    if (n == 0ull) return;                                                // an empty buffer: no row is written
+    const unsigned long long s = seed + (seed_dev ? *seed_dev : 0ull);
+    const uint32_t L = (uint32_t)R.steps;
+    const unsigned long long lo = n > (unsigned long long)L ? n - (unsigned long long)L : 0ull;
+    const uint32_t V = (uint32_t)(n - lo);                                // 1 .. steps transitions are stored: positions lo .. n - 1
+    const uint32_t slot_lo = (uint32_t)(lo % (unsigned long long)L);
+    const size_t N = (size_t)n_envs;
+    // Positions are handled as offsets d = position - lo, 0 <= d < V <= steps; the slot of offset d is (slot_lo + d) mod steps, below steps.
+    const auto slot_of = [&](uint32_t d) { const uint32_t t = slot_lo + d; return t >= L ? t - L : t; };
+    for (size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x; b < (size_t)n_rows; b += (size_t)gridDim.x * blockDim.x) {
+        // i, p and f are RANGES BY CONSTRUCTION: mulhi32(r, m) < m for every r, so i < n_envs, dp < V and df <= de < V; nothing read from memory becomes an
+        // address -- the episode numbers below are compared, the records copied.
+        const uint32_t i = cwh_shoot_mulhi(cwh_shoot_draw(s, (uint32_t)b, 0u, 0u), (uint32_t)n_envs);
+        const uint32_t dp = cwh_shoot_mulhi(cwh_shoot_draw(s, (uint32_t)b, 1u, 0u), V);
+        const bool relabel = (cwh_shoot_draw(s, (uint32_t)b, 2u, 0u) >> 16) < her;
+        const uint32_t sl = slot_of(dp);
+        const size_t at = (size_t)sl * N + (size_t)i;
+        uint4 h = R.hdr[at], hn = R.next_hdr[at], hg = R.goal_hdr[at];
+        const uint4 p = R.pos[at], pn = R.next_pos[at];
+        uint4 pg = R.goal_pos[at];
+        const uint32_t fl = R.flags[at];
+        int32_t reward = R.reward[at];
+        bool done = (fl & CW_REPLAY_DONE) != 0u;
+        uint32_t desired = h.y >> 16;
+        int32_t future = -1;
+        if (relabel) {
+            const uint32_t ep = R.episode[at];
+            uint32_t a = dp, z = V - 1u;                                  // the last offset in [dp, V) of p's episode: episode numbers never decrease along an
+            while (a < z) {                                               // env's positions, so those equal to p's are one run from dp on (at most 24 rounds)
+                const uint32_t mid = a + (z - a + 1u) / 2u;
+                if (R.episode[(size_t)slot_of(mid) * N + (size_t)i] == ep) a = mid; else z = mid - 1u;
+            }
+            const uint32_t de = a;
+            const uint32_t df = strategy == 0 ? dp + cwh_shoot_mulhi(cwh_shoot_draw(s, (uint32_t)b, 3u, 0u), de - dp + 1u) : de;
+            const uint32_t sf = slot_of(df);
+            const size_t af = (size_t)sf * N + (size_t)i;
+            hg = R.next_hdr[af];
+            pg = R.next_pos[af];
+            const uint32_t g = hg.y & 0xFFFFu;
+            hg.y = g | (g << 16);
+            h.y = (h.y & 0xFFFFu) | (g << 16);
+            hn.y = (hn.y & 0xFFFFu) | (g << 16);
+            reward = cwh_replay_reward(hn.y & 0xFFFFu, g, task_mask, (int)((hn.z >> 17) & 1u), (int)(fl & CW_REPLAY_CHANGED), max_steps);
+            done = (hn.z & 0xFFFFu) >= (uint32_t)max_steps || reward == max_steps;
+            desired = g;
+            future = (int32_t)sf;
+        }
+        if (O.hdr) O.hdr[b] = h;
+        if (O.pos) O.pos[b] = p;
+        if (O.next_hdr) O.next_hdr[b] = hn;
+        if (O.next_pos) O.next_pos[b] = pn;
+        if (O.goal_hdr) O.goal_hdr[b] = hg;
+        if (O.goal_pos) O.goal_pos[b] = pg;
+        if (O.action) O.action[b] = R.action[at];
+        if (O.reward) O.reward[b] = reward;
+        if (O.done) O.done[b] = done ? 1 : 0;
+        if (O.desired) O.desired[b] = (uint16_t)desired;
+        if (O.env) O.env[b] = (int32_t)i;
+        if (O.slot) O.slot[b] = (int32_t)sl;
+        if (O.future) O.future[b] = future;
     }
 }
 
@@ -3428,6 +3563,30 @@ hipError_t cwk_launch_refit(const CwParams *P, const CwTuning *T, const int32_t 
     else
         hipLaunchKernelGGL(cw_refit_count_kernel<false>, g_count, block, 0, st, env_of, P->n_envs, n_states, n_steps, n_elites, seed, seed_dev, weights_in, elites,
                            smooth, gain, weights);
+    return hipGetLastError();
+}
+
+// cw_replay_push: the push over the envs, then the one-lane launch that advances n; cw_replay_sample: grid-stride under the refit's grid rule
+hipError_t cwk_launch_replay_push(const CwParams *P, const CwReplay *R, const void *actions, int act_dtype, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_replay_push_kernel, dim3((unsigned)((P->n_envs + 255) / 256)), dim3(256), 0, st, *P, *R, actions, act_dtype);
+    const hipError_t rc = hipGetLastError();
+    if (rc != hipSuccess) return rc;
+    hipLaunchKernelGGL(cw_replay_advance_kernel, dim3(1), dim3(64), 0, st, *R);
+    return hipGetLastError();
+}
+
+hipError_t cwk_launch_replay_clear(const CwParams *P, const CwTuning *T, const CwReplay *R, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_replay_clear_kernel, dim3((unsigned)cwh_refit_grid((int64_t)P->n_envs, T->n_cu)), dim3(256), 0, st, *R, P->n_envs);
+    return hipGetLastError();
+}
+
+hipError_t cwk_launch_replay_sample(const CwParams *P, const CwTuning *T, const CwReplay *R, int n_rows, unsigned long long seed,
+                                    const unsigned long long *seed_dev, uint32_t her, int strategy, const CwReplayOut *O, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_replay_sample_kernel, dim3((unsigned)cwh_refit_grid((int64_t)n_rows, T->n_cu)), dim3(256), 0, st, *R, P->n_envs, P->task_mask,
+                       P->max_steps, n_rows, seed, seed_dev, her, strategy, *O);
     return hipGetLastError();
 }
 

@@ -138,6 +138,36 @@ struct CwReachOut {
     int32_t *searched_depth;     // [1]
 };
 
+// The REPLAY BUFFER of an engine (cw_replay_reserve): `steps` slots of n_envs transitions each in device memory, TIME-MAJOR -- slot t of env i at [t * n_envs + i],
+// so a push is one coalesced run per array -- one array per field, and a control block.  One allocation, its sections cw_host.cpp's (cwh_replay_layout).  A
+// transition is three packed records (the state s, its successor s', the episode's goal as a record), the action (255: outside 0..5), flags (bit 0 changed,
+// bit 1 done), the reward and the env's episode number: 106 bytes.  ctl[0] = n, the pushes since the last clear, advanced ON THE DEVICE by a one-lane kernel
+// behind every push; env_episode[i]: the episode number of env i's newest transition.
+#define CW_REPLAY_CHANGED 0x1u
+#define CW_REPLAY_DONE 0x2u
+struct CwReplay {
+    uint4 *hdr, *pos;                // [steps][n_envs] s
+    uint4 *next_hdr, *next_pos;      // [steps][n_envs] s'
+    uint4 *goal_hdr, *goal_pos;      // [steps][n_envs] the goal record
+    int32_t *reward;                 // [steps][n_envs]
+    uint32_t *episode;               // [steps][n_envs]
+    uint8_t *action, *flags;         // [steps][n_envs]
+    uint32_t *env_episode;           // [n_envs]
+    unsigned long long *ctl;         // [CW_REPLAY_CTL_WORDS]: [0] n
+    int32_t steps;                   // L: a position becomes a slot only through `% steps`
+};
+#define CW_REPLAY_CTL_WORDS 32
+
+// Where cw_replay_sample_kernel leaves a minibatch of B rows (the public cw_replay_out with the records typed).  A null field is not written.
+struct CwReplayOut {
+    uint4 *hdr, *pos, *next_hdr, *next_pos, *goal_hdr, *goal_pos;     // [B]
+    uint8_t *action;
+    int32_t *reward;
+    uint8_t *done;
+    uint16_t *desired;
+    int32_t *env, *slot, *future;
+};
+
 // Where cw_expand_kernel leaves the six successors of M states (the public cw_expand_out with the records typed): every array ACTION-MAJOR, row a * M + j =
 // action a on input state j.  A null field is not written.
 struct CwExpandOut {

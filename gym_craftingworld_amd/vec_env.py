@@ -416,6 +416,8 @@ def shoot_weights(weights, horizon, m):
 
 
 REFIT_FIELDS = ('elites', 'weights', 'elite_min')
+REPLAY_FIELDS = ('hdr', 'slot_pos', 'next_hdr', 'next_slot_pos', 'goal_hdr', 'goal_slot_pos', 'action', 'reward', 'done', 'desired', 'env', 'slot', 'future')
+REPLAY_STRATEGIES = ('future', 'final')
 
 
 def refit_args(ret, elites, horizon, smooth=1, gain=1, env_of=None, num_envs=None):
@@ -1489,6 +1491,89 @@ class CraftingWorldVecEnv:
             out['searched_depth'].fill_(D)
         return dict(out, states=self._seen_ctl[0:1].clone())
 
+    # ------------------------------------------------------------------ replay of packed records
+    def replay_reserve(self, steps):
+        """Allocate (or re-allocate: everything stored is dropped; 0 frees it) the engine's replay buffer of `steps` slots of num_envs transitions, 106
+        bytes a transition, in device memory (cw_replay_reserve; synchronises this engine's work).  steps: 0 .. 2**24 with steps * num_envs < 2**31
+        (ValueError otherwise)."""
+        steps = _shoot_int(steps, 'steps', 0, 2 ** 24)
+        if steps * self.num_envs >= 2 ** 31:
+            raise ValueError('steps * num_envs = %d must stay below 2**31' % (steps * self.num_envs))
+        self._settle()
+        self._replay = None
+        L.check(self._lib.cw_replay_reserve(self._h, steps), 'cw_replay_reserve', self._lib)
+        if steps:
+            tab = L.cw_replay_table()
+            L.check(self._lib.cw_replay_buffers(self._h, C.byref(tab)), 'cw_replay_buffers', self._lib)
+            di, ln = self.device.index, (tab.steps, tab.num_envs)
+            rec = {f: tensor_view(getattr(tab, f), ln + ((16,) if f.endswith('hdr') else (8,)), torch.uint8 if f.endswith('hdr') else torch.int16, di)
+                   for f in ('hdr', 'slot_pos', 'next_hdr', 'next_slot_pos', 'goal_hdr', 'goal_slot_pos')}
+            self._replay = dict(rec, action=tensor_view(tab.action, ln, torch.uint8, di), flags=tensor_view(tab.flags, ln, torch.uint8, di),
+                                reward=tensor_view(tab.reward, ln, torch.int32, di), episode=tensor_view(tab.episode, ln, torch.int32, di),
+                                env_episode=tensor_view(tab.env_episode, ln[1:], torch.int32, di), n=tensor_view(tab.n, (1,), torch.int64, di))
+
+    def replay_bytes(self):
+        """bytes of the replay buffer (0 without one)"""
+        return int(self._lib.cw_replay_bytes(self._h))
+
+    def replay_clear(self):
+        """Forget every stored transition: n = 0, every env's episode number 0 (cw_replay_clear: one kernel, capturable)."""
+        self._call('cw_replay_clear', sync=False)
+
+    def replay_size(self):
+        """n, the pushes since the last clear (0 without a buffer; reading it synchronises).  min(n, steps) positions are stored."""
+        view = getattr(self, '_replay', None)
+        return 0 if view is None else int(view['n'].item())
+
+    def replay_view(self):
+        """The buffer as zero-copy device tensors, READ-ONLY and valid until the next replay_reserve(): 'hdr' uint8 [L, N, 16] / 'slot_pos' int16 [L, N, 8]
+        (the state s), 'next_hdr' / 'next_slot_pos' (s'), 'goal_hdr' / 'goal_slot_pos' (the goal record), 'action' uint8 [L, N] (255: outside 0..5),
+        'flags' uint8 [L, N] (bit 0 changed, bit 1 done), 'reward' int32 [L, N], 'episode' int32 [L, N] (the bit pattern of a uint32), 'env_episode'
+        int32 [N] and 'n' int64 [1].  Position k lives in slot k % L.  CraftingWorldError without a buffer."""
+        view = getattr(self, '_replay', None)
+        if view is None:
+            raise L.CraftingWorldError('no replay buffer reserved (replay_reserve)')
+        return dict(view)
+
+    def replay_push(self, actions):
+        """Store the transition every env is ABOUT to make: call it BEFORE step() / step_async() with the same actions (the same argument handling).  One
+        lane per env reads its state, applies the pure step as expand() does, and writes (s, s', the goal record, action, flags, reward, episode) into
+        slot n % L; n advances on the device (cw_replay_push: two kernels, no host round trip, capturable with the step; nothing of the engine but the
+        buffer is written).  An action outside 0..5 is stored as 255.  The episode number goes up whenever the previous transition of the env was done or
+        its s' is not this push's s byte for byte -- an auto-reset, reset_envs, load_records, snapshot_load, imagine_obs(commit=True) in between.
+        step_many() and rollout() are not recorded."""
+        a, dt = self._actions(actions)
+        self._call('cw_replay_push', a, dt, sync=False)
+
+    def replay_sample(self, batch, seed=0, *, her=0.0, strategy='future', fields=None, out=None):
+        """A minibatch of `batch` rows drawn uniformly from the stored transitions, a fraction of them relabelled in hindsight (cw_replay_sample: one
+        kernel, exact integer arithmetic, no host round trip, capturable; nothing but the outputs is written; include/craftingworld.h states every rule).
+        seed: an int 0 .. 2**64 - 1 or a device word, as shoot() takes it.  her: a float in [0, 1], the probability that a row is relabelled; it goes
+        over as round(her * 65536) and a row is relabelled iff a 16-bit draw lies below that (0.0 never, 1.0 always).  strategy: 'future' -- the new goal
+        is the achieved mask after a uniformly drawn step of the same episode from the row's own on -- or 'final', after the episode's last stored step.
+        -> a dict of device tensors, rows [B]: 'hdr' uint8 [B, 16] / 'slot_pos' int16 [B, 8] (s), 'next_hdr' / 'next_slot_pos' (s'), 'goal_hdr' /
+        'goal_slot_pos' (the goal as a record), 'action' uint8, 'reward' int32, 'done' bool, 'desired' int16 (the goal mask the row is judged by), 'env',
+        'slot' and 'future' int32 (-1: not relabelled) for gathering side data kept in [L, N] tensors.  In a relabelled row the desired bytes of the
+        records, reward and done are those under the new goal.  fields: a subset of REPLAY_FIELDS (default all).  out: a dict returned by an earlier call
+        with the same batch and fields, written again.  With an empty buffer no row is written.  The frames of a sample:
+            obs      = env.render_records(r['hdr'], r['slot_pos'])
+            next_obs = env.render_records(r['next_hdr'], r['next_slot_pos'])
+            goal     = env.render_records(r['goal_hdr'], r['goal_slot_pos'])"""
+        names = _field_names(fields, REPLAY_FIELDS, REPLAY_FIELDS)
+        b = _shoot_int(batch, 'batch', 0, 2 ** 27)
+        if type(her) is bool or not isinstance(her, (int, float, np.integer, np.floating)) or not 0.0 <= her <= 1.0:
+            raise ValueError('her must be a number in [0, 1], got %r' % (her,))
+        if strategy not in REPLAY_STRATEGIES:
+            raise ValueError('strategy must be one of %s, got %r' % (REPLAY_STRATEGIES, strategy))
+        seed, seed_dev = self._shoot_seed(seed)
+        spec = {f: ((b, 16), torch.uint8) if f.endswith('hdr') else ((b, 8), torch.int16) if f.endswith('slot_pos') else
+                ((b,), {'action': torch.uint8, 'done': torch.bool, 'desired': torch.int16}.get(f, torch.int32)) for f in REPLAY_FIELDS}
+        out = self._out_dict(out, names, spec)
+        if b:
+            self._call('cw_replay_sample', b, seed, seed_dev, int(round(float(her) * 65536)), REPLAY_STRATEGIES.index(strategy),
+                       C.byref(_out_struct(L.cw_replay_out, out)), sync=False, keep=out)
+        return out
+
     def step_async(self, actions):
         # the per-step path: a device tensor of the right shape goes to cw_step with nothing built on the way (pointer and stream as plain ints)
         if type(actions) is torch.Tensor and actions.is_cuda:
@@ -1500,6 +1585,16 @@ class CraftingWorldVecEnv:
                     L.check(rc, 'cw_step', self._lib)
                 self._pending = True
                 return
+        actions, dt = self._actions(actions)
+        if type(actions) is torch.Tensor:
+            self._actions_keepalive = actions
+            actions = C.c_void_p(actions.data_ptr())
+        L.check(self._lib.cw_step(self._h, actions, dt, self._stream()), 'cw_step', self._lib)
+        self._pending = True
+
+    def _actions(self, actions):
+        """actions as step_async takes them -> (what cw_step / cw_replay_push is handed, its CW_ACT_* dtype): a contiguous tensor of num_envs actions on the
+        env's device, or -- a host_outputs engine given host actions -- the engine's mapped buffer, filled, as a pointer"""
         if self.host_outputs and not (torch.is_tensor(actions) and actions.is_cuda):
             a = np.asarray(actions).reshape(-1)             # host actions go through the engine's mapped buffer
             if a.size != self.num_envs:
@@ -1507,10 +1602,7 @@ class CraftingWorldVecEnv:
             self._host_actions[:] = a
             if a.dtype != np.int32:                          # (a wider value must not wrap into 0..5: every one outside it is the counted no-op)
                 self._host_actions[(a < 0) | (a > 5)] = -1
-            L.check(self._lib.cw_step(self._h, C.c_void_p(self._host_actions.ctypes.data), L.CW_ACT_I32, self._stream()),
-                    'cw_step', self._lib)
-            self._pending = True
-            return
+            return C.c_void_p(self._host_actions.ctypes.data), L.CW_ACT_I32
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions), device=self.device)
         if actions.device != self.device:
@@ -1520,10 +1612,7 @@ class CraftingWorldVecEnv:
         actions = actions.contiguous()
         if actions.numel() != self.num_envs:
             raise ValueError('expected %d actions, got %d' % (self.num_envs, actions.numel()))
-        self._actions_keepalive = actions
-        L.check(self._lib.cw_step(self._h, C.c_void_p(actions.data_ptr()), _ACT_DTYPES[actions.dtype], self._stream()),
-                'cw_step', self._lib)
-        self._pending = True
+        return actions, _ACT_DTYPES[actions.dtype]
 
     def step_wait(self):
         if not self._pending:

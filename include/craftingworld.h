@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; then cw_refit_out, cw_shoot_refit; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; then cw_refit_out, cw_shoot_refit; then cw_replay_table, cw_replay_out, cw_replay_reserve, cw_replay_bytes, cw_replay_buffers, cw_replay_clear, cw_replay_push, cw_replay_sample; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -610,6 +610,114 @@ int cw_reach(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const u
  *   misaligned hdr / slot_pos (16 bytes) or src (4 bytes), the overlaps above.  (65 536 envs at 21x21: 20 us state-only, 0.33 ms with the dirty-cell frames repainted; 13 us for 219 selected envs:
  *   tools/measure_load_records.py, profiles/r13_load_records.txt.) */
 int cw_load_records(cw_engine *e, const int32_t *src, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_records, uint8_t *status, cw_stream_t stream);
+
+/* --- the learner's side of the record family: a device-resident REPLAY BUFFER of transitions kept as packed records, and minibatches drawn from it with
+ * hindsight relabelling (HER), without a host round trip.  A transition is (s, s', the episode's goal) as three 32-byte records plus action, flags, reward and
+ * an episode number: 106 bytes, where the three frames of a 21x21 pixel transition are 63 KB; cw_render_records paints the frames of a minibatch when it is drawn.
+ * Everything below is exact integer arithmetic and a function of the inputs alone, never of scheduling.  cw_replay_push is called BEFORE cw_step with the same
+ * actions; cw_step_many and cw_rollout are NOT recorded (out of scope).
+ *
+ * THE BUFFER: L = steps slots of N = num_envs transitions, time-major [L][N] (slot t of env i at index t * N + i).  Per slot and env: hdr [16] / slot_pos [8] (the
+ *   state s), next_hdr / next_slot_pos (the successor s'), goal_hdr / goal_slot_pos (the goal record), action uint8, flags uint8 (bit 0 changed, bit 1 done),
+ *   reward int32, episode uint32.  A control block holds uint64 n, the pushes since the last clear, and per env the episode number of its newest transition.
+ *   POSITION k = 0, 1, ... is the k-th push since the last clear; it lives in slot k % L; positions lo .. n - 1 are stored, lo = max(0, n - L).
+ * cw_replay_reserve: ONE allocation of cw_replay_bytes() bytes, made as cw_seen_reserve and cw_snapshot_reserve make theirs; synchronous, waits for this engine's own
+ *   work only.  The new buffer is zero-filled and cleared (n = 0) before the call returns; steps == 0 frees it; CW_ERR_HIP leaves the engine WITHOUT a buffer.  Freed
+ *   by cw_destroy.  Not part of a checkpoint blob or a snapshot row; left alone by cw_reset, cw_checkpoint_load and cw_seed_*.  CW_ERR_INVALID: a null engine, steps
+ *   outside 0 .. 2^24, steps * num_envs >= 2^31.  Offsets are 64-bit throughout.
+ * cw_replay_buffers: the device arrays, zero-copy, READ-ONLY for callers and valid until the next cw_replay_reserve; CW_ERR_STATE without a buffer.
+ * cw_replay_clear: n = 0 and every env's episode number 0 (ONE kernel, capturable); the slots' bytes stay and are unreachable.  CW_ERR_STATE before the first
+ *   cw_reset / cw_checkpoint_load and without a buffer.
+ *
+ * cw_replay_push: one lane per env i (cw_replay_push_kernel).  actions and action_dtype exactly as cw_step takes them, host_actions of a host_outputs engine included.
+ *   s = the env's current hdr / slot_pos.  (s', reward, done, changed) = the pure step of s under the action exactly as cw_expand computes it, with the env's own
+ *   start positions.  An action id outside 0..5 is cw_step's state-preserving no-op (step_num += 1, reward -1, changed 0); it is stored as 255 and NOT counted
+ *   anywhere.  The transition is written to slot n % L.
+ *   THE GOAL RECORD of env i: bytes 0-1 the row and column of the goal state's agent cell, byte 2 (hold) 0, byte 3 the env's menu id, bytes 4-5 (achieved) =
+ *   bytes 6-7 (desired) = the env's desired mask, bytes 8-11 (step_num, flags) 0, bytes 12-15 the goal state's slot codes; goal_slot_pos the goal state's slot
+ *   positions.  Its cw_render_records frame is the env's desired_goal frame.
+ *   PURE with respect to the engine: nothing but the buffer is written -- no state, stream, look-ahead ring, counter (counters[3] included), output array or frame.
+ *   THE EPISODE RULE is a function of what was pushed, with no hook into any reset, load or restore call.  The transition of push k for env i CONTINUES the episode
+ *   of push k - 1 iff that transition was not done AND its next_hdr / next_slot_pos equal this push's hdr / slot_pos in all 32 bytes; otherwise the env's episode
+ *   number goes up by one.  The first push after a clear starts episode 0.  The predecessor is read before the slot is written, so steps == 1 is legal.
+ *   Consequences: an auto-reset, cw_reset_masked, cw_load_records, cw_snapshot_load or cw_imagine_masked(commit) between two pushes starts a new episode, because
+ *   the bytes differ (a load of the very bytes s' continues it); on an engine without auto-reset a finished env that keeps stepping yields episodes of length 1.
+ *   Episode numbers never decrease along an env's positions; they are uint32 and only ever compared for equality.
+ *   n lives on the device and advances there AFTER the push's stores, by a kernel boundary (a second, one-lane launch) -- never by a lane or workgroup waiting for
+ *   another -- so a replayed graph pushes into the next slot each time.  Enqueues TWO kernels; no host synchronisation, no allocation; capturable with cw_step.
+ *   CW_ERR_STATE before the first cw_reset / cw_checkpoint_load and without a buffer; otherwise the argument rules of cw_step (CW_ERR_INVALID: a null engine or
+ *   actions, a bad dtype).
+ *
+ * cw_replay_sample: B = n_rows rows, one minibatch (cw_replay_sample_kernel: one lane per row, grid-stride).  s = seed + (seed_dev ? *seed_dev : 0) mod 2^64, as
+ *   cw_shoot; draw and mulhi32 are THE DRAW of cw_shoot, draw(s, state, sample, step).  The kernel reads n from the device, so the call is capturable.
+ *   lo = max(0, n - L), V = n - lo.  For n == 0 NO row is written.  For row b:
+ *     env       i = mulhi32(draw(s, b, 0, 0), N);
+ *     position  p = lo + mulhi32(draw(s, b, 1, 0), V)      -- together uniform over the stored transitions;
+ *     the row is RELABELLED iff (draw(s, b, 2, 0) >> 16) < her; her is 0 .. 65 536: 0 never, 65 536 always;
+ *     e = the last position in [p, n) whose stored episode number for env i equals that of p (a binary search, at most 24 loads, no back-pointers);
+ *     strategy 0 (future): f = p + mulhi32(draw(s, b, 3, 0), e - p + 1);  strategy 1 (final): f = e;
+ *     the relabelled goal g = the achieved mask of the stored next_hdr at (f, i), bytes 4-5.
+ *   Outputs (cw_replay_out; DEVICE pointers [B]; a NULL field is not written, all NULL is CW_ERR_INVALID; the record fields 16-byte, reward / env / slot / future
+ *   4-byte, desired 2-byte aligned; no output may overlap another):
+ *     hdr, slot_pos            the stored s at (p, i); in a relabelled row bytes 6-7 of hdr are g.
+ *     next_hdr, next_slot_pos  the stored s'; the same rule for bytes 6-7.
+ *     goal_hdr, goal_slot_pos  not relabelled: the stored goal record.  Relabelled: the stored s' record at (f, i) with bytes 6-7 = g.  Its achieved equals its
+ *                              desired equals the row's `desired` in both cases; its frame is the achieved-goal image HER uses.
+ *     action                   the stored action (255: outside 0..5).
+ *     reward, done             not relabelled: as stored.  Relabelled: reward = -1 unless the stored changed bit is set; if it is set, reward = max_steps iff the
+ *                              reward rule holds of a' = the achieved mask of the stored s' (bytes 4-5) and g under the engine's task mask, the rule named by bit 1
+ *                              of the stored s' record's flag word (byte 10): clear, EQUAL: a' == g; set, SUBSET: (g & ~a') == 0 and some position equal, i.e.
+ *                              (~(g ^ a') & task mask) != 0 -- cw_step's own expressions.  done = (step_num of the stored s', bytes 8-9, >= max_steps) or
+ *                              reward == max_steps.
+ *     desired                  g, or the stored mask (bytes 6-7 of the stored hdr).
+ *     env, slot, future        i, p % L, and f % L (-1 when not relabelled): with these a caller gathers side data of its own kept in [L][N] tensors.
+ *   Every other byte of the records is the stored one: the success count in flag bits 2-15 stays the episode's AS PLAYED, step_num and the slot data likewise.
+ *   PURE: reads the buffer, writes the outputs, nothing else.  ONE kernel, no atomics, no host synchronisation, no allocation; every obs_mode, host_outputs engines
+ *   included.  n_rows == 0: CW_OK, nothing enqueued.  CW_ERR_INVALID, tested in this order: a null engine or out; n_rows < 0 or above 2^27; her above 65 536; a
+ *   strategy other than 0 or 1; every field NULL; a misaligned field; two fields sharing a byte.  Then CW_ERR_STATE before the first cw_reset / cw_checkpoint_load
+ *   and without a buffer.
+ *   (21x21, L = 256, launch included, 4 096 / 65 536 envs: a push 14 / 14 us beside 9 / 10 us for the state-only cw_step it precedes; a sample at her = 52 429 of
+ *   4 096 rows 21 us and of 65 536 rows 30 - 34 us, against 620 - 640 us for the same minibatch assembled in torch from the table (randint, index gathers, the
+ *   episode end from the episode column, compute_reward_batch); with three cw_render_records calls 75 us against 0.71 ms and 0.83 - 0.85 against 1.46 ms: no shape
+ *   measured is slower than the torch route.  tools/measure_replay.py, profiles/r15_replay.txt.) */
+typedef struct cw_replay_table {   /* DEVICE pointers into the buffer, [steps][num_envs] unless noted */
+    const uint8_t  *hdr;            /* [..][16] */
+    const uint16_t *slot_pos;       /* [..][8]  */
+    const uint8_t  *next_hdr;
+    const uint16_t *next_slot_pos;
+    const uint8_t  *goal_hdr;
+    const uint16_t *goal_slot_pos;
+    const uint8_t  *action;
+    const uint8_t  *flags;
+    const int32_t  *reward;
+    const uint32_t *episode;
+    const uint32_t *env_episode;    /* [num_envs] the episode number of each env's newest transition */
+    const uint64_t *n;              /* [1] the pushes since the last clear */
+    int32_t steps;
+    int32_t num_envs;
+} cw_replay_table;
+typedef struct cw_replay_out {     /* DEVICE pointers [B]; a NULL field is not written; all NULL: CW_ERR_INVALID */
+    uint8_t  *hdr;                  /* [B][16], 16-byte aligned like the five record fields below */
+    uint16_t *slot_pos;             /* [B][8] */
+    uint8_t  *next_hdr;
+    uint16_t *next_slot_pos;
+    uint8_t  *goal_hdr;
+    uint16_t *goal_slot_pos;
+    uint8_t  *action;
+    int32_t  *reward;
+    uint8_t  *done;
+    uint16_t *desired;
+    int32_t  *env;
+    int32_t  *slot;
+    int32_t  *future;
+} cw_replay_out;
+int cw_replay_reserve(cw_engine *e, int32_t steps);
+size_t cw_replay_bytes(const cw_engine *e);                      /* 0 without a buffer */
+int cw_replay_buffers(cw_engine *e, cw_replay_table *out);
+int cw_replay_clear(cw_engine *e, cw_stream_t stream);
+int cw_replay_push(cw_engine *e, const void *actions, int action_dtype, cw_stream_t stream);
+int cw_replay_sample(cw_engine *e, int32_t n_rows, uint64_t seed, const uint64_t *seed_dev, uint32_t her, int32_t strategy,
+                     const cw_replay_out *out, cw_stream_t stream);
 
 /* --- step(action) for every env (ray.py:301-378) + auto-reset of finished envs --------------
  * actions: DEVICE pointer to N actions of dtype CW_ACT_*, values 0..5 = Up,Right,Down,Left,
