@@ -190,6 +190,11 @@ class cwh_tuning(C.Structure):
               [(f, C.c_double) for f in ('head_notch', 'busy_notch', 'period_ns', 'rate_tbs')]
 
 
+class cwh_span(C.Structure):
+    """what a call reads or writes through one pointer (csrc/cw_host.h: cwh_spans_misaligned, cwh_spans_clash); at 0: not given"""
+    _fields_ = [('at', C.c_uint64), ('bytes', C.c_uint64), ('align', C.c_uint64)]
+
+
 cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variable's text or None (a pointer: ctypes cannot return a char* a callback made)
 
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
@@ -205,6 +210,7 @@ CWH_REFIT_BLOCKS_PER_CU = 8
 CWH_SEEN_OK, CWH_SEEN_NO_RECORDS, CWH_SEEN_NO_FIELD, CWH_SEEN_N_STATES, CWH_SEEN_ALIGN, CWH_SEEN_OVERLAP = range(6)
 CWH_SEEN_KEY_WORDS, CWH_SEEN_MAX_CAPACITY, CWH_SEEN_PROBES = 9, 1 << 28, 128
 CWH_SEEN_ROW_BITS, CWH_SEEN_MAX_EPOCH = 28, (1 << 36) - 2
+CWH_SEEN_SECTIONS, CWH_SEEN_CTL_BYTES = 5, 256
 CWH_REACH_OK, CWH_REACH_NO_FIELD, CWH_REACH_N_STATES, CWH_REACH_DEPTH, CWH_REACH_PAIR, CWH_REACH_ENV_OF, CWH_REACH_OWN_STATES, CWH_REACH_ALIGN, \
     CWH_REACH_OVERLAP = range(9)
 CWH_REACH_CHUNK, CWH_REACH_MAX_ROWS, CWH_REACH_MAX_DEPTH, CWH_REACH_BLOCKS_PER_CU, CWH_REACH_SECTIONS = 4096, (2 ** 28 - 1) // 6 - 63, 32767, 8, 18
@@ -267,6 +273,10 @@ HOST_HELPERS = {
     'cwh_reach_args': (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                  C.c_uint64]),
     'cwh_ranges_overlap': (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    'cwh_spans_misaligned': (C.c_int, [C.POINTER(cwh_span), C.c_int]),
+    'cwh_spans_clash': (C.c_int, [C.POINTER(cwh_span), C.c_int, C.POINTER(cwh_span), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    'cwh_sections_layout': (C.c_uint64, [C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    'cwh_seen_layout': (C.c_int64, [C.c_int64, _VP]),
     'cwh_guard_init': (None, [C.POINTER(cwh_guard), C.c_double]),
     'cwh_guard_step': (C.c_int, [C.POINTER(cwh_guard), C.c_double, C.c_double]),
     'cwh_sweep_periods': (None, [C.c_double, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

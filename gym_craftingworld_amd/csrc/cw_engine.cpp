@@ -102,6 +102,32 @@ struct DeviceGuard {
     }
 };
 
+// A REGION: one device allocation of the engine's outside every checkpoint blob and snapshot row, cut into sections by a cwh_*_layout of cw_host.cpp -- the
+// snapshot bank, the visited set, the reach workspace, the replay buffer.  Its reserve is synchronous: the old region goes first (0 rows / slots / steps:
+// that is all), then a NewRegion holds the allocation while it is cleared and frees it again unless the reserve commits it to the engine.
+struct Region {
+    void *base = nullptr;              // null: none reserved
+    size_t bytes = 0;
+    explicit operator bool() const { return base != nullptr; }
+};
+static void region_free(Region &r)
+{
+    if (r.base) (void)hipFree(r.base);
+    r = Region{};
+}
+struct NewRegion {
+    Region r;
+    bool alloc(size_t bytes)           // false: no device memory (the error is the caller's to word)
+    {
+        if (hipMalloc(&r.base, bytes) != hipSuccess) { (void)hipGetLastError(); r.base = nullptr; return false; }
+        r.bytes = bytes;
+        return true;
+    }
+    char *at(uint64_t offset) const { return (char *)r.base + offset; }
+    Region commit() { const Region out = r; r = Region{}; return out; }
+    ~NewRegion() { region_free(r); }
+};
+
 struct cw_engine {
     int device = 0;
     int obs_mode = 0;
@@ -114,18 +140,16 @@ struct cw_engine {
     int32_t *host_actions = nullptr;
     std::vector<CwMenuDev> menus;
     uint32_t *seed_scratch = nullptr;  // [N] device: seeds of cw_seed_int
-    void *bank = nullptr;              // the snapshot bank's one allocation (cw_snapshot_reserve), or null: none reserved
+    Region bank;                       // the snapshot bank (cw_snapshot_reserve), or none reserved
     CwBank B{};                        // ... its sections (cw_host.cpp: cwh_snapshot_section_bytes)
     size_t bank_row_bytes = 0;
-    void *seen = nullptr;              // the visited set's one allocation (cw_seen_reserve), or null: none reserved
-    CwSeen Sn{};                       // ... its arrays (cw_layout.h)
+    Region seen;                       // the visited set (cw_seen_reserve)
+    CwSeen Sn{};                       // ... its arrays (cw_host.cpp: cwh_seen_layout)
     int64_t seen_slots = 0;
-    void *reach = nullptr;             // cw_reach's workspace, one allocation (cw_reach_reserve), or null: none reserved
+    Region reach;                      // cw_reach's workspace (cw_reach_reserve)
     CwReach Rc{};                      // ... its sections (cw_host.cpp: cwh_reach_layout)
-    size_t reach_bytes = 0;
-    void *replay = nullptr;            // the replay buffer's one allocation (cw_replay_reserve), or null: none reserved
+    Region replay;                     // the replay buffer (cw_replay_reserve)
     CwReplay Rp{};                     // ... its sections (cw_host.cpp: cwh_replay_layout)
-    size_t replay_bytes = 0;
     int n = 0, S = 0, ncell = 0, K = 0;
     // resident stepper of the single-env loop (cw_step_resident; cw_kernels.hip: cw_resident_kernel)
     CwResident *res = nullptr;         // pinned coherent host memory, or null (engine not eligible)
@@ -682,10 +706,7 @@ int cw_destroy(cw_engine *e)
     if (e->last_work) (void)hipEventDestroy(e->last_work);
     for (auto &smp : e->guard_ring) for (hipEvent_t ev : smp.ev) if (ev) (void)hipEventDestroy(ev);
     for (void *p : e->allocs) (void)hipFree(p);
-    if (e->bank) (void)hipFree(e->bank);
-    if (e->seen) (void)hipFree(e->seen);
-    if (e->reach) (void)hipFree(e->reach);
-    if (e->replay) (void)hipFree(e->replay);
+    for (Region *r : {&e->bank, &e->seen, &e->reach, &e->replay}) region_free(*r);
     for (void *p : e->host_allocs) (void)hipHostFree(p);
     delete e;
     return CW_OK;
@@ -843,49 +864,39 @@ int cw_sample_state_masked(cw_engine *e, const uint8_t *mask, int32_t pooled, ui
 }
 
 // ------------------------------------------------------------------------------ snapshot bank
-// The bank is one allocation of the engine's, outside every checkpoint blob; cw_checkpoint_load, cw_seed_* and cw_generate_fixed_states leave it alone (a row
+// The bank is a Region of the engine's, outside every checkpoint blob; cw_checkpoint_load, cw_seed_* and cw_generate_fixed_states leave it alone (a row
 // is self-contained: it carries its own stream, ring and pool row).  Re-allocating drops every saved row: the new bank's valid bytes are zero.
-static void bank_free(cw_engine *e)
-{
-    if (e->bank) (void)hipFree(e->bank);
-    e->bank = nullptr;
-    e->B = CwBank{};
-    e->bank_row_bytes = 0;
-}
-
 int cw_snapshot_reserve(cw_engine *e, int32_t rows)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: null engine");
     if (rows < 0) return fail(CW_ERR_INVALID, "cw_snapshot_reserve: rows = %d must be >= 0", rows);
     SyncEntry in(e);                                 // (the engine's own work: a save or load in flight uses the bank about to go)
     if (in.rc != CW_OK) return in.rc;
-    bank_free(e);
+    region_free(e->bank);
+    e->B = CwBank{};
+    e->bank_row_bytes = 0;
     if (rows == 0) return CW_OK;
     size_t bytes[CWH_SNAP_SECTIONS], at[CWH_SNAP_SECTIONS];
     uint64_t total = 0, row_bytes = 0;
     cwh_snapshot_section_bytes(rows, e->K, e->P.lookahead ? CW_LA_DEPTH : 0, bytes, at, &total, &row_bytes);
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)total) != hipSuccess) {
-        (void)hipGetLastError();
+    NewRegion nr;
+    if (!nr.alloc((size_t)total))
         return fail(CW_ERR_HIP, "cw_snapshot_reserve: no device memory for %d rows of %llu bytes", rows, (unsigned long long)row_bytes);
-    }
-    if (hipMemsetAsync((char *)p + at[CWH_SNAP_VALID], 0, bytes[CWH_SNAP_VALID], e->aux) != hipSuccess || hipStreamSynchronize(e->aux) != hipSuccess) {
+    if (hipMemsetAsync(nr.at(at[CWH_SNAP_VALID]), 0, bytes[CWH_SNAP_VALID], e->aux) != hipSuccess || hipStreamSynchronize(e->aux) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(p);
         return fail(CW_ERR_HIP, "cw_snapshot_reserve: clearing the valid bytes failed");
     }
-    char *const b = (char *)p;
     CwBank &B = e->B;
-    B.hdr = (uint4 *)(b + at[CWH_SNAP_HDR]); B.pos = (uint4 *)(b + at[CWH_SNAP_POS]);
-    B.init_pos = (uint4 *)(b + at[CWH_SNAP_INIT_POS]); B.goal_pos = (uint4 *)(b + at[CWH_SNAP_GOAL_POS]);
-    B.goal_codes = (uint32_t *)(b + at[CWH_SNAP_GOAL_CODES]); B.ep_no = (int32_t *)(b + at[CWH_SNAP_EP_NO]);
-    B.init_agent = (uint16_t *)(b + at[CWH_SNAP_INIT_AGENT]); B.goal_agent = (uint16_t *)(b + at[CWH_SNAP_GOAL_AGENT]);
-    B.mt = (uint32_t *)(b + at[CWH_SNAP_MT]); B.mt_idx = (int32_t *)(b + at[CWH_SNAP_MT_IDX]);
-    B.nx_init_pos = (uint4 *)(b + at[CWH_SNAP_NX_INIT_POS]); B.nx_goal_pos = (uint4 *)(b + at[CWH_SNAP_NX_GOAL_POS]);
-    B.nx_misc = (uint4 *)(b + at[CWH_SNAP_NX_MISC]); B.nx_ctl = (uint32_t *)(b + at[CWH_SNAP_NX_CTL]);
-    B.pool = (uint16_t *)(b + at[CWH_SNAP_POOL]); B.valid = (uint8_t *)(b + at[CWH_SNAP_VALID]);
+    B.hdr = (uint4 *)nr.at(at[CWH_SNAP_HDR]); B.pos = (uint4 *)nr.at(at[CWH_SNAP_POS]);
+    B.init_pos = (uint4 *)nr.at(at[CWH_SNAP_INIT_POS]); B.goal_pos = (uint4 *)nr.at(at[CWH_SNAP_GOAL_POS]);
+    B.goal_codes = (uint32_t *)nr.at(at[CWH_SNAP_GOAL_CODES]); B.ep_no = (int32_t *)nr.at(at[CWH_SNAP_EP_NO]);
+    B.init_agent = (uint16_t *)nr.at(at[CWH_SNAP_INIT_AGENT]); B.goal_agent = (uint16_t *)nr.at(at[CWH_SNAP_GOAL_AGENT]);
+    B.mt = (uint32_t *)nr.at(at[CWH_SNAP_MT]); B.mt_idx = (int32_t *)nr.at(at[CWH_SNAP_MT_IDX]);
+    B.nx_init_pos = (uint4 *)nr.at(at[CWH_SNAP_NX_INIT_POS]); B.nx_goal_pos = (uint4 *)nr.at(at[CWH_SNAP_NX_GOAL_POS]);
+    B.nx_misc = (uint4 *)nr.at(at[CWH_SNAP_NX_MISC]); B.nx_ctl = (uint32_t *)nr.at(at[CWH_SNAP_NX_CTL]);
+    B.pool = (uint16_t *)nr.at(at[CWH_SNAP_POOL]); B.valid = (uint8_t *)nr.at(at[CWH_SNAP_VALID]);
     B.rows = rows;
-    e->bank = p;
+    e->bank = nr.commit();
     e->bank_row_bytes = (size_t)row_bytes;
     return CW_OK;
 }
@@ -920,16 +931,12 @@ int cw_snapshot_load(cw_engine *e, const int32_t *rows, int32_t with_stream, cw_
 }
 
 // ------------------------------------------------------------------------------ expand: the six successors of every state
+// a pointer as the integer the HIP-free rules of cw_host.cpp take (0: null)
+static uint64_t addr(const void *p) { return (uint64_t)(uintptr_t)p; }
 // a record array is read and written 16 bytes at a time (null: not given)
 static int aligned16(const void *p, const char *what, const char *who)
 {
-    return ((uintptr_t)p & 15u) == 0 ? CW_OK : fail(CW_ERR_INVALID, "%s: %s is not 16-byte aligned", who, what);
-}
-// [out, out + out_bytes) shares a byte with the header or the slot records a kernel reads (rec_bytes each)
-static bool overlaps_records(const void *out, uint64_t out_bytes, const void *hdr, const void *pos, uint64_t rec_bytes)
-{
-    return cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)hdr, rec_bytes) ||
-           cwh_ranges_overlap((uint64_t)(uintptr_t)out, out_bytes, (uint64_t)(uintptr_t)pos, rec_bytes);
+    return (addr(p) & 15u) == 0 ? CW_OK : fail(CW_ERR_INVALID, "%s: %s is not 16-byte aligned", who, what);
 }
 // What cw_expand (max_steps 0: no steps, its own states once), cw_plan (the same, depth already checked) and cw_simulate (its own states broadcast) check alike: the HIP-free rules of cw_host.cpp
 // (cwh_records_args, tested on the CPU) as the caller's error text, then the alignment of the records in and out.
@@ -993,10 +1000,9 @@ int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, cons
     // the records the kernel reads: the caller's n_states, or the engine's own num_envs
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     const uint64_t in_bytes = 16ull * (uint64_t)(hdr_in ? n_states : e->n), out_bytes = 16ull * (uint64_t)n_states;
-    const void *const outs[2] = {out->hdr, out->slot_pos};
-    for (int k = 0; k < 2; k++)
-        if (outs[k] && overlaps_records(outs[k], out_bytes, h, p, in_bytes))
-            return fail(CW_ERR_INVALID, "cw_simulate: out->%s overlaps the records read", k ? "slot_pos" : "hdr");
+    const cwh_span outs[2] = {{addr(out->hdr), out_bytes, 16}, {addr(out->slot_pos), out_bytes, 16}}, ins[2] = {{addr(h), in_bytes, 16}, {addr(p), in_bytes, 16}};
+    const int clash = cwh_spans_clash(outs, 2, ins, 2, 0, nullptr);
+    if (clash >= 0) return fail(CW_ERR_INVALID, "cw_simulate: out->%s overlaps the records read", clash ? "slot_pos" : "hdr");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_simulate called before cw_reset");
     if (n_states == 0) return CW_OK;
     EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
@@ -1054,14 +1060,13 @@ int cw_shoot(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const u
     if (bad != CW_OK) return bad;
     const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
     const uint64_t m = (uint64_t)n_states, rec_bytes = 16ull * m, w_bytes = weights ? 12ull * (uint64_t)n_steps * m : 0;
-    const struct { const void *at; uint64_t bytes; const char *name; } outs[4] = {
-        {out->hdr, rec_bytes, "hdr"}, {out->slot_pos, rec_bytes, "slot_pos"}, {out->plan, (uint64_t)n_steps * m, "plan"}, {out->ret, 4ull * (uint64_t)n_samples * m, "ret"}};
-    for (int k = 0; k < 4; k++) {
-        if (!outs[k].at) continue;
-        if (overlaps_records(outs[k].at, outs[k].bytes, h, p, rec_bytes)) return fail(CW_ERR_INVALID, "cw_shoot: out->%s overlaps the records read", outs[k].name);
-        if (cwh_ranges_overlap((uint64_t)(uintptr_t)outs[k].at, outs[k].bytes, (uint64_t)(uintptr_t)weights, w_bytes))
-            return fail(CW_ERR_INVALID, "cw_shoot: out->%s overlaps the weights", outs[k].name);
-    }
+    static const char *const names[4] = {"hdr", "slot_pos", "plan", "ret"};
+    const cwh_span outs[4] = {{addr(out->hdr), rec_bytes, 16}, {addr(out->slot_pos), rec_bytes, 16}, {addr(out->plan), (uint64_t)n_steps * m, 1},
+                              {addr(out->ret), 4ull * (uint64_t)n_samples * m, 4}};
+    const cwh_span ins[3] = {{addr(h), rec_bytes, 16}, {addr(p), rec_bytes, 16}, {addr(weights), w_bytes, 2}};
+    int other = 0;
+    const int clash = cwh_spans_clash(outs, 4, ins, 3, 0, &other);
+    if (clash >= 0) return fail(CW_ERR_INVALID, "cw_shoot: out->%s overlaps the %s", names[clash], other < 2 ? "records read" : "weights");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_shoot called before cw_reset");
     if (n_states == 0) return CW_OK;
     EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
@@ -1103,9 +1108,8 @@ int cw_shoot_refit(cw_engine *e, const int32_t *env_of, int32_t n_states, int32_
                    cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_shoot_refit: null %s", !e ? "engine" : "out");
-    const auto at = [](const void *p) { return (uint64_t)(uintptr_t)p; };
-    switch (cwh_refit_args(at(env_of), n_states, n_steps, n_samples, n_elites, at(weights_in), at(ret), smooth, gain, at(out->elites), at(out->weights),
-                           at(out->elite_min))) {
+    switch (cwh_refit_args(addr(env_of), n_states, n_steps, n_samples, n_elites, addr(weights_in), addr(ret), smooth, gain, addr(out->elites), addr(out->weights),
+                           addr(out->elite_min))) {
     case CWH_REFIT_OK: break;
     case CWH_REFIT_NULL: return fail(CW_ERR_INVALID, "cw_shoot_refit: null %s", !ret ? "ret" : "out->elites");
     case CWH_REFIT_N_STATES: return fail(CW_ERR_INVALID, "cw_shoot_refit: n_states = %d must be 0 .. %d", n_states, CWH_MAX_STATES);
@@ -1131,16 +1135,8 @@ int cw_shoot_refit(cw_engine *e, const int32_t *env_of, int32_t n_states, int32_
 }
 
 // ------------------------------------------------------------------------------ replay: transitions as packed records, relabelled minibatches
-// One allocation of the engine's, like the snapshot bank and the visited set and as far from every checkpoint blob and snapshot row; its sections are
-// cw_host.cpp's (cwh_replay_layout).  A reserve drops everything stored: the new buffer is zero-filled and cleared before the call returns.
-static void replay_free(cw_engine *e)
-{
-    if (e->replay) (void)hipFree(e->replay);
-    e->replay = nullptr;
-    e->Rp = CwReplay{};
-    e->replay_bytes = 0;
-}
-
+// A Region of the engine's, as far from every checkpoint blob and snapshot row as the others; its sections are cw_host.cpp's (cwh_replay_layout).
+// A reserve drops everything stored: the new buffer is zero-filled and cleared before the call returns.
 int cw_replay_reserve(cw_engine *e, int32_t steps)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_replay_reserve: null engine");
@@ -1150,44 +1146,40 @@ int cw_replay_reserve(cw_engine *e, int32_t steps)
         return fail(CW_ERR_INVALID, "cw_replay_reserve: steps = %d must be 0 .. %d with steps * num_envs (%d) below 2^31", steps, CWH_REPLAY_MAX_STEPS, e->n);
     SyncEntry in(e);                                 // (the engine's own work: a push or a sample in flight uses the buffer about to go)
     if (in.rc != CW_OK) return in.rc;
-    replay_free(e);
+    region_free(e->replay);
+    e->Rp = CwReplay{};
     if (steps == 0) return CW_OK;
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    NewRegion nr;
+    if (!nr.alloc((size_t)bytes))
         return fail(CW_ERR_HIP, "cw_replay_reserve: no device memory for %d steps of %d envs (%lld bytes)", steps, e->n, (long long)bytes);
-    }
-    char *const b = (char *)p;
     CwReplay R{};
-    R.ctl = (unsigned long long *)(b + at[CWH_REPLAY_S_CTL]);
-    R.env_episode = (uint32_t *)(b + at[CWH_REPLAY_S_ENV_EPISODE]);
-    R.hdr = (uint4 *)(b + at[CWH_REPLAY_S_HDR]);
-    R.pos = (uint4 *)(b + at[CWH_REPLAY_S_POS]);
-    R.next_hdr = (uint4 *)(b + at[CWH_REPLAY_S_NEXT_HDR]);
-    R.next_pos = (uint4 *)(b + at[CWH_REPLAY_S_NEXT_POS]);
-    R.goal_hdr = (uint4 *)(b + at[CWH_REPLAY_S_GOAL_HDR]);
-    R.goal_pos = (uint4 *)(b + at[CWH_REPLAY_S_GOAL_POS]);
-    R.reward = (int32_t *)(b + at[CWH_REPLAY_S_REWARD]);
-    R.episode = (uint32_t *)(b + at[CWH_REPLAY_S_EPISODE]);
-    R.action = (uint8_t *)(b + at[CWH_REPLAY_S_ACTION]);
-    R.flags = (uint8_t *)(b + at[CWH_REPLAY_S_FLAGS]);
+    R.ctl = (unsigned long long *)nr.at(at[CWH_REPLAY_S_CTL]);
+    R.env_episode = (uint32_t *)nr.at(at[CWH_REPLAY_S_ENV_EPISODE]);
+    R.hdr = (uint4 *)nr.at(at[CWH_REPLAY_S_HDR]);
+    R.pos = (uint4 *)nr.at(at[CWH_REPLAY_S_POS]);
+    R.next_hdr = (uint4 *)nr.at(at[CWH_REPLAY_S_NEXT_HDR]);
+    R.next_pos = (uint4 *)nr.at(at[CWH_REPLAY_S_NEXT_POS]);
+    R.goal_hdr = (uint4 *)nr.at(at[CWH_REPLAY_S_GOAL_HDR]);
+    R.goal_pos = (uint4 *)nr.at(at[CWH_REPLAY_S_GOAL_POS]);
+    R.reward = (int32_t *)nr.at(at[CWH_REPLAY_S_REWARD]);
+    R.episode = (uint32_t *)nr.at(at[CWH_REPLAY_S_EPISODE]);
+    R.action = (uint8_t *)nr.at(at[CWH_REPLAY_S_ACTION]);
+    R.flags = (uint8_t *)nr.at(at[CWH_REPLAY_S_FLAGS]);
     R.steps = steps;
-    if (hipMemsetAsync(p, 0, (size_t)bytes, e->aux) != hipSuccess || cwk_launch_replay_clear(&e->P, &e->tune, &R, e->aux) != hipSuccess ||
+    if (hipMemsetAsync(nr.r.base, 0, nr.r.bytes, e->aux) != hipSuccess || cwk_launch_replay_clear(&e->P, &e->tune, &R, e->aux) != hipSuccess ||
         hipStreamSynchronize(e->aux) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(p);
         return fail(CW_ERR_HIP, "cw_replay_reserve: clearing the buffer failed");
     }
-    e->replay = p;
+    e->replay = nr.commit();
     e->Rp = R;
-    e->replay_bytes = (size_t)bytes;
     return CW_OK;
 }
 
 size_t cw_replay_bytes(const cw_engine *e)
 {
     if (!e) { (void)fail(CW_ERR_INVALID, "cw_replay_bytes: null engine"); return 0; }
-    return e->replay ? e->replay_bytes : 0;
+    return e->replay.bytes;
 }
 
 int cw_replay_buffers(cw_engine *e, cw_replay_table *out)
@@ -1242,10 +1234,9 @@ int cw_replay_sample(cw_engine *e, int32_t n_rows, uint64_t seed, const uint64_t
                      cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_replay_sample: null %s", !e ? "engine" : "out");
-    const auto at = [](const void *p) { return (uint64_t)(uintptr_t)p; };
-    const uint64_t fields[CWH_REPLAY_FIELDS] = {at(out->hdr), at(out->slot_pos), at(out->next_hdr), at(out->next_slot_pos), at(out->goal_hdr),
-                                                at(out->goal_slot_pos), at(out->action), at(out->reward), at(out->done), at(out->desired), at(out->env),
-                                                at(out->slot), at(out->future)};
+    const uint64_t fields[CWH_REPLAY_FIELDS] = {addr(out->hdr), addr(out->slot_pos), addr(out->next_hdr), addr(out->next_slot_pos), addr(out->goal_hdr),
+                                                addr(out->goal_slot_pos), addr(out->action), addr(out->reward), addr(out->done), addr(out->desired), addr(out->env),
+                                                addr(out->slot), addr(out->future)};
     switch (cwh_replay_sample_args(n_rows, her, strategy, fields)) {
     case CWH_REPLAY_OK: break;
     case CWH_REPLAY_N_ROWS: return fail(CW_ERR_INVALID, "cw_replay_sample: n_rows = %d must be 0 .. %d", n_rows, CWH_MAX_STATES);
@@ -1271,16 +1262,8 @@ int cw_replay_sample(cw_engine *e, int32_t n_rows, uint64_t seed, const uint64_t
 }
 
 // ------------------------------------------------------------------------------ seen: the visited set of packed records
-// One allocation of the engine's, like the snapshot bank and as far from every checkpoint blob and snapshot row: the control block (256 bytes), then the tags,
-// the owners and the two halves of the stored keys, 48 bytes a slot.  A reserve drops everything seen: the new set is cleared before the call returns.
-static void seen_free(cw_engine *e)
-{
-    if (e->seen) (void)hipFree(e->seen);
-    e->seen = nullptr;
-    e->Sn = CwSeen{};
-    e->seen_slots = 0;
-}
-
+// A Region of the engine's, as far from every checkpoint blob and snapshot row as the others; its sections are cw_host.cpp's (cwh_seen_layout: the control
+// block, then the tags, the owners and the two halves of the stored keys, 48 bytes a slot).  A reserve drops everything seen: the new set is cleared before the call returns.
 int cw_seen_reserve(cw_engine *e, int64_t capacity, int32_t tag_bits)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_seen_reserve: null engine");
@@ -1289,30 +1272,28 @@ int cw_seen_reserve(cw_engine *e, int64_t capacity, int32_t tag_bits)
     if (tag_bits < 0 || tag_bits > 63) return fail(CW_ERR_INVALID, "cw_seen_reserve: tag_bits = %d must be 0 (the full hash) .. 63", tag_bits);
     SyncEntry in(e);                                 // (the engine's own work: an insert in flight uses the set about to go)
     if (in.rc != CW_OK) return in.rc;
-    seen_free(e);
+    region_free(e->seen);
+    e->Sn = CwSeen{};
+    e->seen_slots = 0;
     if (slots == 0) return CW_OK;
-    const size_t n = (size_t)slots, ctl_bytes = 256;
-    void *p = nullptr;
-    if (hipMalloc(&p, ctl_bytes + n * 48) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(CW_ERR_HIP, "cw_seen_reserve: no device memory for %lld slots of 48 bytes", (long long)slots);
-    }
-    char *const b = (char *)p;
+    uint64_t at[CWH_SEEN_SECTIONS];
+    const int64_t bytes = cwh_seen_layout(slots, at);
+    NewRegion nr;
+    if (!nr.alloc((size_t)bytes)) return fail(CW_ERR_HIP, "cw_seen_reserve: no device memory for %lld slots of 48 bytes", (long long)slots);
     CwSeen S{};
-    S.ctl = (unsigned long long *)b;
-    S.tag = (unsigned long long *)(b + ctl_bytes);
-    S.owner = (unsigned long long *)(b + ctl_bytes + n * 8);
-    S.key_a = (uint4 *)(b + ctl_bytes + n * 16);
-    S.key_b = (uint4 *)(b + ctl_bytes + n * 32);
-    S.mask = (uint32_t)(n - 1);
+    S.ctl = (unsigned long long *)nr.at(at[CWH_SEEN_S_CTL]);
+    S.tag = (unsigned long long *)nr.at(at[CWH_SEEN_S_TAG]);
+    S.owner = (unsigned long long *)nr.at(at[CWH_SEEN_S_OWNER]);
+    S.key_a = (uint4 *)nr.at(at[CWH_SEEN_S_KEY_A]);
+    S.key_b = (uint4 *)nr.at(at[CWH_SEEN_S_KEY_B]);
+    S.mask = (uint32_t)(slots - 1);
     S.probes = slots < CWH_SEEN_PROBES ? (int32_t)slots : CWH_SEEN_PROBES;
     S.tag_bits = tag_bits;
     if (cwk_launch_seen_clear(&e->tune, &S, e->aux) != hipSuccess || hipStreamSynchronize(e->aux) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(p);
         return fail(CW_ERR_HIP, "cw_seen_reserve: clearing the set failed");
     }
-    e->seen = p;
+    e->seen = nr.commit();
     e->Sn = S;
     e->seen_slots = slots;
     return CW_OK;
@@ -1347,8 +1328,7 @@ int cw_seen_clear(cw_engine *e, cw_stream_t stream)
 int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_states, const cw_seen_out *out, cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_seen_insert: null %s", !e ? "engine" : "out");
-    switch (cwh_seen_args((uint64_t)(uintptr_t)group, (uint64_t)(uintptr_t)hdr, (uint64_t)(uintptr_t)slot_pos, n_states, (uint64_t)(uintptr_t)out->fresh,
-                          (uint64_t)(uintptr_t)out->first)) {
+    switch (cwh_seen_args(addr(group), addr(hdr), addr(slot_pos), n_states, addr(out->fresh), addr(out->first))) {
     case CWH_SEEN_OK: break;
     case CWH_SEEN_NO_RECORDS: return fail(CW_ERR_INVALID, "cw_seen_insert: null %s", !hdr ? "hdr" : "slot_pos");
     case CWH_SEEN_NO_FIELD: return fail(CW_ERR_INVALID, "cw_seen_insert: every field of out is null");
@@ -1371,8 +1351,7 @@ int cw_seen_insert(cw_engine *e, const int32_t *group, const uint8_t *hdr, const
 int cw_load_records(cw_engine *e, const int32_t *src, const uint8_t *hdr, const uint16_t *slot_pos, int32_t n_records, uint8_t *status, cw_stream_t stream)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_load_records: null engine");
-    switch (cwh_load_records_args(e->n, (uint64_t)(uintptr_t)src, (uint64_t)(uintptr_t)hdr, (uint64_t)(uintptr_t)slot_pos, n_records, (uint64_t)(uintptr_t)status,
-                                  (uint64_t)(uintptr_t)e->P.hdr, (uint64_t)(uintptr_t)e->P.pos)) {
+    switch (cwh_load_records_args(e->n, addr(src), addr(hdr), addr(slot_pos), n_records, addr(status), addr(e->P.hdr), addr(e->P.pos))) {
     case CWH_LOAD_OK: break;
     case CWH_LOAD_NO_RECORDS: return fail(CW_ERR_INVALID, "cw_load_records: null %s", !hdr ? "hdr" : "slot_pos");
     case CWH_LOAD_N_RECORDS: return fail(CW_ERR_INVALID, "cw_load_records: n_records = %d must be 0 .. %d", n_records, CWH_MAX_STATES);
@@ -1390,16 +1369,8 @@ int cw_load_records(cw_engine *e, const int32_t *src, const uint8_t *hdr, const 
 }
 
 // ------------------------------------------------------------------------------ reach: breadth-first search without a host round trip
-// The workspace is one allocation of the engine's, like the visited set and as far from every checkpoint blob and snapshot row; its sections are
-// cw_host.cpp's (cwh_reach_layout).  Nothing of it needs an initial value: every call writes what it reads.
-static void reach_free(cw_engine *e)
-{
-    if (e->reach) (void)hipFree(e->reach);
-    e->reach = nullptr;
-    e->Rc = CwReach{};
-    e->reach_bytes = 0;
-}
-
+// The workspace is a Region of the engine's, as far from every checkpoint blob and snapshot row as the others; its sections are cw_host.cpp's
+// (cwh_reach_layout).  Nothing of it needs an initial value: every call writes what it reads.
 int cw_reach_reserve(cw_engine *e, int64_t max_rows, int32_t max_depth)
 {
     if (!e) return fail(CW_ERR_INVALID, "cw_reach_reserve: null engine");
@@ -1410,45 +1381,42 @@ int cw_reach_reserve(cw_engine *e, int64_t max_rows, int32_t max_depth)
                     (long long)CWH_REACH_MAX_ROWS, max_depth, CWH_REACH_MAX_DEPTH);
     SyncEntry in(e);                                 // (the engine's own work: a search in flight uses the workspace about to go)
     if (in.rc != CW_OK) return in.rc;
-    reach_free(e);
+    region_free(e->reach);
+    e->Rc = CwReach{};
     if (bytes == 0) return CW_OK;
-    void *p = nullptr;
-    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    NewRegion nr;
+    if (!nr.alloc((size_t)bytes))
         return fail(CW_ERR_HIP, "cw_reach_reserve: no device memory for %lld bytes (%lld rows, %d levels)", (long long)bytes, (long long)max_rows, max_depth);
-    }
-    char *const b = (char *)p;
     CwReach R{};
-    R.ctl = (int32_t *)(b + at[CWH_REACH_S_CTL]);
+    R.ctl = (int32_t *)nr.at(at[CWH_REACH_S_CTL]);
     R.sizes = R.ctl + CWH_REACH_CTL_WORDS;
     R.chunk = R.sizes + max_depth + 1;
     for (int k = 0; k < 2; k++) {
-        R.f_hdr[k] = (uint4 *)(b + at[CWH_REACH_S_F_HDR0 + 4 * k]);
-        R.f_pos[k] = (uint4 *)(b + at[CWH_REACH_S_F_POS0 + 4 * k]);
-        R.f_env[k] = (int32_t *)(b + at[CWH_REACH_S_F_ENV0 + 4 * k]);
-        R.f_start[k] = (int32_t *)(b + at[CWH_REACH_S_F_START0 + 4 * k]);
+        R.f_hdr[k] = (uint4 *)nr.at(at[CWH_REACH_S_F_HDR0 + 4 * k]);
+        R.f_pos[k] = (uint4 *)nr.at(at[CWH_REACH_S_F_POS0 + 4 * k]);
+        R.f_env[k] = (int32_t *)nr.at(at[CWH_REACH_S_F_ENV0 + 4 * k]);
+        R.f_start[k] = (int32_t *)nr.at(at[CWH_REACH_S_F_START0 + 4 * k]);
     }
-    R.s_hdr = (uint4 *)(b + at[CWH_REACH_S_HDR]);
-    R.s_pos = (uint4 *)(b + at[CWH_REACH_S_POS]);
-    R.s_grp = (int32_t *)(b + at[CWH_REACH_S_GRP]);
-    R.s_fresh = (uint8_t *)(b + at[CWH_REACH_S_FRESH]);
-    R.links = (int32_t *)(b + at[CWH_REACH_S_LINKS]);
-    R.dist = (int32_t *)(b + at[CWH_REACH_S_DIST]);
-    R.sol = (int32_t *)(b + at[CWH_REACH_S_SOL]);
-    R.bid = (int32_t *)(b + at[CWH_REACH_S_BID]);
-    R.active = (uint8_t *)(b + at[CWH_REACH_S_ACTIVE]);
+    R.s_hdr = (uint4 *)nr.at(at[CWH_REACH_S_HDR]);
+    R.s_pos = (uint4 *)nr.at(at[CWH_REACH_S_POS]);
+    R.s_grp = (int32_t *)nr.at(at[CWH_REACH_S_GRP]);
+    R.s_fresh = (uint8_t *)nr.at(at[CWH_REACH_S_FRESH]);
+    R.links = (int32_t *)nr.at(at[CWH_REACH_S_LINKS]);
+    R.dist = (int32_t *)nr.at(at[CWH_REACH_S_DIST]);
+    R.sol = (int32_t *)nr.at(at[CWH_REACH_S_SOL]);
+    R.bid = (int32_t *)nr.at(at[CWH_REACH_S_BID]);
+    R.active = (uint8_t *)nr.at(at[CWH_REACH_S_ACTIVE]);
     R.max_rows = (int32_t)max_rows;
     R.max_depth = max_depth;
-    e->reach = p;
+    e->reach = nr.commit();
     e->Rc = R;
-    e->reach_bytes = (size_t)bytes;
     return CW_OK;
 }
 
 size_t cw_reach_bytes(const cw_engine *e)
 {
     if (!e) { (void)fail(CW_ERR_INVALID, "cw_reach_bytes: null engine"); return 0; }
-    return e->reach ? e->reach_bytes : 0;
+    return e->reach.bytes;
 }
 
 // Checks (cwh_reach_args, tested on the CPU), then kernels only: no wait, no allocation, the same call whether it runs or is captured.  Of the engine the
@@ -1457,9 +1425,8 @@ int cw_reach(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const u
              cw_stream_t stream)
 {
     if (!e || !out) return fail(CW_ERR_INVALID, "cw_reach: null %s", !e ? "engine" : "out");
-    switch (cwh_reach_args(e->n, (uint64_t)(uintptr_t)env_of, (uint64_t)(uintptr_t)hdr_in, (uint64_t)(uintptr_t)slot_pos_in, n_states, max_depth,
-                           (uint64_t)(uintptr_t)out->distance, (uint64_t)(uintptr_t)out->plan, (uint64_t)(uintptr_t)out->first_action,
-                           (uint64_t)(uintptr_t)out->frontier, (uint64_t)(uintptr_t)out->searched_depth)) {
+    switch (cwh_reach_args(e->n, addr(env_of), addr(hdr_in), addr(slot_pos_in), n_states, max_depth, addr(out->distance), addr(out->plan),
+                           addr(out->first_action), addr(out->frontier), addr(out->searched_depth))) {
     case CWH_REACH_OK: break;
     case CWH_REACH_NO_FIELD: return fail(CW_ERR_INVALID, "cw_reach: every field of out is null");
     case CWH_REACH_N_STATES: return fail(CW_ERR_INVALID, "cw_reach: n_states = %d must be 0 .. %lld", n_states, (long long)CWH_REACH_MAX_ROWS);
@@ -1509,13 +1476,14 @@ int cw_render_records(cw_engine *e, const uint8_t *hdr, const uint16_t *slot_pos
         return fail(CW_ERR_INVALID, "cw_render_records: null %s", !e ? "engine" : !hdr ? "hdr" : !slot_pos ? "slot_pos" : "out_frames");
     const int bad = states_args("cw_render_records", hdr, slot_pos, n_states);
     if (bad != CW_OK) return bad;
-    if (e->P.raster != CW_RASTER_ALT && ((uintptr_t)out_frames & 3u) != 0)      // (the Ray painter's 12-byte stores; AltObs frames start at every alignment anyway)
-        return fail(CW_ERR_INVALID, "cw_render_records: out_frames is not 4-byte aligned");
-    const uint64_t o_bytes = (uint64_t)n_states * e->P.frame_bytes;
-    if (overlaps_records(out_frames, o_bytes, hdr, slot_pos, 16ull * (uint64_t)n_states))
-        return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the records read");
-    if (mask && cwh_ranges_overlap((uint64_t)(uintptr_t)out_frames, o_bytes, (uint64_t)(uintptr_t)mask, (uint64_t)n_states))
-        return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the mask");
+    const uint64_t m = (uint64_t)n_states;
+    // (4-byte aligned for the Ray painter's 12-byte stores; AltObs frames start at every alignment anyway)
+    const cwh_span frames = {addr(out_frames), m * e->P.frame_bytes, e->P.raster != CW_RASTER_ALT ? 4u : 1u};
+    const cwh_span ins[3] = {{addr(hdr), 16 * m, 16}, {addr(slot_pos), 16 * m, 16}, {addr(mask), m, 1}};
+    if (cwh_spans_misaligned(&frames, 1) >= 0) return fail(CW_ERR_INVALID, "cw_render_records: out_frames is not 4-byte aligned");
+    int other = 0;
+    if (cwh_spans_clash(&frames, 1, ins, 3, 0, &other) >= 0)
+        return fail(CW_ERR_INVALID, "cw_render_records: out_frames overlaps the %s", other < 2 ? "records read" : "mask");
     if (!e->has_reset) return fail(CW_ERR_STATE, "cw_render_records called before cw_reset");
     if (n_states == 0) return CW_OK;
     EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);

@@ -162,14 +162,11 @@ int cwh_snapshot_section_bytes(int64_t rows, int32_t k, int32_t la_depth, size_t
 {
     const size_t R = rows > 0 ? (size_t)rows : 0, K = k > 0 ? (size_t)k : 0, D = la_depth > 0 ? (size_t)la_depth : 0, la = D ? 1 : 0;
     const size_t per_row[CWH_SNAP_SECTIONS] = {16, 16, 16, 16, 4, 4, 2, 2, CWH_MT_N * 4, 4, D * 16, D * 16, D * 16, la * 4, K * 9 * 2, 1};
-    uint64_t at = 0, row = 0;
-    for (int i = 0; i < CWH_SNAP_SECTIONS; i++) {
-        if (sizes) sizes[i] = per_row[i] * R;
-        if (offsets) offsets[i] = (size_t)at;
-        at += (per_row[i] * R + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
-        row += per_row[i];
-    }
-    if (total) *total = at;
+    uint64_t bytes[CWH_SNAP_SECTIONS], at[CWH_SNAP_SECTIONS], row = 0;
+    for (int i = 0; i < CWH_SNAP_SECTIONS; i++) { bytes[i] = per_row[i] * R; row += per_row[i]; }
+    const uint64_t all = cwh_sections_layout(bytes, CWH_SNAP_SECTIONS, CWH_SNAP_ALIGN, at);
+    for (int i = 0; i < CWH_SNAP_SECTIONS; i++) { if (sizes) sizes[i] = (size_t)bytes[i]; if (offsets) offsets[i] = (size_t)at[i]; }
+    if (total) *total = all;
     if (row_bytes) *row_bytes = row;
     return CWH_SNAP_SECTIONS;
 }
@@ -241,6 +238,41 @@ int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_byte
     return a < b_end && b < a_end;
 }
 
+// ------------------------------------------------------------------------------ the span checker and the section layout
+int cwh_spans_misaligned(const cwh_span *spans, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (spans[i].at && spans[i].align && spans[i].at % spans[i].align) return i;
+    return -1;
+}
+
+static bool spans_share(const cwh_span &a, const cwh_span &b) { return a.at && b.at && cwh_ranges_overlap(a.at, a.bytes, b.at, b.bytes); }
+int cwh_spans_clash(const cwh_span *outs, int n_outs, const cwh_span *ins, int n_ins, int among_outs, int *other)
+{
+    for (int o = 0; o < n_outs; o++) {
+        int hit = -1;
+        for (int i = 0; i < n_ins && hit < 0; i++)
+            if (spans_share(outs[o], ins[i])) hit = i;
+        for (int q = o + 1; among_outs && q < n_outs && hit < 0; q++)
+            if (spans_share(outs[o], outs[q])) hit = n_ins + q;
+        if (hit < 0) continue;
+        if (other) *other = hit;
+        return o;
+    }
+    return -1;
+}
+
+uint64_t cwh_sections_layout(const uint64_t *bytes, int n, uint64_t align, uint64_t *offsets)
+{
+    uint64_t at = 0;
+    if (!align) align = 1;
+    for (int i = 0; i < n; i++) {
+        if (offsets) offsets[i] = at;
+        at += (bytes[i] + align - 1) / align * align;
+    }
+    return at;
+}
+
 // ------------------------------------------------------------------------------ cw_shoot_refit: the weight, the grid, the argument rules
 uint32_t cwh_refit_weight_of(uint32_t smooth, uint32_t gain, uint32_t count) { return cwh_refit_weight(smooth, gain, count); }
 int64_t cwh_refit_grid_of(int64_t items, int32_t n_cu) { return cwh_refit_grid(items, n_cu); }
@@ -256,20 +288,12 @@ int cwh_refit_args(uint64_t env_of, int32_t n_states, int32_t n_steps, int32_t n
     if ((uint64_t)n_states * (uint64_t)n_samples * (uint64_t)n_steps > CWH_SHOOT_MAX_WORK) return CWH_REFIT_WORK;       // (<= 2^27 * 2^16 * 2^15)
     if (smooth > 65535u) return CWH_REFIT_SMOOTH;
     if (gain < 1u || gain > 65535u) return CWH_REFIT_GAIN;
-    if ((env_of & 3u) || (ret & 3u) || (elites & 3u) || (elite_min & 3u) || (weights_in & 1u) || (weights & 1u)) return CWH_REFIT_ALIGN;
     const uint64_t m = (uint64_t)n_states, w_bytes = 12 * (uint64_t)n_steps * m;
-    const uint64_t outs[3][2] = {{elites, 4 * (uint64_t)n_elites * m}, {weights, w_bytes}, {elite_min, 4 * m}};
-    const uint64_t ins[3][2] = {{ret, 4 * (uint64_t)n_samples * m}, {env_of, 4 * m}, {weights_in, w_bytes}};
-    for (int o = 0; o < 3; o++) {
-        if (!outs[o][0]) continue;
-        for (int i = 0; i < 3; i++) {
-            if (!ins[i][0] || (o == 1 && i == 2 && weights == weights_in)) continue;                                      // (in place: the one overlap allowed)
-            if (cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_REFIT_OVERLAP;
-        }
-        for (int q = o + 1; q < 3; q++)
-            if (outs[q][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], outs[q][0], outs[q][1])) return CWH_REFIT_OVERLAP;
-    }
-    return CWH_REFIT_OK;
+    const cwh_span outs[3] = {{elites, 4 * (uint64_t)n_elites * m, 4}, {weights, w_bytes, 2}, {elite_min, 4 * m, 4}};
+    const cwh_span ins[3] = {{ret, 4 * (uint64_t)n_samples * m, 4}, {env_of, 4 * m, 4}, {weights_in, w_bytes, 2}};
+    if (cwh_spans_misaligned(outs, 3) >= 0 || cwh_spans_misaligned(ins, 3) >= 0) return CWH_REFIT_ALIGN;
+    // (in place, the one overlap allowed: weights_in at the address of weights is the same bytes, and weights is tested against everything else)
+    return cwh_spans_clash(outs, 3, ins, weights == weights_in ? 2 : 3, 1, nullptr) >= 0 ? CWH_REFIT_OVERLAP : CWH_REFIT_OK;
 }
 
 // ------------------------------------------------------------------------------ the visited set's key, size and argument rules
@@ -301,16 +325,17 @@ int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_sta
     if (!hdr || !slot_pos) return CWH_SEEN_NO_RECORDS;
     if (!fresh && !first) return CWH_SEEN_NO_FIELD;
     if (n_states < 0 || n_states > CWH_MAX_STATES) return CWH_SEEN_N_STATES;
-    if ((hdr & 15u) || (slot_pos & 15u) || (group & 3u) || (first & 3u)) return CWH_SEEN_ALIGN;
     const uint64_t m = (uint64_t)n_states;
-    const uint64_t outs[2][2] = {{fresh, m}, {first, 4 * m}}, ins[3][2] = {{hdr, 16 * m}, {slot_pos, 16 * m}, {group, 4 * m}};
-    for (int o = 0; o < 2; o++) {
-        if (!outs[o][0]) continue;
-        for (int i = 0; i < 3; i++)
-            if (ins[i][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_SEEN_OVERLAP;
-    }
-    if (fresh && first && cwh_ranges_overlap(fresh, m, first, 4 * m)) return CWH_SEEN_OVERLAP;
-    return CWH_SEEN_OK;
+    const cwh_span outs[2] = {{fresh, m, 1}, {first, 4 * m, 4}}, ins[3] = {{hdr, 16 * m, 16}, {slot_pos, 16 * m, 16}, {group, 4 * m, 4}};
+    if (cwh_spans_misaligned(outs, 2) >= 0 || cwh_spans_misaligned(ins, 3) >= 0) return CWH_SEEN_ALIGN;
+    return cwh_spans_clash(outs, 2, ins, 3, 1, nullptr) >= 0 ? CWH_SEEN_OVERLAP : CWH_SEEN_OK;
+}
+
+int64_t cwh_seen_layout(int64_t slots, uint64_t *offsets)
+{
+    if (slots < 2 || slots > 2 * CWH_SEEN_MAX_CAPACITY || (slots & (slots - 1))) return -1;
+    const uint64_t n = (uint64_t)slots, bytes[CWH_SEEN_SECTIONS] = {CWH_SEEN_CTL_BYTES, 8 * n, 8 * n, 16 * n, 16 * n};
+    return (int64_t)cwh_sections_layout(bytes, CWH_SEEN_SECTIONS, 16, offsets);
 }
 
 // ------------------------------------------------------------------------------ cw_load_records: the rule a record passes, the index check, the argument rules
@@ -334,17 +359,12 @@ int cwh_load_records_args(int32_t num_envs, uint64_t src, uint64_t hdr, uint64_t
     if (!hdr || !slot_pos) return CWH_LOAD_NO_RECORDS;
     if (n_records < 0 || n_records > CWH_MAX_STATES) return CWH_LOAD_N_RECORDS;
     if (!src && n_records != num_envs) return CWH_LOAD_OWN_ORDER;
-    if ((hdr & 15u) || (slot_pos & 15u) || (src & 3u)) return CWH_LOAD_ALIGN;
     const uint64_t r = 16ull * (uint64_t)n_records, n = num_envs > 0 ? (uint64_t)num_envs : 0;
-    const uint64_t recs[2] = {hdr, slot_pos}, own[2] = {engine_hdr, engine_slot_pos};
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 2; j++)
-            if (own[j] && cwh_ranges_overlap(recs[i], r, own[j], 16 * n)) return CWH_LOAD_ENGINE_OVERLAP;
-    if (status) {
-        if (cwh_ranges_overlap(status, n, hdr, r) || cwh_ranges_overlap(status, n, slot_pos, r)) return CWH_LOAD_STATUS_OVERLAP;
-        if (src && cwh_ranges_overlap(status, n, src, 4 * n)) return CWH_LOAD_STATUS_OVERLAP;
-    }
-    return CWH_LOAD_OK;
+    const cwh_span read[3] = {{hdr, r, 16}, {slot_pos, r, 16}, {src, 4 * n, 4}}, own[2] = {{engine_hdr, 16 * n, 16}, {engine_slot_pos, 16 * n, 16}};
+    const cwh_span status_span = {status, n, 1};
+    if (cwh_spans_misaligned(read, 3) >= 0) return CWH_LOAD_ALIGN;
+    if (cwh_spans_clash(read, 2, own, 2, 0, nullptr) >= 0) return CWH_LOAD_ENGINE_OVERLAP;
+    return cwh_spans_clash(&status_span, 1, read, 3, 0, nullptr) >= 0 ? CWH_LOAD_STATUS_OVERLAP : CWH_LOAD_OK;
 }
 
 // ------------------------------------------------------------------------------ cw_replay_*: the relabelled reward, the buffer's sections, the argument rules
@@ -358,12 +378,7 @@ int64_t cwh_replay_layout(int32_t steps, int32_t num_envs, uint64_t *offsets)
     if (steps < 1 || steps > CWH_REPLAY_MAX_STEPS || num_envs < 1 || (int64_t)steps * (int64_t)num_envs >= (1ll << 31)) return -1;
     const uint64_t N = (uint64_t)num_envs, T = (uint64_t)steps * N;
     const uint64_t bytes[CWH_REPLAY_SECTIONS] = {CWH_REPLAY_CTL_BYTES, 4 * N, 16 * T, 16 * T, 16 * T, 16 * T, 16 * T, 16 * T, 4 * T, 4 * T, T, T};
-    uint64_t at = 0;
-    for (int i = 0; i < CWH_REPLAY_SECTIONS; i++) {
-        if (offsets) offsets[i] = at;
-        at += (bytes[i] + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
-    }
-    return (int64_t)at;
+    return (int64_t)cwh_sections_layout(bytes, CWH_REPLAY_SECTIONS, CWH_SNAP_ALIGN, offsets);
 }
 int64_t cwh_replay_bytes_of(int32_t steps, int32_t num_envs) { return cwh_replay_layout(steps, num_envs, nullptr); }
 
@@ -377,16 +392,14 @@ int cwh_replay_sample_args(int32_t n_rows, uint32_t her, int32_t strategy, const
     if (her > 65536u) return CWH_REPLAY_HER;
     if (strategy != 0 && strategy != 1) return CWH_REPLAY_STRATEGY;
     int any = 0;
-    for (int f = 0; f < CWH_REPLAY_FIELDS; f++) any |= fields[f] != 0;
+    cwh_span outs[CWH_REPLAY_FIELDS];
+    for (int f = 0; f < CWH_REPLAY_FIELDS; f++) {
+        any |= fields[f] != 0;
+        outs[f] = cwh_span{fields[f], (uint64_t)kReplayFieldBytes[f] * (uint64_t)n_rows, (uint64_t)kReplayFieldBytes[f]};
+    }
     if (!any) return CWH_REPLAY_NO_FIELD;
-    for (int f = 0; f < CWH_REPLAY_FIELDS; f++)
-        if (fields[f] & (uint64_t)(kReplayFieldBytes[f] - 1)) return CWH_REPLAY_ALIGN;
-    for (int f = 0; f < CWH_REPLAY_FIELDS; f++)
-        for (int g = f + 1; g < CWH_REPLAY_FIELDS; g++)
-            if (fields[f] && fields[g] &&
-                cwh_ranges_overlap(fields[f], (uint64_t)kReplayFieldBytes[f] * (uint64_t)n_rows, fields[g], (uint64_t)kReplayFieldBytes[g] * (uint64_t)n_rows))
-                return CWH_REPLAY_OVERLAP;
-    return CWH_REPLAY_OK;
+    if (cwh_spans_misaligned(outs, CWH_REPLAY_FIELDS) >= 0) return CWH_REPLAY_ALIGN;
+    return cwh_spans_clash(outs, CWH_REPLAY_FIELDS, nullptr, 0, 1, nullptr) >= 0 ? CWH_REPLAY_OVERLAP : CWH_REPLAY_OK;
 }
 
 // ------------------------------------------------------------------------------ cw_reach: the rows of a level, the workspace's sections, the argument rules
@@ -400,12 +413,7 @@ int64_t cwh_reach_layout(int64_t max_rows, int32_t max_depth, uint64_t *offsets)
     const uint64_t R = (uint64_t)max_rows, D = (uint64_t)max_depth, rows = (uint64_t)cwh_reach_rows(max_rows), chunks = (uint64_t)cwh_reach_chunks((int64_t)rows);
     const uint64_t bytes[CWH_REACH_SECTIONS] = {4 * (CWH_REACH_CTL_WORDS + D + 1 + chunks), 16 * R, 16 * R, 4 * R, 4 * R, 16 * R, 16 * R, 4 * R, 4 * R,
                                                 16 * rows, 16 * rows, 4 * rows, chunks * CWH_REACH_CHUNK, 4 * R * (D - 1), 4 * R, 4 * R, 4 * R, R};
-    uint64_t at = 0;
-    for (int i = 0; i < CWH_REACH_SECTIONS; i++) {
-        if (offsets) offsets[i] = at;
-        at += (bytes[i] + CWH_SNAP_ALIGN - 1) / CWH_SNAP_ALIGN * CWH_SNAP_ALIGN;
-    }
-    return (int64_t)at;
+    return (int64_t)cwh_sections_layout(bytes, CWH_REACH_SECTIONS, CWH_SNAP_ALIGN, offsets);
 }
 int64_t cwh_reach_bytes_of(int64_t max_rows, int32_t max_depth) { return cwh_reach_layout(max_rows, max_depth, nullptr); }
 
@@ -418,18 +426,11 @@ int cwh_reach_args(int32_t num_envs, uint64_t env_of, uint64_t hdr_in, uint64_t 
     if (!hdr_in != !slot_pos_in) return CWH_REACH_PAIR;
     if (env_of && !hdr_in) return CWH_REACH_ENV_OF;
     if (!hdr_in && n_states != num_envs) return CWH_REACH_OWN_STATES;
-    if ((hdr_in & 15u) || (slot_pos_in & 15u) || (env_of & 3u) || (distance & 3u) || (frontier & 3u) || (searched_depth & 3u)) return CWH_REACH_ALIGN;
     const uint64_t m = (uint64_t)n_states, d = (uint64_t)max_depth;
-    const uint64_t outs[5][2] = {{distance, 4 * m}, {plan, d * m}, {first_action, m}, {frontier, 4 * d}, {searched_depth, 4}};
-    const uint64_t ins[3][2] = {{hdr_in, 16 * m}, {slot_pos_in, 16 * m}, {env_of, 4 * m}};
-    for (int o = 0; o < 5; o++) {
-        if (!outs[o][0]) continue;
-        for (int i = 0; i < 3; i++)
-            if (ins[i][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], ins[i][0], ins[i][1])) return CWH_REACH_OVERLAP;
-        for (int q = o + 1; q < 5; q++)
-            if (outs[q][0] && cwh_ranges_overlap(outs[o][0], outs[o][1], outs[q][0], outs[q][1])) return CWH_REACH_OVERLAP;
-    }
-    return CWH_REACH_OK;
+    const cwh_span outs[5] = {{distance, 4 * m, 4}, {plan, d * m, 1}, {first_action, m, 1}, {frontier, 4 * d, 4}, {searched_depth, 4, 4}};
+    const cwh_span ins[3] = {{hdr_in, 16 * m, 16}, {slot_pos_in, 16 * m, 16}, {env_of, 4 * m, 4}};
+    if (cwh_spans_misaligned(outs, 5) >= 0 || cwh_spans_misaligned(ins, 3) >= 0) return CWH_REACH_ALIGN;
+    return cwh_spans_clash(outs, 5, ins, 3, 1, nullptr) >= 0 ? CWH_REACH_OVERLAP : CWH_REACH_OK;
 }
 
 // ------------------------------------------------------------------------------ the sweep clock's periods and schedule

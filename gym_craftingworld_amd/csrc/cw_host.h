@@ -154,6 +154,20 @@ int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot
 // the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
 
+// ---- THE SPAN CHECKER: every "is this pointer aligned, does this output share a byte with what it must not" of the entry points goes through these two.
+// A span is what a call reads or writes through one pointer: the address as an integer (0: not given), its bytes, the alignment the kernels need of it
+// (0 or 1: any address).
+typedef struct cwh_span { uint64_t at, bytes, align; } cwh_span;
+// the index of the first given span whose address is no multiple of its alignment, -1: none
+int cwh_spans_misaligned(const cwh_span *spans, int n);
+// The first output that shares a byte (cwh_ranges_overlap) with something it must not: the outputs in order, each against the inputs in order and then, with
+// among_outs, against the outputs behind it in order.  A span not given, or of no bytes, shares none.  -> the output's index and in *other (may be null) the
+// other side's -- i for ins[i], n_ins + q for outs[q] --, or -1: no clash.
+int cwh_spans_clash(const cwh_span *outs, int n_outs, const cwh_span *ins, int n_ins, int among_outs, int *other);
+// ---- THE SECTION LAYOUT of a region, one allocation cut into n sections in order (snapshot bank, visited set, reach workspace, replay buffer): section i
+// starts at offsets[i] (may be null), the sum of the sections before it, each rounded up to a multiple of align (>= 1).  -> the bytes of the region
+uint64_t cwh_sections_layout(const uint64_t *bytes, int n, uint64_t align, uint64_t *offsets);
+
 // ---- cw_shoot / cw_shoot_actions: THE DRAW (include/craftingworld.h states it), shared by the kernels and the host -- integers only, so a CPU model is exact.
 // cwh_shoot_prefix is the part that does not depend on the step: the kernels compute it once per sample, outside the step loop.
 static inline CWH_HOST_DEVICE uint32_t cwh_shoot_mix(uint32_t x)
@@ -233,8 +247,9 @@ int64_t cwh_refit_grid_of(int64_t items, int32_t n_cu);                         
 // (CWH_REFIT_NULL), 0 <= n_states <= CWH_MAX_STATES (CWH_REFIT_N_STATES), 1 <= n_steps <= CWH_SIM_MAX_STEPS (CWH_REFIT_N_STEPS), 1 <= n_samples <=
 // CWH_SHOOT_MAX_SAMPLES (CWH_REFIT_N_SAMPLES), 1 <= n_elites <= n_samples (CWH_REFIT_N_ELITES), n_states * n_samples * n_steps <= CWH_SHOOT_MAX_WORK
 // (CWH_REFIT_WORK: cw_shoot's cap; the refit draws n_states * n_elites * n_steps times at most), smooth <= 65 535 (CWH_REFIT_SMOOTH), 1 <= gain <= 65 535
-// (CWH_REFIT_GAIN), env_of, ret, elites, elite_min 4-byte and weights_in, weights 2-byte aligned (CWH_REFIT_ALIGN), no output sharing a byte with ret,
-// env_of, another output or weights_in -- except weights == weights_in, the SAME address: the refit in place (CWH_REFIT_OVERLAP).
+// (CWH_REFIT_GAIN), env_of, ret, elites, elite_min 4-byte and weights_in, weights 2-byte aligned (CWH_REFIT_ALIGN: cwh_spans_misaligned), no output
+// sharing a byte with ret, env_of, another output or weights_in (CWH_REFIT_OVERLAP: cwh_spans_clash) -- except weights == weights_in, the SAME address, the
+// refit in place: weights_in then is no input of its own, its bytes are exactly those of weights, which is tested against every other span.
 enum { CWH_REFIT_OK = 0, CWH_REFIT_NULL = 1, CWH_REFIT_N_STATES = 2, CWH_REFIT_N_STEPS = 3, CWH_REFIT_N_SAMPLES = 4, CWH_REFIT_N_ELITES = 5, CWH_REFIT_WORK = 6,
        CWH_REFIT_SMOOTH = 7, CWH_REFIT_GAIN = 8, CWH_REFIT_ALIGN = 9, CWH_REFIT_OVERLAP = 10 };
 int cwh_refit_args(uint64_t env_of, int32_t n_states, int32_t n_steps, int32_t n_samples, int32_t n_elites, uint64_t weights_in, uint64_t ret, uint32_t smooth,
@@ -280,9 +295,16 @@ uint64_t cwh_seen_hash_of(const uint32_t *key /* [9] */);                       
 #define CWH_SEEN_ROW_BITS 28        // an owner word is epoch << 28 | row: rows below 2^27, 36 bits of epoch
 #define CWH_SEEN_MAX_EPOCH ((1ull << 36) - 2ull)
 int64_t cwh_seen_slots_of(int64_t capacity);
+// the set of `slots` slots: CWH_SEEN_SECTIONS sections in this order -- the control block (CWH_SEEN_CTL_BYTES), tag and owner (8 bytes a slot each), key_a and
+// key_b (16 each) --, packed: every one a multiple of 16 bytes, the alignment the key halves need, 48 bytes a slot in all.  Writes the sections' offsets (may
+// be null); -> the bytes, -1 unless slots is a count cwh_seen_slots_of gives a set: a power of two, 2 .. 2 * CWH_SEEN_MAX_CAPACITY.
+#define CWH_SEEN_CTL_BYTES 256
+enum { CWH_SEEN_S_CTL = 0, CWH_SEEN_S_TAG, CWH_SEEN_S_OWNER, CWH_SEEN_S_KEY_A, CWH_SEEN_S_KEY_B, CWH_SEEN_SECTIONS };
+int64_t cwh_seen_layout(int64_t slots, uint64_t *offsets);
 // the argument rules of cw_seen_insert, in the order they are tested; addresses as integers (0: null), so the rules need no HIP: records given
 // (CWH_SEEN_NO_RECORDS), some output (CWH_SEEN_NO_FIELD), 0 <= n_states <= CWH_MAX_STATES (CWH_SEEN_N_STATES), hdr and slot_pos 16-byte aligned and group,
-// first 4-byte aligned (CWH_SEEN_ALIGN), neither output sharing a byte with hdr, slot_pos, group or the other output (CWH_SEEN_OVERLAP)
+// first 4-byte aligned (CWH_SEEN_ALIGN: cwh_spans_misaligned), neither output sharing a byte with hdr, slot_pos, group or the other output
+// (CWH_SEEN_OVERLAP: cwh_spans_clash)
 enum { CWH_SEEN_OK = 0, CWH_SEEN_NO_RECORDS = 1, CWH_SEEN_NO_FIELD = 2, CWH_SEEN_N_STATES = 3, CWH_SEEN_ALIGN = 4, CWH_SEEN_OVERLAP = 5 };
 int cwh_seen_args(uint64_t group, uint64_t hdr, uint64_t slot_pos, int32_t n_states, uint64_t fresh, uint64_t first);
 
