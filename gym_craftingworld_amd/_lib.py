@@ -65,6 +65,11 @@ class cw_simulate_out(C.Structure):
                 ('slot_pos', C.c_void_p), ('rewards', C.c_void_p), ('dones', C.c_void_p)]
 
 
+class cw_unroll_out(C.Structure):
+    _fields_ = [('hdr', C.c_void_p), ('slot_pos', C.c_void_p), ('reward', C.c_void_p), ('done', C.c_void_p), ('changed', C.c_void_p),
+                ('taken', C.c_void_p), ('length', C.c_void_p)]
+
+
 class cw_plan_out(C.Structure):
     _fields_ = [('q', C.c_void_p), ('length', C.c_void_p), ('done', C.c_void_p), ('achieved', C.c_void_p), ('hdr', C.c_void_p),
                 ('slot_pos', C.c_void_p), ('plan', C.c_void_p)]
@@ -129,6 +134,7 @@ ABI = {
     'cw_expand': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(cw_expand_out), _VP]),
     'cw_export_onehot_states': (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
     'cw_simulate': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.POINTER(cw_simulate_out), _VP]),
+    'cw_unroll': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.POINTER(cw_unroll_out), _VP]),
     'cw_plan': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(cw_plan_out), _VP]),
     'cw_shoot': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, C.POINTER(cw_shoot_out), _VP]),
     'cw_shoot_actions': (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_uint64, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
@@ -200,6 +206,7 @@ cwh_lookup = C.CFUNCTYPE(_VP, _VP, C.c_char_p)      # (ctx, name) -> the variabl
 CWH_GUARD_NONE, CWH_GUARD_SLOWDOWN, CWH_GUARD_TRIAL_UP, CWH_GUARD_TRIAL_KEPT, CWH_GUARD_TRIAL_UNDONE = range(5)
 CWH_REC_OK, CWH_REC_NO_FIELD, CWH_REC_N_STATES, CWH_REC_N_STEPS, CWH_REC_PAIR, CWH_REC_ENV_OF, CWH_REC_OWN_STATES = range(7)
 CWH_REC_PLAN_WORK = 7
+CWH_REC_UNROLL_ROWS = 8
 CWH_MAX_STATES, CWH_SIM_MAX_STEPS = 1 << 27, 32767
 CWH_PLAN_MAX_DEPTH, CWH_PLAN_MAX_LEAVES = 8, 1 << 32
 CWH_REC_SHOOT_WORK, CWH_REC_SHOOT_SAMPLES = 8, 9
@@ -244,6 +251,7 @@ HOST_HELPERS = {
     'cwh_piece_chunks_of': (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'cwh_records_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int]),
     'cwh_plan_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
+    'cwh_unroll_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int]),
     'cwh_shoot_args': (C.c_int, [C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int]),
     'cwh_shoot_actions_args': (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     'cwh_shoot_draw_of': (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -57,6 +57,8 @@ hipError_t cwk_launch_seen_insert(const CwParams *P, const CwTuning *T, const Cw
 hipError_t cwk_launch_seen_clear(const CwTuning *T, const CwSeen *S, hipStream_t st);
 hipError_t cwk_launch_reach(const CwParams *P, const CwTuning *T, const CwSeen *S, const CwReach *R, const int32_t *env_of, const uint4 *hdr, const uint4 *pos,
                             int n_states, int depth, const CwReachOut *O, hipStream_t st);
+hipError_t cwk_launch_unroll(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
+                             int n_steps, int stop_at_done, const CwUnrollOut *O, hipStream_t st);
 hipError_t cwk_launch_simulate(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
                                int n_steps, int stop_at_done, const CwSimulateOut *O, hipStream_t st);
 hipError_t cwk_launch_rollout(const CwParams *P, const uint8_t *actions, int T, int32_t *rewards, uint8_t *dones, hipStream_t st);
@@ -265,7 +267,7 @@ struct Entry {
 // An entry point that ENQUEUES on the caller's stream: Entry, then the stream is noted for quiesce() (note_work) -- and `return in.done()` records last_work,
 // after which a resident kernel starts.  Two properties differ from call to call, and each call keeps the value it was written with:
 //   CAPTURE_AWARE  asks whether the stream is recording a graph, and then marks the engine `captured` instead of noting the stream: cw_reset_masked,
-//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_plan, cw_shoot, cw_shoot_actions, cw_shoot_refit, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_replay_clear, cw_replay_push, cw_replay_sample, cw_export_onehot_states, cw_render_records,
+//                  cw_imagine_masked, cw_sample_state_masked, cw_snapshot_save / _load, cw_expand, cw_simulate, cw_unroll, cw_plan, cw_shoot, cw_shoot_actions, cw_shoot_refit, cw_seen_clear, cw_seen_insert, cw_reach, cw_load_records, cw_replay_clear, cw_replay_push, cw_replay_sample, cw_export_onehot_states, cw_render_records,
 //                  cw_rollout.  ANY_STREAM notes the stream regardless: cw_reset, cw_render, cw_render_onehot, cw_export_grid, cw_export_onehot(_of).
 //   LAST_WORK      records the event: cw_reset and every CAPTURE_AWARE call but cw_rollout.  NO_LAST_WORK: cw_rollout and the ANY_STREAM readers.
 enum Capture { ANY_STREAM, CAPTURE_AWARE };
@@ -1011,6 +1013,43 @@ int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, cons
     O.ret = out->ret; O.length = out->length; O.done = out->done; O.achieved = out->achieved;
     O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.rewards = out->rewards; O.dones = out->dones;
     HIP_TRY(cwk_launch_simulate(&e->P, env_of, h, p, hdr_in ? 0 : 1, n_states, actions, n_steps, stop_at_done ? 1 : 0, &O, (hipStream_t)stream));
+    return in.done();
+}
+
+// ------------------------------------------------------------------------------ unroll: cw_simulate with every record along the way written out
+// cw_simulate's shape: checks (cwh_unroll_args: cw_simulate's rules and the cap on one launch's rows; alignment; no output may share a byte with the records
+// read, the actions, env_of or another output), then ONE kernel.  Writes nothing of the engine but counters[7].
+int cw_unroll(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states, const uint8_t *actions,
+              int32_t n_steps, int32_t stop_at_done, const cw_unroll_out *out, cw_stream_t stream)
+{
+    if (!e || !out || !actions) return fail(CW_ERR_INVALID, "cw_unroll: null %s", !e ? "engine" : !out ? "out" : "actions");
+    const int n_fields = !!out->hdr + !!out->slot_pos + !!out->reward + !!out->done + !!out->changed + !!out->taken + !!out->length;
+    if (cwh_unroll_args(e->n, env_of != nullptr, hdr_in != nullptr, slot_pos_in != nullptr, n_states, n_steps, n_fields) == CWH_REC_UNROLL_ROWS)
+        return fail(CW_ERR_INVALID, "cw_unroll: (n_steps + 1) = %d times n_states = %d is above %d records in one call", n_steps + 1, n_states, CWH_MAX_STATES);
+    const int bad = records_args("cw_unroll", e, env_of, hdr_in, slot_pos_in, n_states, n_steps, CWH_SIM_MAX_STEPS, true, n_fields, out->hdr, out->slot_pos);
+    if (bad != CW_OK) return bad;
+    // the records the kernel reads: the caller's n_states, or the engine's own num_envs
+    const uint4 *const h = hdr_in ? (const uint4 *)hdr_in : e->P.hdr, *const p = hdr_in ? (const uint4 *)slot_pos_in : e->P.pos;
+    const uint64_t m = (uint64_t)n_states, in_bytes = 16ull * (uint64_t)(hdr_in ? n_states : e->n), steps = (uint64_t)n_steps * m, rows = steps + m;
+    static const char *const out_names[7] = {"hdr", "slot_pos", "reward", "done", "changed", "taken", "length"};
+    static const char *const in_names[4] = {"the records read", "the records read", "actions", "env_of"};
+    const cwh_span outs[7] = {{addr(out->hdr), 16 * rows, 16}, {addr(out->slot_pos), 16 * rows, 16}, {addr(out->reward), 4 * steps, 4}, {addr(out->done), steps, 1},
+                              {addr(out->changed), steps, 1}, {addr(out->taken), steps, 1}, {addr(out->length), 4 * m, 4}};
+    const cwh_span ins[4] = {{addr(h), in_bytes, 16}, {addr(p), in_bytes, 16}, {addr(actions), steps, 1}, {addr(env_of), 4 * m, 4}};
+    int at = cwh_spans_misaligned(outs, 7);
+    if (at >= 0) return fail(CW_ERR_INVALID, "cw_unroll: out->%s is not %d-byte aligned", out_names[at], (int)outs[at].align);
+    if (cwh_spans_misaligned(ins, 4) >= 0) return fail(CW_ERR_INVALID, "cw_unroll: env_of is not 4-byte aligned");      // (the records: records_args)
+    int other = 0;
+    at = cwh_spans_clash(outs, 7, ins, 4, 1, &other);
+    if (at >= 0) return fail(CW_ERR_INVALID, "cw_unroll: out->%s overlaps %s%s", out_names[at], other < 4 ? "" : "out->", other < 4 ? in_names[other] : out_names[other - 4]);
+    if (!e->has_reset) return fail(CW_ERR_STATE, "cw_unroll called before cw_reset");
+    if (n_states == 0) return CW_OK;
+    EnqueueEntry in(e, stream, CAPTURE_AWARE, LAST_WORK);
+    if (in.rc != CW_OK) return in.rc;
+    CwUnrollOut O;
+    O.hdr = (uint4 *)out->hdr; O.pos = (uint4 *)out->slot_pos; O.reward = out->reward; O.done = out->done; O.changed = out->changed; O.taken = out->taken;
+    O.length = out->length;
+    HIP_TRY(cwk_launch_unroll(&e->P, env_of, h, p, hdr_in ? 0 : 1, n_states, actions, n_steps, stop_at_done ? 1 : 0, &O, (hipStream_t)stream));
     return in.done();
 }
 

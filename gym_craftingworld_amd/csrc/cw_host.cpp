@@ -204,6 +204,14 @@ int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot
     return rc;
 }
 
+int cwh_unroll_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields)
+{
+    const int rc = cwh_records_args(num_envs, has_env_of, has_hdr_in, has_slot_pos_in, n_states, n_steps, n_out_fields, CWH_SIM_MAX_STEPS, 1);
+    if (rc == CWH_REC_NO_FIELD || rc == CWH_REC_N_STATES || rc == CWH_REC_N_STEPS) return rc;
+    if (((uint64_t)n_steps + 1u) * (uint64_t)n_states > (uint64_t)CWH_MAX_STATES) return CWH_REC_UNROLL_ROWS;      // (<= 2^15 * 2^27)
+    return rc;
+}
+
 int cwh_shoot_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int32_t n_samples,
                    int n_out_fields)
 {

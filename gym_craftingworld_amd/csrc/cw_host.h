@@ -151,6 +151,11 @@ int cwh_records_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_s
 #define CWH_PLAN_MAX_LEAVES (1ull << 32)
 enum { CWH_REC_PLAN_WORK = 7 };
 int cwh_plan_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t depth, int n_out_fields);
+// ... and of cw_unroll: cwh_records_args as cw_simulate calls it (1 <= n_steps <= CWH_SIM_MAX_STEPS, its own states broadcast), and behind the step check and
+// before the pointer rules the cap on the rows of ONE launch: (n_steps + 1) * n_states <= CWH_MAX_STATES (CWH_REC_UNROLL_ROWS) -- the whole [T + 1][M] record
+// array is then a legal input, flattened, to every call that reads records, and each record array stays at or below 2 GiB.
+enum { CWH_REC_UNROLL_ROWS = 8 };
+int cwh_unroll_args(int32_t num_envs, int has_env_of, int has_hdr_in, int has_slot_pos_in, int32_t n_states, int32_t n_steps, int n_out_fields);
 // the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte (an empty range shares none; a range that would wrap ends at the top of the address space)
 int cwh_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes);
 

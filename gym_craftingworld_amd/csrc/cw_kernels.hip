@@ -20,6 +20,8 @@
 //   cw_render_records_kernel  the frames of such records in the engine's raster, one wave per state (paint_state_frame); writes nothing of the engine.
 //   cw_simulate_kernel  T steps of M such states along M action sequences of the caller's, one lane per state, the state in registers throughout, the
 //                     action bytes fetched a block of steps ahead; writes nothing of the engine.
+//   cw_unroll_kernel  cw_simulate_kernel with the record after every step written out, step-major, two 16-byte stores a lane and step; writes nothing of
+//                     the engine.
 //   cw_plan_kernel    the best return within D steps after each first action of M such states and the plan that reaches it: one lane per (first action,
 //                     state) pair, a depth-first search with its stack in registers and a wave-uniform action at every level; writes nothing of the engine.
 //   cw_shoot_kernel   random shooting: the best of K sampled T-step plans of M such states, the actions drawn where they are used by a counter-based
@@ -775,6 +777,84 @@ __global__ __launch_bounds__(256) void cw_simulate_kernel(CwParams P, const int3
     if (O.achieved) O.achieved[j] = (uint16_t)(h.y & 0xFFFFu);
     if (O.hdr) O.hdr[j] = h;
     if (O.pos) O.pos[j] = pack_pos(sp);
+}
+
+// ------------------------------------------------------------------------------------ unroll
+// cw_unroll: cw_simulate with EVERY record along the way written out -- the same lane per state, the same registers, the same action bytes fetched one
+// block ahead, the same freezing by selection; what is new is the stores.  Row 0 (the record as read) is stored before the loop; after step t every lane of
+// the wave stores row t + 1 as two 16-byte stores (step-major: one contiguous KiB per wave and array) and its four trace values (one contiguous run per wave
+// each).  ALL LANES STORE EVERY ROW, with selected values -- a frozen lane stores its frozen record again and zeros in the traces --, so a wave never
+// diverges on a store; which fields are written is uniform (a null pointer).  A wave whose lanes have all ended leaves at the next block boundary, and the
+// tail loop writes the rows that remain: the frozen record repeated, zeros in the traces.  The row offsets are 64-bit: (T + 1) * M * 16 reaches 2^31.
+// A state that takes no part writes no row of any array.
+__global__ __launch_bounds__(256) void cw_unroll_kernel(CwParams P, const int32_t *__restrict__ env_of, const uint4 *__restrict__ hdr_in,
+                                                        const uint4 *__restrict__ pos_in, int own, int n_states, const uint8_t *__restrict__ actions,
+                                                        int T, int stop_at_done, CwUnrollOut O)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);          // ((T + 1) * n_states <= 2^27)
+    const int env = state_env(P, env_of, j, n_states, true);
+    if (env < 0) return;
+    const size_t M = (size_t)n_states;
+    const int src = own ? env : j;
+    uint4 h = hdr_in[src];
+    uint32_t sp[8];
+    const uint4 pos0 = pos_in[src];
+    unpack_pos(pos0, sp);
+    const uint4 ip = P.init_pos[env];
+    const uint8_t *const ap = actions + j;
+    uint32_t raw[CW_SIM_BLOCK];
+#pragma unroll
+    for (int k = 0; k < CW_SIM_BLOCK; k++) raw[k] = ap[(size_t)min(k, T - 1) * M];
+    if (O.hdr) O.hdr[j] = h;                                              // row 0: the record as read, byte for byte
+    if (O.pos) O.pos[j] = pos0;
+    int32_t length = T;
+    bool active = true, any_done = false;
+    int t0 = 0;
+    for (; t0 < T; t0 += CW_SIM_BLOCK) {
+        const uint32_t lo = raw[0] | (raw[1] << 8) | (raw[2] << 16) | (raw[3] << 24), hi = raw[4] | (raw[5] << 8) | (raw[6] << 16) | (raw[7] << 24);
+        if (t0 + CW_SIM_BLOCK < T) {                                      // the next block's bytes: in flight while this block steps
+#pragma unroll
+            for (int k = 0; k < CW_SIM_BLOCK; k++) raw[k] = ap[(size_t)min(t0 + CW_SIM_BLOCK + k, T - 1) * M];
+        }
+        if (stop_at_done && !CW_BALLOT(active)) break;                    // every state of the wave has ended
+        const int n = min(CW_SIM_BLOCK, T - t0);
+        for (int k = 0; k < n; k++) {
+            const int t = t0 + k;
+            const int a = (int)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xFFu);
+            uint4 h2 = h;
+            uint32_t sp2[8];
+#pragma unroll
+            for (int s = 0; s < 8; s++) sp2[s] = sp[s];
+            const CwStepOut o = step_env(P, h2, sp2, a, [&]() { return ip; });
+            const bool done_now = active && o.done;
+            h.x = active ? h2.x : h.x; h.y = active ? h2.y : h.y; h.z = active ? h2.z : h.z; h.w = active ? h2.w : h.w;      // (word by word: registers)
+#pragma unroll
+            for (int s = 0; s < 8; s++) sp[s] = active ? sp2[s] : sp[s];
+            length = (done_now && !any_done) ? t + 1 : length;
+            any_done = any_done || done_now;
+            const size_t at = (size_t)t * M + j;                          // (row t of the traces; row t + 1 of the records is at + M)
+            if (O.hdr) O.hdr[at + M] = h;
+            if (O.pos) O.pos[at + M] = pack_pos(sp);
+            if (O.reward) O.reward[at] = active ? o.reward : 0;
+            if (O.done) O.done[at] = done_now ? 1 : 0;
+            if (O.changed) O.changed[at] = (active && o.changed) ? 1 : 0;
+            if (O.taken) O.taken[at] = active ? 1 : 0;
+            if (stop_at_done) active = active && !o.done;
+        }
+    }
+    if (t0 < T) {                                                         // (a wave that left early: the rows after every state's end)
+        const uint4 pos = pack_pos(sp);
+        for (int t = t0; t < T; t++) {
+            const size_t at = (size_t)t * M + j;
+            if (O.hdr) O.hdr[at + M] = h;
+            if (O.pos) O.pos[at + M] = pos;
+            if (O.reward) O.reward[at] = 0;
+            if (O.done) O.done[at] = 0;
+            if (O.changed) O.changed[at] = 0;
+            if (O.taken) O.taken[at] = 0;
+        }
+    }
+    if (O.length) O.length[j] = length;
 }
 
 // ------------------------------------------------------------------------------------ plan
@@ -3436,6 +3516,15 @@ hipError_t cwk_launch_step(const CwParams *P, const CwTuning *T, const void *act
 hipError_t cwk_launch_refill(const CwParams *P, const CwTuning *T, int all_envs, hipStream_t st)
 {
     hipLaunchKernelGGL(cw_refill_kernel, dim3(cw_reset_grid(*T, P->n_envs)), dim3(CW_RESET_WAVES * CW_WAVE), 0, st, *P, all_envs);
+    return hipGetLastError();
+}
+
+// cw_unroll: one launch, one lane per state
+hipError_t cwk_launch_unroll(const CwParams *P, const int32_t *env_of, const uint4 *hdr, const uint4 *pos, int own, int n_states, const uint8_t *actions,
+                             int n_steps, int stop_at_done, const CwUnrollOut *O, hipStream_t st)
+{
+    hipLaunchKernelGGL(cw_unroll_kernel, dim3((unsigned)((n_states + 255) / 256)), dim3(256), 0, st, *P, env_of, hdr, pos, own, n_states, actions, n_steps,
+                       stop_at_done, *O);
     return hipGetLastError();
 }
 

@@ -191,6 +191,18 @@ struct CwSimulateOut {
     uint8_t *dones;          // [T][M]
 };
 
+// Where cw_unroll_kernel leaves EVERY record along T steps of M states (the public cw_unroll_out with the records typed), step-major.  A null field is not
+// written.
+struct CwUnrollOut {
+    uint4 *hdr;              // [T + 1][M] row 0: the record as read, row t + 1: the record after step t (a step not taken repeats the row before it)
+    uint4 *pos;              // [T + 1][M]
+    int32_t *reward;         // [T][M] 0 for a step not taken
+    uint8_t *done;           // [T][M]
+    uint8_t *changed;        // [T][M] the step changed the state
+    uint8_t *taken;          // [T][M] 1: the step was taken
+    int32_t *length;         // [M] 1 + index of the first done step, T if none
+};
+
 // Where cw_plan_kernel leaves the best plan of each (first action, state) pair (the public cw_plan_out with the records typed): ACTION-MAJOR like CwExpandOut,
 // row a * M + j.  A null field is not written.
 struct CwPlanOut {

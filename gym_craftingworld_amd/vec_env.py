@@ -335,6 +335,22 @@ def simulate_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of):
     return _simulate_tm(num_envs, shape, dtype, None if hdr is None else m)
 
 
+UNROLL_FIELDS = ('hdr', 'slot_pos', 'reward', 'done', 'changed', 'taken', 'length')
+UNROLL_MAX_ROWS = 2 ** 27
+
+
+def _unroll_rows(T, m):
+    """cw_unroll's cap on one launch: the [T + 1, M] record arrays hold at most 2**27 records"""
+    if (T + 1) * m > UNROLL_MAX_ROWS:
+        raise ValueError('(T + 1) * M = %d * %d records: at most 2**27 in one call' % (T + 1, m))
+    return T, m
+
+
+def unroll_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of):
+    """What cw_unroll is handed, validated on the host: -> (T, M).  simulate_args' rules, and (T + 1) * M <= 2**27: ValueError beyond it."""
+    return _unroll_rows(*simulate_args(num_envs, actions_shape_dtype, hdr, slot_pos, env_of))
+
+
 PLAN_FIELDS = ('q', 'length', 'done', 'achieved_mask', 'hdr', 'slot_pos', 'plan', 'best_action', 'best_q')
 PLAN_MAX_DEPTH, PLAN_MAX_LEAVES = 8, 2 ** 32
 
@@ -949,7 +965,7 @@ class CraftingWorldVecEnv:
     # ------------------------------------------------------------------ looking one step ahead
     @property
     def expand_skipped(self):
-        """how many states expand(), simulate(), plan() and shoot() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
+        """how many states expand(), simulate(), unroll(), plan() and shoot() have skipped so far for an env index >= num_envs (counters[7]; reading it synchronises)"""
         return int(self._counters_raw[7].item())
 
     def _records(self, hdr, slot_pos, env_of):
@@ -1030,6 +1046,42 @@ class CraftingWorldVecEnv:
         out = self._out_dict(out, names, spec)
         if m:
             self._call('cw_simulate', env_of, hdr, slot_pos, m, actions, T, 1 if stop_at_done else 0, C.byref(_out_struct(L.cw_simulate_out, out)), keep=out)
+        return out
+
+    # ------------------------------------------------------------------ whole trajectories
+    def unroll(self, actions, hdr=None, slot_pos=None, env_of=None, *, stop_at_done=True, fields=None, out=None):
+        """Which states does this plan pass through?  (cw_unroll: simulate()'s kernel with the record after EVERY step written out -- one launch, no host
+        round trip, no synchronisation, capturable; no env is touched and no RNG stream drawn from.)  The arguments are simulate()'s, rule for rule:
+        actions uint8 [T, M] (an id above 5 is the no-op), without records the envs' current states BROADCAST ([T, K * N] or [T, K, N]: plan k of env i
+        in column k * N + i), with hdr [..., 16] / slot_pos [..., 8] / env_of the caller's states, one column per record (a negative env_of entry takes
+        no part and NO row of it is written at any step; an entry >= num_envs is skipped by the kernel and counted in expand_skipped).  (T + 1) * M
+        <= 2**27 in one call.  -> a dict of device tensors, STEP-MAJOR, the states flattened to M as simulate() returns them:
+        'hdr' uint8 [T + 1, M, 16] / 'slot_pos' int16 [T + 1, M, 8]: row 0 is the state as read, row t + 1 the state after step t -- byte for byte
+        expand()'s successor of row t for actions[t], and row T simulate()'s final record; 'reward' int32 [T, M], 'done' / 'changed' / 'taken' bool
+        [T, M] (simulate()'s traces; expand()'s `changed`; taken: the step was taken); 'length' int32 [M] (simulate()'s).  stop_at_done=True: a step is
+        taken iff no earlier step of its state returned done; a step not taken has reward 0, done / changed / taken False, and its row repeats the row
+        before it, so the final record repeats to row T.  False: every step is taken.  The achieved mask after step t is bytes 4-5 of hdr[t + 1].
+        fields: a subset of UNROLL_FIELDS (default all).  out: a dict returned by an earlier call with the same T, M and fields, written again.
+        The slices callers want, with r = env.unroll(actions):
+            r['hdr'][:-1] (and r['slot_pos'][:-1]) with actions are the (s_t, a_t) pairs;
+            r['hdr'][1:] are the successors;
+            env.render_records(r['hdr'][1:].reshape(-1, 16), r['slot_pos'][1:].reshape(-1, 8), mask=r['taken'].reshape(-1)) paints the frames of
+            the steps taken."""
+        names = _field_names(fields, UNROLL_FIELDS, UNROLL_FIELDS)
+        own = hdr is None and slot_pos is None
+        m, _, hdr, slot_pos, env_of = self._records(hdr, slot_pos, env_of)
+        if self._in_place(actions, (torch.uint8,)):
+            T, m = _unroll_rows(*_simulate_tm(self.num_envs, actions.shape, np.uint8, None if own else m))
+        else:
+            a = as_numpy(actions)
+            T, m = _unroll_rows(*_simulate_tm(self.num_envs, a.shape, a.dtype, None if own else m))
+            actions = torch.as_tensor(simulate_actions(a)).to(self.device)
+        spec = {'hdr': ((T + 1, m, 16), torch.uint8), 'slot_pos': ((T + 1, m, 8), self.slot_pos.dtype), 'reward': ((T, m), torch.int32),
+                'done': ((T, m), torch.bool), 'changed': ((T, m), torch.bool), 'taken': ((T, m), torch.bool), 'length': ((m,), torch.int32)}
+        out = self._out_dict(out, names, spec)
+        if m:
+            self._call('cw_unroll', env_of, hdr, slot_pos, m, actions, T, 1 if stop_at_done else 0, C.byref(_out_struct(L.cw_unroll_out, out)), sync=False,
+                       keep=out)                                  # (device tensors, nothing a host reads next: no synchronisation, host_outputs engines included)
         return out
 
     # ------------------------------------------------------------------ searching every plan

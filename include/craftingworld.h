@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define CW_ABI_VERSION 5   /* 5: cw_buffer_table.episode_return, cw_get_fixed_states (and, added since without a new number: cw_reset_masked, cw_imagine_masked, cw_sample_state_masked, cw_snapshot_reserve, cw_snapshot_save,
-                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; then cw_refit_out, cw_shoot_refit; then cw_replay_table, cw_replay_out, cw_replay_reserve, cw_replay_bytes, cw_replay_buffers, cw_replay_clear, cw_replay_push, cw_replay_sample; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
+                            * cw_snapshot_load, cw_snapshot_row_bytes, cw_expand, cw_export_onehot_states, cw_simulate_out, cw_simulate), then cw_render_records, then cw_plan_out, cw_plan; then cw_shoot_out, cw_shoot, cw_shoot_actions; then cw_seen_out, cw_seen_reserve, cw_seen_clear, cw_seen_insert, cw_seen_counters, cw_seen_slots; then cw_reach_out, cw_reach_reserve, cw_reach_bytes, cw_reach; then cw_load_records; then cw_refit_out, cw_shoot_refit; then cw_replay_table, cw_replay_out, cw_replay_reserve, cw_replay_bytes, cw_replay_buffers, cw_replay_clear, cw_replay_push, cw_replay_sample; then cw_unroll_out, cw_unroll; 4: cw_tuner_state, one painter, look-ahead records.  Round 6 changed no
                             * signature or struct: cw_get_mt reports numpy's own (key, pos) form, cw_rollout issues one launch per max_steps steps, checkpoint blobs
                             * are version 4 (a ring of look-ahead records per env; older blobs are refused with CW_ERR_INVALID), hdr flags bits 2-15 count successes */
 #define CW_MT_N 624        /* MT19937 words per env (numpy RandomState key)        */
@@ -127,7 +127,7 @@ typedef struct cw_buffer_table {
                               *      8 words: [4] is the engine's own (the finished count the last sweep of the observation array saw --
                               *      the sweep paces its first jobs by what the step before it did), [5] counts resets of a look-ahead engine that
                               *      found no record waiting (performance diagnostics), [6] counts the envs a snapshot or record load skipped
-                              *      (cw_snapshot_save / cw_snapshot_load: a bad row number; cw_load_records: an index out of range or a refused record), [7] counts the states skipped by cw_expand, cw_simulate, cw_plan or cw_shoot for an env index at or above num_envs.
+                              *      (cw_snapshot_save / cw_snapshot_load: a bad row number; cw_load_records: an index out of range or a refused record), [7] counts the states skipped by cw_expand, cw_simulate, cw_unroll, cw_plan or cw_shoot for an env index at or above num_envs.
                               *      Read-only for callers. */
     size_t frame_bytes;      /* P*P*3 (CW_RASTER_RAY) or (3S+3)*3S*3 (CW_RASTER_ALT) */
     int32_t *host_actions;   /* [N]  cw_config.host_outputs only (else NULL): mapped host buffer usable as cw_step's actions (CW_ACT_I32) */
@@ -358,6 +358,44 @@ typedef struct cw_simulate_out {  /* DEVICE pointers (host_outputs engines: or G
 int cw_simulate(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states,
                 const uint8_t *actions /* DEVICE uint8 [n_steps][n_states] */, int32_t n_steps, int32_t stop_at_done,
                 const cw_simulate_out *out, cw_stream_t stream);
+
+/* --- whole trajectories: cw_simulate with EVERY record along the way written out -- the states of a plan, not only its end (imitation data from the planners,
+ * value targets along a plan, the frames of a whole trajectory through cw_render_records, any step of a plan as a start state through cw_load_records).
+ * M = n_states, T = n_steps; the records are step-major, row t of state j at [t * M + j]. */
+typedef struct cw_unroll_out {   /* DEVICE pointers (host_outputs engines: or GPU-mapped host memory); NULL = not written; all NULL: CW_ERR_INVALID */
+    uint8_t  *hdr;       /* [T+1][M][16]  row 0: the record as read; row t+1: the record after step t; 16-byte aligned */
+    uint16_t *slot_pos;  /* [T+1][M][8]   16-byte aligned */
+    int32_t  *reward;    /* [T][M]  */
+    uint8_t  *done;      /* [T][M]  */
+    uint8_t  *changed;   /* [T][M]  the step changed the state (cw_expand's `changed`) */
+    uint8_t  *taken;     /* [T][M]  1: step t was taken; goes into cw_render_records as a mask for rows 1..T */
+    int32_t  *length;    /* [M]     cw_simulate's length */
+} cw_unroll_out;
+/* The inputs are cw_simulate's, rule for rule: hdr_in == NULL broadcasts the engine's own states (n_states a positive multiple of num_envs, state j is env
+ *   j % num_envs); otherwise the caller's records with env_of NULL or DEVICE int32[M] -- a negative entry: the state takes no part and NO row of it is
+ *   written at any t; an entry >= num_envs is skipped the same way and counted once in counters[7].  An action id above 5 is the no-op: step_num + 1,
+ *   reward -1, changed 0.
+ * The outputs, by equalities with the calls that exist:
+ *   reward, done and length equal cw_simulate's rewards, dones and length for the same arguments.
+ *   Row T of hdr / slot_pos equals cw_simulate's hdr / slot_pos byte for byte.  Row 0 is the record read, byte for byte -- with broadcast states the
+ *     engine's records tiled.
+ *   For a TAKEN step t with action a <= 5, row t+1 is byte for byte cw_expand's successor (a, .) of row t, and changed[t] is its `changed`.
+ *   stop_at_done != 0: step t is taken iff no earlier step of that state returned done.  For a step NOT taken reward, done, changed and taken are all 0 and
+ *     row t+1 equals row t, so the final record repeats to row T.  stop_at_done == 0: every step is taken.
+ *   The achieved mask after step t is bytes 4-5 of hdr[t+1]; there is no separate field.
+ * ONE LAUNCH STAYS BOUNDED: (n_steps + 1) * n_states <= 2^27.  The whole [T+1][M] record array is then a legal input, flattened, to cw_render_records,
+ *   cw_export_onehot_states, cw_seen_insert and cw_load_records, and each record array stays at or below 2 GiB.
+ * PURE: nothing of the engine is written except counters[7], and that only for a skipped state; nothing is drawn from any RNG stream.
+ * Enqueues ONE kernel (cw_unroll_kernel: one lane per state, the state in registers for all T steps, two 16-byte stores a lane and step) on `stream` -- no
+ *   host synchronisation, no allocation -- and can be captured into a HIP graph.  Every obs_mode, with and without auto_reset, host_outputs engines included.
+ *   n_states == 0 (with hdr_in): CW_OK, nothing enqueued.  Errors, tested in this order -- CW_ERR_INVALID: a null engine, out or actions; all seven fields
+ *   NULL, n_states < 0 or above 2^27, n_steps < 1 or above 32 767, (n_steps + 1) * n_states above 2^27, hdr_in without slot_pos_in or the reverse, env_of
+ *   without hdr_in, n_states not a positive multiple of num_envs without hdr_in; a misaligned hdr_in / slot_pos_in / out->hdr / out->slot_pos (16 bytes),
+ *   out->reward / out->length / env_of (4 bytes); an output sharing a byte with the records read, actions, env_of or another output.  Then CW_ERR_STATE
+ *   before the first cw_reset / cw_checkpoint_load.  (Not timed yet: tools/measure_unroll.py.) */
+int cw_unroll(cw_engine *e, const int32_t *env_of, const uint8_t *hdr_in, const uint16_t *slot_pos_in, int32_t n_states,
+              const uint8_t *actions /* DEVICE uint8 [n_steps][n_states] */, int32_t n_steps, int32_t stop_at_done,
+              const cw_unroll_out *out, cw_stream_t stream);
 
 /* --- searching every plan: the best that can be done from a state within D steps, and which action starts it (the exhaustive receding-horizon controller:
  * an expert for imitation, an optimal-within-horizon baseline, an exact ranking of the six actions, the "goal reachable within D steps" label).
