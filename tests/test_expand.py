@@ -4,7 +4,6 @@ set_state + step, every row that must not be written against a sentinel, and the
 bit-exact.  No timing."""
 import ctypes as C
 import functools
-from itertools import product
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ from masked_check import spread, take
 from oracle_replay import make_env, np_states, one_hot_of, same
 from records_check import DENSE, POS_HELD, decode
 from records_gpu import SENT, caller_records, env_of_cases, host as _host, sentinel_out, walked_engine
-from state_tables import oracle_frame as _oracle_frame, table_coverage, table_desired, wall_table
+from state_tables import local_table as _table, oracle_frame as _oracle_frame, table_coverage, table_desired, wall_table
 
 pytestmark = pytest.mark.gpu
 
@@ -35,41 +34,6 @@ def _dense_of(snap):
 
 # ------------------------------------------------------------------------------------------------------------------------------ 1. the whole local transition table
 S1, MAX1 = 5, 9
-DR = [(-1, 0), (0, 1), (1, 0), (0, -1)]
-
-
-@functools.lru_cache(maxsize=None)
-def _table():
-    """The states of test_hip_parity.test_systematic_transition_table without its action dimension: (object in the target cell 0..8) x (object under the
-    agent) x (hold) x (the side 0..3 on which the target cell lies) x (where the init grid put sticks / axe / hammer / tree relative to the two cells) x
-    (achieved bits) x (agent interior / in the corner); target and under never the same non-empty code.  -> grid, init_grid [n, 5, 5], agent [n, 2], hold,
-    achieved [n]"""
-    S = S1
-    cases = []
-    for tgt, under, hold, side, initv, achv, wall in product(range(9), (0, 1, 2, 3, 7, 8), range(4), range(4), range(4), range(3), (0, 1)):
-        if tgt and tgt == under:
-            continue
-        ar, ac = (0, 0) if wall else (2, 2)
-        g = np.zeros((S, S), np.uint8)
-        g[ar, ac] = under
-        tr, tc = ar + DR[side][0], ac + DR[side][1]
-        if 0 <= tr < S and 0 <= tc < S:
-            g[tr, tc] = tgt
-        else:
-            tr, tc = ar, ac                      # the wall: target == own cell
-        ig = np.zeros((S, S), np.uint8)          # one of each object; objects 1, 2, 3, 5 placed per initv
-        spots = {0: [(4, 0), (4, 1), (4, 2), (4, 3)],
-                 1: [(tr, tc), (4, 1), (4, 2), (4, 3)],
-                 2: [(4, 0), (tr, tc), (4, 2), (4, 3)] if hold != 3 else [(4, 0), (4, 1), (tr, tc), (4, 3)],
-                 3: [(4, 0), (4, 1), (4, 2), (tr, tc)]}[initv]
-        for code, (r, c) in zip((1, 2, 3, 5), spots):
-            ig[r, c] = code
-        for code, (r, c) in zip((4, 6, 7, 8), [(3, 4), (2, 4), (1, 4), (0, 4)]):
-            ig[r, c] = code
-        cases.append((g, ig, (ar, ac), hold, (0, 1 << 3, 0x1FF)[achv]))
-    assert len(cases) == 18816
-    return (np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), np.array([c[2] for c in cases], np.int64),
-            np.array([c[3] for c in cases], np.int64), np.array([c[4] for c in cases], np.int64))
 
 
 @functools.lru_cache(maxsize=None)

@@ -3,6 +3,9 @@
 step, on many seeds and configs -- a wider net than the committed fixtures.  Compares reward, done,
 achieved/desired vectors, one-hot state, observation / desired_goal / init_observation images and
 the MT19937 state after every reset.  Prints a summary; exits non-zero on the first mismatch.
+Its states are the ones random and scripted trajectories visit; the whole transition tables are compared with the reference by
+tools/gen_table_golden.py, whose recorded answers the suite checks on the CPU and on the GPU (tests/test_oracle_table.py,
+tests/test_reference_table.py).
 
     python tools/diff_vs_reference.py [n_seeds [ray|alt|flat|onehot ...]]
 """
